@@ -15,6 +15,11 @@ all-reduced (MIN of probabilities) and the gradients are all-reduced (AVG) over 
 before Adam, so every replica applies the identical update.
 
 Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md §6).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the
+passes that take runs of their own (the staged data-parallel point, the section profiler
+behind `kernels` / `roofline` / `gpu_busy_ms_per_step`, the CPU baseline); --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy.
 """
 
 from __future__ import annotations
@@ -72,14 +77,50 @@ def parse():
                    help="after the --warmup steps, further untimed steps until this much warm-up "
                         "time has passed (the GPU's clocks ramp over the first ~20 ms of load); "
                         "the count is reported as settle_steps")
-    p.add_argument("--no-profile", action="store_true", help="skip the profiled pass")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the passes of their own: the "
+                        "dp_staged_ms_per_step pass (dqn), the section-profiler pass (kernels, "
+                        "roofline, gpu_busy_ms_per_step, lstm) and the CPU baseline; without it "
+                        "the run sets up, warms up, times --steps steps and prints the line "
+                        "(those fields null or empty)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (loss, "
+                        "priorities, the updated parameters, ...) as DIR/<name>.npy; the settling "
+                        "steps are then a fixed count, so equal arguments give equal inputs")
+    p.add_argument("--no-profile", action="store_true", help="--full: skip the profiled pass")
     p.add_argument("--profile-steps", type=int, default=50,
-                   help="steps of the separate, untimed section-profiler pass")
+                   help="--full: steps of the separate, untimed section-profiler pass")
     p.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--no-staged", action="store_true",
-                   help="dqn: skip the dp_staged_ms_per_step pass (kernel traces of the fused step)")
+                   help="--full, dqn: skip the dp_staged_ms_per_step pass (kernel traces of the "
+                        "fused step)")
     return p.parse_args()
+
+
+# --dump-outputs: settling steps by count (about --settle-seconds' default of load at each
+# workload's step time), so the number of steps before the dumped one does not depend on the
+# clock.
+DUMP_SETTLE_STEPS = {"dqn": 1000, "d4pg": 3000, "impala": 1000, "r2d2": 100}
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """Writes each array as `path`/<name>.npy (float32, or float64 where it is computed in
+    float64), at most DUMP_MAX_BYTES in all: an array over its even share of the budget is
+    cut to a fixed, seeded sample of its flattened elements (sorted indices)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_model() -> str:
@@ -281,6 +322,17 @@ def setup_dqn(args, world, rank, dev):
                     reissued=learner._reissued,  # noqa: SLF001
                     verdict_timeouts=g["verdict_timeouts"])
     meta["_guard"] = guard
+
+    def outputs():
+        # What a caller of step() is left with: the logged loss, the |td| priorities written
+        # back for the step's batch, and the learner's variables after the update (save()
+        # settles a re-issued step first, as every reader of the learner's state does).
+        state = learner.save()
+        n = learner.native
+        return dict(loss=n.loss, priorities=n.priorities[:B], params=n.params, target=n.target,
+                    adam_m=n.m, adam_v=n.v,
+                    steps=np.array([state["num_steps"], state["optimizer"]["step"]], np.float64))
+    meta["_outputs"] = outputs
     return (learner.step, B, meta, lambda: float(learner.native.loss.item()),
             lambda: cpu_baseline(B, A, args.cpu_baseline_seconds))
 
@@ -459,6 +511,9 @@ def setup_d4pg(args, world, rank, dev):
                 "obs": "f32[24]", "act": "f32[6]", "atoms": 51,
                 "policy": "LayerNormMLP(256,256,256)+tanh", "critic": "LayerNormMLP(512,512,256)+51",
                 "sampler": "uniform", "parallelism": "dp1"})
+    meta["_outputs"] = lambda: dict(
+        critic_loss=learner.native.critic_loss, policy_loss=learner.native.policy_loss,
+        params=learner.native.params, target=learner.native.target)
     return (learner.step, B, meta, lambda: float(learner.native.critic_loss.item()),
             lambda: d4pg_cpu_baseline(B, args.cpu_baseline_seconds))
 
@@ -547,6 +602,7 @@ def setup_impala(args, world, rank, dev):
         config={"workload": "impala_atari_lstm_vtrace (BASELINE configs[3])",
                 "batch_sequences": B, "sequence_length": T, "frames_per_step": B * T,
                 "obs": "uint8[84,84,4]", "num_actions": A, "lstm": H, "parallelism": "dp1"})
+    meta["_outputs"] = lambda: dict(metrics=n.metrics, params=n.params)
     return (step, B * T, meta, lambda: float(n.metrics[0].item()),
             lambda: impala_cpu_baseline(B, T, args.cpu_baseline_seconds))
 
@@ -638,6 +694,8 @@ def setup_r2d2(args, world, rank, dev):
                 "batch_sequences": B, "sequence_length": T, "burn_in": BI, "n_step": 5,
                 "frames_per_step": B * T, "obs": "uint8[84,84,4]", "num_actions": A,
                 "lstm": H, "parallelism": "dp1"})
+    meta["_outputs"] = lambda: dict(loss=n.loss, priorities=n.priorities[:B], params=n.params,
+                                    target=n.target)
     return (step, B, meta, lambda: float(n.loss[0].item()),
             lambda: r2d2_cpu_baseline(2, T, BI, args.cpu_baseline_seconds))
 
@@ -932,6 +990,9 @@ def main():
     if args.workload in ("insert", "impala_actors"):
         if world > 1:
             raise SystemExit(f"the {args.workload} workload is single-GPU")
+        if args.dump_outputs:
+            raise SystemExit(f"--dump-outputs: the {args.workload} workload's steps race host "
+                             "threads, so its outputs do not repeat")
         if args.workload == "insert":
             insert_bench(args, dev)
         else:
@@ -955,7 +1016,12 @@ def main():
     # warm-up have passed; the count is the same on every rank (from the slowest rank's warm-up
     # rate), since every step issues collectives.
     settle = 0
-    if args.settle_seconds > 0 and args.steps > 0:
+    if args.dump_outputs and args.settle_seconds > 0 and args.steps > 0:
+        settle = DUMP_SETTLE_STEPS[args.workload]  # by count: the dumped step is the same step
+        for i in range(settle):
+            step()
+        torch.cuda.synchronize(dev)
+    elif args.settle_seconds > 0 and args.steps > 0:
         spent = time.perf_counter() - tw
         per = spent / max(args.warmup, 1)
         if world > 1:
@@ -997,11 +1063,16 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # before any later pass steps the learner again
+        arrays = meta["_outputs"]()  # on every rank: reading the state may re-issue a step
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
     # The N = 1 point of a scaling curve: a data-parallel rank runs the learner's stages with
     # the collectives between them (DQNLearner._staged_step); the same stages on one GPU with
     # the collectives left out, timed like the line above (separately, after it).
     staged_ms = None
-    if "_set_staged" in meta and world == 1 and args.steps > 0 and not args.no_staged:
+    if (args.full and "_set_staged" in meta and world == 1 and args.steps > 0
+            and not args.no_staged):
         meta["_set_staged"](True)
         for i in range(min(args.warmup, 10)):
             step()
@@ -1015,7 +1086,7 @@ def main():
     # Per-kernel durations come from a separate pass with the in-library section profiler
     # (HIP event pairs on the launch stream), so its event records stay out of the timed
     # region above.
-    if not args.no_profile and args.profile_steps > 0:
+    if args.full and not args.no_profile and args.profile_steps > 0:
         torch.cuda.synchronize(dev)  # prefetched batches land before profiling starts
         L.acme_profile_reset()
         _lib.set_profiling(True)
@@ -1026,7 +1097,7 @@ def main():
     loss = loss_fn()
 
     sections = []
-    for i in range(L.acme_profile_num_sections()):
+    for i in range(L.acme_profile_num_sections() if args.full else 0):
         import ctypes
         nm, ms, cnt = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_int64()
         fl, by = ctypes.c_double(), ctypes.c_double()
@@ -1084,7 +1155,7 @@ def main():
                   file=sys.stderr)
         print(f"[bench] replay fill {t_fill:.1f}s, final loss {loss:.5f}", file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_fn()
     if rank == 0:
         out = {
@@ -1102,7 +1173,7 @@ def main():
         }
         if guard is not None:
             out["step_guard"] = guard
-        if "_lstm_T" in meta:
+        if args.full and "_lstm_T" in meta:
             # The LSTM unroll per timestep (one launch each way) against a dependent kernel
             # boundary on MI355X (1.45 us between trivial kernels, MI355X_MICROARCH.md
             # "boundary"), the floor of one launch per timestep before any work.

@@ -30,6 +30,32 @@ def test_merge_launch_sections_sums_time_and_flops():
     assert m["per_launch"][1]["avg_us"] == 52.0
 
 
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    arrays = dict(loss=torch.tensor([1.5]), priorities=np.arange(4, dtype=np.float64),
+                  counts=np.arange(3, dtype=np.int64), big=np.arange(1000, dtype=np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 400)  # 400 bytes per array: `big` is cut
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert got["loss"].dtype == np.float32 and got["loss"].tolist() == [1.5]
+    assert got["priorities"].dtype == np.float64 and got["priorities"].tolist() == [0, 1, 2, 3]
+    assert got["counts"].dtype == np.float32 and got["counts"].tolist() == [0, 1, 2]
+    assert got["big"].shape == (100,) and (np.diff(got["big"]) > 0).all()  # a sorted sample
+    assert sum(a.nbytes for a in got.values()) <= 4 * 400
+    np.testing.assert_array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))  # fixed
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
 def test_merge_launch_sections_without_the_second_section_is_a_no_op():
     online = _rec("fc_fwd", 100, 43.0, 290.0)
     sections = [online]

@@ -12,7 +12,7 @@ for i in 1 2 3; do
 done
 for v in A B; do
   eval "E=\$$v"
-  env $E timeout -k 10 150 python3 bench.py --workload ${W:-dqn} --no-cpu-baseline --steps 100 --warmup 20 $EXTRA > $O/p_${v}.json 2>$O/p_${v}.err
+  env $E timeout -k 10 150 python3 bench.py --workload ${W:-dqn} --full --no-cpu-baseline --steps 100 --warmup 20 $EXTRA > $O/p_${v}.json 2>$O/p_${v}.err
   python3 -c "
 import json;d=json.load(open('$O/p_${v}.json'))
 print('$v', {k['name']:k['avg_us'] for k in d['kernels'][:14]})"

@@ -17,12 +17,12 @@ mkdir -p gpurun_out
 rm -rf gpurun_out/prof_$W gpurun_out/pmc_fetch_$W gpurun_out/pmc_write_$W
 export ACME_V_SIDE=1
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$W \
-  -- python3 bench.py --workload $W --no-cpu-baseline --steps $STEPS --warmup 5 \
+  -- python3 bench.py --workload $W --full --no-cpu-baseline --steps $STEPS --warmup 5 \
   > gpurun_out/prof_$W.log 2>&1
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch_$W \
-  -- python3 bench.py --workload $W --no-cpu-baseline --steps $PSTEPS --warmup 2 --profile-steps 3 \
+  -- python3 bench.py --workload $W --full --no-cpu-baseline --steps $PSTEPS --warmup 2 --profile-steps 3 \
   > gpurun_out/pmc_fetch_$W.log 2>&1
 timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write_$W \
-  -- python3 bench.py --workload $W --no-cpu-baseline --steps $PSTEPS --warmup 2 --profile-steps 3 \
+  -- python3 bench.py --workload $W --full --no-cpu-baseline --steps $PSTEPS --warmup 2 --profile-steps 3 \
   > gpurun_out/pmc_write_$W.log 2>&1
 echo "profile_round $W done"
