@@ -78,6 +78,17 @@ class D4PGConfig(ctypes.Structure):
                 ("clipping", c_i32), ("layer_norm_epsilon", c_f32)]
 
 
+class DDPGConfig(ctypes.Structure):  # D4PGConfig without num_atoms / vmin / vmax
+    _fields_ = [("obs_dim", c_i32), ("act_dim", c_i32), ("max_batch", c_i32),
+                ("num_policy_layers", c_i32), ("policy_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("num_critic_layers", c_i32), ("critic_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("action_min", c_f32 * D4PG_MAX_ACT), ("action_max", c_f32 * D4PG_MAX_ACT),
+                ("discount", c_f32), ("target_update_period", c_i32),
+                ("policy_learning_rate", c_f32), ("critic_learning_rate", c_f32),
+                ("adam_beta1", c_f32), ("adam_beta2", c_f32), ("adam_epsilon", c_f32),
+                ("clipping", c_i32), ("layer_norm_epsilon", c_f32)]
+
+
 class D4PGBatch(ctypes.Structure):
     _fields_ = [("o_tm1", c_vp), ("a_tm1", c_vp), ("r_t", c_vp), ("d_t", c_vp), ("o_t", c_vp),
                 ("batch", c_i64)]
@@ -290,6 +301,22 @@ _SIGS = {
     "acme_d4pg_num_steps": (c_i64, [c_vp]),
     "acme_d4pg_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_d4pg_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
+                                       ctypes.POINTER(c_i64)]),
+    "acme_ddpg_create": (c_i32, [ctypes.POINTER(DDPGConfig), ctypes.POINTER(c_vp)]),
+    "acme_ddpg_destroy": (c_i32, [c_vp]),
+    "acme_ddpg_flat_size": (c_i64, [c_vp]),
+    "acme_ddpg_policy_size": (c_i64, [c_vp]),
+    "acme_ddpg_num_tensors": (c_i32, [c_vp]),
+    "acme_ddpg_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(ctypes.c_char_p)]),
+    "acme_ddpg_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_ddpg_step": (c_i32, [c_vp, ctypes.POINTER(D4PGBatch), ctypes.POINTER(D4PGOutputs),
+                               c_vp]),
+    "acme_ddpg_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "acme_ddpg_num_steps": (c_i64, [c_vp]),
+    "acme_ddpg_set_num_steps": (c_i32, [c_vp, c_i64]),
+    "acme_ddpg_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
                                        ctypes.POINTER(c_i64)]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),

@@ -18,6 +18,12 @@
 // activate_final); policy head NearZeroInitializedLinear + TanhToSpec
 // (rescaling.py:55-74); critic head DiscreteValuedHead (distributional.py:36-67).
 //
+// DDPG (acme_ddpg_*, acme/agents/tf/ddpg/learning.py:143-237) is the same learner object with
+// a scalar head: the critic is LayerNormMLP(critic_sizes + (1,)), and ddpg_head_td_kernel
+// (head forward, TD loss 0.5 (r + discount d q_t - q_tm1)^2, the head's input gradient)
+// stands where the head GEMMs, the categorical loss kernel and the head's input-gradient
+// problem stand for D4PG; everything else of the step is shared.
+//
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
 // epilogues and masked dgrads; the row-wise work (LayerNorm+tanh, TanhToSpec head,
@@ -99,7 +105,11 @@ struct acme_d4pg {
   double* norm_part = nullptr;            // [2][kNormBlocks]
   float* norms = nullptr;                 // [2] global norms (policy, critic)
   float* loss_tmp = nullptr;              // [2] critic / policy loss
-  float* ce = nullptr;                    // [B] per-row cross-entropy
+  float* ce = nullptr;                    // [B] per-row cross-entropy (DDPG: 0.5 td^2)
+  // DDPG (acme_ddpg_create): the critic ends in one scalar, con.out / ctg.out hold q.
+  bool scalar_head = false;
+  float* td = nullptr;                    // [B] TD error
+  float* dq = nullptr;                    // [2B] dloss/dq (rows < B), 1 (dpg rows)
   int64_t* dev_step = nullptr;            // device mirror of num_steps (Adam t)
   // Captured step graphs, keyed by the batch / output pointers, B and the target copy.
   struct Graph {
@@ -160,7 +170,10 @@ void add_net(acme_d4pg* l, NetDesc& d, const char* prefix, int din, int nl, cons
     d.w[i] = add_tensor(l, q + "/w", {sizes[i - 1], sizes[i]});
     d.b[i] = add_tensor(l, q + "/b", {sizes[i]});
   }
-  const std::string h = std::string(prefix) + "/" + head;
+  // head == nullptr: the output layer is the LayerNormMLP's own last linear (DDPG's critic,
+  // LayerNormMLP(sizes + (1,))).
+  const std::string h = head ? std::string(prefix) + "/" + head
+                             : p + "/mlp/linear_" + std::to_string(nl - 1);
   d.ow = add_tensor(l, h + "/w", {sizes[nl - 1], nout});
   d.ob = add_tensor(l, h + "/b", {nout});
 }
@@ -501,6 +514,90 @@ __global__ void __launch_bounds__(256) d4pg_loss_kernel(
   const float ql = on ? c_logits[(size_t)row * K + lane] : -INFINITY;
   const float tl = on && row < B ? t_logits[(size_t)row * K + lane] : -INFINITY;
   loss_row(ql, tl, row, lane, r, d, values, B, K, discount, dlogits, ce_out);
+}
+
+// ------------------------------------------------------------------ DDPG head + TD loss
+// The scalar critic head of DDPG (acme/agents/tf/ddpg/learning.py:185-198) forward, the TD
+// loss and the head's input gradient in one launch.  One wave per row (4 rows per 256-thread
+// block), lane i takes the float4 column groups i, i + 64, ... of the last hidden layer.
+//   every row : q = h . w + b (lane partials in k order, then the butterfly sum)
+//   rows < B  : q_t from the target critic's row, td = r + discount d q_t - q,
+//               loss[row] = 0.5 td^2 (summed into the loss by adam_clip_kernel), dq = -td / B
+//   rows >= B : dpg rows, dq = d q / d q = 1
+//   dz[row][j] = act'(h[row][j]) * (dq * w[j]): DenseDgrad's epilogue of a K = 1 problem.
+struct HeadTdArgs {
+  const float *h, *w, *b;     // online critic: last hidden [2B][H], head [H], [1]
+  const float *th, *tw, *tb;  // target critic: [B][H], [H], [1]
+  const float *r, *d;         // [B]
+  int B, H, act;
+  float discount;
+  float *q, *tq, *td, *dq, *loss;  // [2B], [B], [B], [2B], [B]
+  float* dz;                       // [2B][H]
+};
+
+__global__ void __launch_bounds__(256) ddpg_head_td_kernel(const HeadTdArgs a) {
+  using f32x4 = gemm::f32x4;
+  constexpr int kV = kMaxWidth / 256;  // float4 groups per lane
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= 2 * a.B) return;  // uniform per wave
+  const int n4 = a.H / 4;
+  const bool td_row = row < a.B;
+  const f32x4* __restrict__ h4 = reinterpret_cast<const f32x4*>(a.h + (size_t)row * a.H);
+  const f32x4* __restrict__ w4 = reinterpret_cast<const f32x4*>(a.w);
+  const f32x4* __restrict__ th4 =
+      reinterpret_cast<const f32x4*>(a.th + (size_t)(td_row ? row : 0) * a.H);
+  const f32x4* __restrict__ tw4 = reinterpret_cast<const f32x4*>(a.tw);
+  // Every load goes out before the first use (clamped indices; unused groups add nothing).
+  f32x4 hv[kV], wv[kV], thv[kV], twv[kV];
+#pragma unroll
+  for (int u = 0; u < kV; ++u) {
+    const int k = min(lane + 64 * u, n4 - 1);
+    hv[u] = h4[k];
+    wv[u] = w4[k];
+    if (td_row) {
+      thv[u] = th4[k];
+      twv[u] = tw4[k];
+    }
+  }
+  float acc = 0.f, tacc = 0.f;
+#pragma unroll
+  for (int u = 0; u < kV; ++u) {
+    if (lane + 64 * u >= n4) break;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = fmaf(hv[u][j], wv[u][j], acc);
+    if (td_row) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tacc = fmaf(thv[u][j], twv[u][j], tacc);
+    }
+  }
+  const float q = wave_sum(acc) + a.b[0];
+  float dq = 1.f;
+  if (td_row) {
+    const float tq = wave_sum(tacc) + a.tb[0];
+    const float pcont = a.discount * a.d[row];
+    const float td = (a.r[row] + pcont * tq) - q;
+    dq = -td / (float)a.B;
+    if (lane == 0) {
+      a.tq[row] = tq;
+      a.td[row] = td;
+      a.loss[row] = 0.5f * td * td;
+    }
+  }
+  if (lane == 0) {
+    a.q[row] = q;
+    a.dq[row] = dq;
+  }
+  f32x4* __restrict__ dz4 = reinterpret_cast<f32x4*>(a.dz + (size_t)row * a.H);
+#pragma unroll
+  for (int u = 0; u < kV; ++u) {
+    const int k = lane + 64 * u;
+    if (k >= n4) break;
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = act_bwd(a.act, hv[u][j], dq * wv[u][j]);
+    dz4[k] = o;
+  }
 }
 
 // ------------------------------------------------------------------ LayerNorm backward
@@ -1057,8 +1154,11 @@ int launch_bwd_last(const char* name, BwdGroup& g, const std::vector<LnReduce>& 
 // gradient and its weight gradient (over the first `wrows` rows).  Leaves dLoss/d(LayerNorm
 // output) in dz[0].
 int lnmlp_backward_mlp(acme_d4pg* l, const NetDesc& d, const Acts& a, float* const* dz, int rows,
-                       int wrows, BwdGroup& g, const char* tag, hipStream_t st) {
-  int rc = launch_bwd(tag, g, st);
+                       int wrows, BwdGroup& g, const char* tag, hipStream_t st,
+                       bool dz_ready = false) {
+  // dz_ready (DDPG: the head kernel wrote dz[nl-1]): what `g` holds rides with the first
+  // layer launch instead of taking one of its own.
+  int rc = dz_ready && d.nl > 1 ? ACME_OK : launch_bwd(tag, g, st);
   for (int i = d.nl - 1; i >= 1 && rc == ACME_OK; --i) {
     add_wgrad(g, a.h[i - 1], wrows, d.sizes[i - 1], dz[i], d.sizes[i], Pm(l, l->grads, d.w[i]),
               Pm(l, l->grads, d.b[i]));
@@ -1132,9 +1232,31 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
     cin[0].head_prm = l->params;
     cin[1].head[0] = {l->ptg.h[pd.nl - 1], l->ptg.t, l->ptg.out};
     cin[1].head_prm = l->target;
-    if ((rc = critic_forward_pair(l, cin, st))) return rc;
+    if (l->scalar_head)
+      rc = lnmlp_forward_pair(l, cd, cin, od, ad, "d4pg_critic_ln", st);
+    else
+      rc = critic_forward_pair(l, cin, st);
+    if (rc) return rc;
   }
-  {
+  BwdGroup g;
+  std::vector<LnReduce> ln;
+  const int cL = cd.nl - 1;
+  if (l->scalar_head) {
+    // DDPG: head forward, TD loss and the head's input gradient in one launch; the head's
+    // weight gradient (one live column) joins the first backward launch.
+    ACME_PROF("ddpg_head_td", st, 2.0 * 5.0 * B * (double)cd.sizes[cL], 0.0);
+    HeadTdArgs a;
+    a.h = l->con.h[cL]; a.w = P(l, l->params, cd.ow); a.b = P(l, l->params, cd.ob);
+    a.th = l->ctg.h[cL]; a.tw = P(l, l->target, cd.ow); a.tb = P(l, l->target, cd.ob);
+    a.r = bt->r_t; a.d = bt->d_t;
+    a.B = B; a.H = cd.sizes[cL]; a.act = act_of_layer(cL); a.discount = l->cfg.discount;
+    a.q = l->con.out; a.tq = l->ctg.out; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
+    a.dz = l->cdz[cL];
+    ddpg_head_td_kernel<<<(unsigned)ceil_div(2 * B, 4), 256, 0, st>>>(a);
+    D4_CHECK();
+    add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dq, 1, Pm(l, l->grads, cd.ow),
+              Pm(l, l->grads, cd.ob));
+  } else {
     ACME_PROF("d4pg_loss", st, 0.0, 0.0);
     d4pg_loss_kernel<<<(unsigned)ceil_div(2 * B, 4), 256, 0, st>>>(
         l->con.out, l->ctg.out, bt->r_t, bt->d_t, l->values, B, cd.nout, l->cfg.discount,
@@ -1143,14 +1265,14 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
   }
   // Critic backward: 2B rows of input gradients (CE rows + dpg rows), weight gradients from
   // the first B.  Launch k carries layer k's input gradient and weight gradient.
-  BwdGroup g;
-  std::vector<LnReduce> ln;
-  const int cL = cd.nl - 1;
-  add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dlogits, cd.nout, Pm(l, l->grads, cd.ow),
-            Pm(l, l->grads, cd.ob));
-  add_dgrad(g, l->dlogits, 2 * B, cd.nout, P(l, l->params, cd.ow), cd.sizes[cL], l->con.h[cL],
-            act_of_layer(cL), l->cdz[cL]);
-  if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, 2 * B, B, g, "d4pg_bwd_head", st)) ||
+  if (!l->scalar_head) {
+    add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dlogits, cd.nout, Pm(l, l->grads, cd.ow),
+              Pm(l, l->grads, cd.ob));
+    add_dgrad(g, l->dlogits, 2 * B, cd.nout, P(l, l->params, cd.ow), cd.sizes[cL], l->con.h[cL],
+              act_of_layer(cL), l->cdz[cL]);
+  }
+  if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, 2 * B, B, g, "d4pg_bwd_head", st,
+                               l->scalar_head)) ||
       (rc = ln_backward(l, cd, l->con, l->cdz[0], 2 * B, B, true, bt->o_tm1, bt->a_tm1, od, ad,
                         l->lnslab, g, ln, st)))
     return rc;
@@ -1257,15 +1379,19 @@ int acme_d4pg_destroy(acme_d4pg* l) {
   return ACME_OK;
 }
 
-int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
+// The learner behind both acme_d4pg_create (categorical head) and acme_ddpg_create (scalar
+// head: cfg->num_atoms = 1, the support unused).
+static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4pg** out) {
   ACME_CHECK_ARG(cfg && out, "null argument");
   ACME_CHECK_ARG(cfg->obs_dim >= 1 && cfg->act_dim >= 1 && cfg->obs_dim + cfg->act_dim <= kMaxIn,
                  "obs_dim + act_dim must be in [2, %d]", kMaxIn);
   ACME_CHECK_ARG(cfg->act_dim <= ACME_D4PG_MAX_ACT, "act_dim must be <= %d", ACME_D4PG_MAX_ACT);
   ACME_CHECK_ARG(cfg->max_batch >= 1 && cfg->max_batch <= 65536, "max_batch must be in [1, 65536]");
-  ACME_CHECK_ARG(cfg->num_atoms >= 2 && cfg->num_atoms <= ACME_D4PG_MAX_ATOMS,
-                 "num_atoms must be in [2, %d]", ACME_D4PG_MAX_ATOMS);
-  ACME_CHECK_ARG(cfg->vmax > cfg->vmin, "vmax must exceed vmin");
+  if (!scalar_head) {
+    ACME_CHECK_ARG(cfg->num_atoms >= 2 && cfg->num_atoms <= ACME_D4PG_MAX_ATOMS,
+                   "num_atoms must be in [2, %d]", ACME_D4PG_MAX_ATOMS);
+    ACME_CHECK_ARG(cfg->vmax > cfg->vmin, "vmax must exceed vmin");
+  }
   ACME_CHECK_ARG(cfg->target_update_period >= 1, "target_update_period must be >= 1");
   for (int n : {cfg->num_policy_layers, cfg->num_critic_layers})
     ACME_CHECK_ARG(n >= 1 && n <= ACME_D4PG_MAX_LAYERS, "layer count must be in [1, %d]",
@@ -1280,6 +1406,7 @@ int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
                    "critic layer sizes must be multiples of 4 in [4, %d]", kMaxWidth);
   acme_d4pg* l = new acme_d4pg();
   l->cfg = *cfg;
+  l->scalar_head = scalar_head;
   auto fail = [&](int code) {
     acme_d4pg_destroy(l);
     return code;
@@ -1288,7 +1415,7 @@ int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
           cfg->act_dim, "near_zero_initialized_linear");
   l->policy_flat = l->flat;
   add_net(l, l->cri, "critic", cfg->obs_dim + cfg->act_dim, cfg->num_critic_layers,
-          cfg->critic_sizes, cfg->num_atoms, "discrete_valued_head/linear");
+          cfg->critic_sizes, cfg->num_atoms, scalar_head ? nullptr : "discrete_valued_head/linear");
   const int B = cfg->max_batch;
   int rc;
   int hmax = 0;
@@ -1316,9 +1443,11 @@ int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
       (rc = dev_alloc(l, &l->norms, 2)) || (rc = dev_alloc(l, &l->loss_tmp, 2)) ||
       (rc = dev_alloc(l, &l->ce, B)) || (rc = dev_alloc(l, &l->dev_step, 1)))
     return fail(rc);
+  if (scalar_head && ((rc = dev_alloc(l, &l->td, B)) || (rc = dev_alloc(l, &l->dq, 2 * B))))
+    return fail(rc);
   // Support: tf.linspace(vmin, vmax, K) (computed in f64, rounded once to f32).
   std::vector<float> vals(cfg->num_atoms), lo(cfg->act_dim), sc(cfg->act_dim);
-  const double step = ((double)cfg->vmax - (double)cfg->vmin) / (cfg->num_atoms - 1);
+  const double step = ((double)cfg->vmax - (double)cfg->vmin) / std::max(cfg->num_atoms - 1, 1);
   for (int i = 0; i < cfg->num_atoms; ++i) vals[i] = (float)((double)cfg->vmin + i * step);
   for (int j = 0; j < cfg->act_dim; ++j) {
     lo[j] = cfg->action_min[j];
@@ -1331,6 +1460,10 @@ int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
     return fail((set_error("hipMemcpy of the D4PG constants failed"), ACME_ERR_HIP));
   *out = l;
   return ACME_OK;
+}
+
+int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
+  return create_learner(cfg, false, out);
 }
 
 int64_t acme_d4pg_flat_size(const acme_d4pg* l) { return l ? l->flat : 0; }
@@ -1431,7 +1564,25 @@ int acme_d4pg_debug_buffer(const acme_d4pg* l, const char* name, const float** o
     const char* n;
     const float* p;
     int64_t c;
-  } items[] = {
+  };
+  if (l->scalar_head) {
+    const Item items[] = {
+        {"p_a", l->pon.out, (int64_t)B * A}, {"t_a", l->ptg.out, (int64_t)B * A},
+        {"c_q", l->con.out, (int64_t)2 * B}, {"t_q", l->ctg.out, (int64_t)B},
+        {"td", l->td, (int64_t)B},           {"dq", l->dq, (int64_t)2 * B},
+        {"dqda", l->dqda, (int64_t)B * A},   {"du", l->du, (int64_t)B * A},
+        {"norms", l->norms, 2},              {"losses", l->loss_tmp, 2},
+    };
+    for (const Item& it : items)
+      if (strcmp(it.n, name) == 0) {
+        *out = it.p;
+        *count = it.c;
+        return ACME_OK;
+      }
+    set_error("unknown debug buffer '%s'", name);
+    return ACME_ERR_INVALID;
+  }
+  const Item items[] = {
       {"p_a", l->pon.out, (int64_t)B * A},      {"t_a", l->ptg.out, (int64_t)B * A},
       {"c_logits", l->con.out, (int64_t)2 * B * K}, {"t_logits", l->ctg.out, (int64_t)B * K},
       {"dlogits", l->dlogits, (int64_t)2 * B * K},  {"dqda", l->dqda, (int64_t)B * A},
@@ -1446,6 +1597,68 @@ int acme_d4pg_debug_buffer(const acme_d4pg* l, const char* name, const float** o
     }
   set_error("unknown debug buffer '%s'", name);
   return ACME_ERR_INVALID;
+}
+
+// ------------------------------------------------------------------ DDPG
+// The same learner object with the scalar head (DDPGLearner._step,
+// acme/agents/tf/ddpg/learning.py:143-237).
+
+int acme_ddpg_create(const acme_ddpg_config* cfg, acme_ddpg** out) {
+  ACME_CHECK_ARG(cfg && out, "null argument");
+  acme_d4pg_config c;
+  memset(&c, 0, sizeof(c));
+  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
+  c.num_policy_layers = cfg->num_policy_layers;
+  c.num_critic_layers = cfg->num_critic_layers;
+  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
+  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
+  c.num_atoms = 1; c.vmin = 0.f; c.vmax = 0.f;
+  memcpy(c.action_min, cfg->action_min, sizeof(c.action_min));
+  memcpy(c.action_max, cfg->action_max, sizeof(c.action_max));
+  c.discount = cfg->discount; c.target_update_period = cfg->target_update_period;
+  c.policy_learning_rate = cfg->policy_learning_rate;
+  c.critic_learning_rate = cfg->critic_learning_rate;
+  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
+  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
+  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
+  acme_d4pg* l = nullptr;
+  const int rc = create_learner(&c, true, &l);
+  if (rc == ACME_OK) *out = reinterpret_cast<acme_ddpg*>(l);
+  return rc;
+}
+
+static acme_d4pg* as_d4pg(acme_ddpg* l) { return reinterpret_cast<acme_d4pg*>(l); }
+static const acme_d4pg* as_cd4pg(const acme_ddpg* l) {
+  return reinterpret_cast<const acme_d4pg*>(l);
+}
+
+int acme_ddpg_destroy(acme_ddpg* l) { return acme_d4pg_destroy(as_d4pg(l)); }
+int64_t acme_ddpg_flat_size(const acme_ddpg* l) { return acme_d4pg_flat_size(as_cd4pg(l)); }
+int64_t acme_ddpg_policy_size(const acme_ddpg* l) { return acme_d4pg_policy_size(as_cd4pg(l)); }
+int32_t acme_ddpg_num_tensors(const acme_ddpg* l) { return acme_d4pg_num_tensors(as_cd4pg(l)); }
+int acme_ddpg_tensor_info(const acme_ddpg* l, int32_t i, int64_t* offset, int64_t* numel,
+                          int32_t* ndim, int64_t* shape4, const char** name) {
+  return acme_d4pg_tensor_info(as_cd4pg(l), i, offset, numel, ndim, shape4, name);
+}
+int acme_ddpg_bind(acme_ddpg* l, float* params, float* target, float* grads, float* adam_m,
+                   float* adam_v) {
+  return acme_d4pg_bind(as_d4pg(l), params, target, grads, adam_m, adam_v);
+}
+int acme_ddpg_step(acme_ddpg* l, const acme_ddpg_batch* batch, const acme_ddpg_outputs* out,
+                   void* stream) {
+  return acme_d4pg_step(as_d4pg(l), batch, out, stream);
+}
+int acme_ddpg_policy(acme_ddpg* l, const float* obs, int64_t rows, int32_t use_target,
+                     float* actions, void* stream) {
+  return acme_d4pg_policy(as_d4pg(l), obs, rows, use_target, actions, stream);
+}
+int64_t acme_ddpg_num_steps(const acme_ddpg* l) { return acme_d4pg_num_steps(as_cd4pg(l)); }
+int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n) {
+  return acme_d4pg_set_num_steps(as_d4pg(l), n);
+}
+int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** out,
+                           int64_t* count) {
+  return acme_d4pg_debug_buffer(as_cd4pg(l), name, out, count);
 }
 
 }  // extern "C"

@@ -659,19 +659,24 @@ def nccl_comm_destroy(comm: int) -> None:
     check(lib().acme_nccl_comm_destroy(ctypes.c_void_p(comm)), "nccl comm destroy")
 
 
-class NativeD4PG:
-    """acme_d4pg learner + its flat buffers (policy tensors first, then critic tensors)."""
+class _NativeActorCritic:
+    """The deterministic-policy-gradient learner handle shared by NativeD4PG and NativeDDPG:
+    flat buffers (policy tensors first, then critic tensors), step, policy.  Subclasses name
+    the C ABI prefix and the config struct, and fill the fields only they have."""
 
-    def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int,
-                 policy_sizes: Sequence[int] = (256, 256, 256),
-                 critic_sizes: Sequence[int] = (512, 512, 256), num_atoms: int = 51,
-                 vmin: float = -150.0, vmax: float = 150.0, action_min=None, action_max=None,
-                 discount: float = 0.99, target_update_period: int = 100,
-                 policy_learning_rate: float = 1e-4, critic_learning_rate: float = 1e-4,
-                 clipping: bool = True, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
-                 adam_epsilon: float = 1e-8, layer_norm_epsilon: float = 1e-5, device=None):
+    _prefix = ""     # "acme_d4pg" / "acme_ddpg"
+    _tag = ""        # error-message tag
+    _config = None   # ctypes config struct
+
+    def _fn(self, name: str):
+        return getattr(lib(), f"{self._prefix}_{name}")
+
+    def _setup(self, *, obs_dim, act_dim, max_batch, policy_sizes, critic_sizes, action_min,
+               action_max, discount, target_update_period, policy_learning_rate,
+               critic_learning_rate, clipping, adam_beta1, adam_beta2, adam_epsilon,
+               layer_norm_epsilon, device, **extra):
         _lib.require_gpu()
-        cfg = _lib.D4PGConfig()
+        cfg = self._config()
         cfg.obs_dim, cfg.act_dim, cfg.max_batch = int(obs_dim), int(act_dim), int(max_batch)
         for n, sizes in (("policy", policy_sizes), ("critic", critic_sizes)):
             if not 1 <= len(sizes) <= _lib.D4PG_MAX_LAYERS:
@@ -690,7 +695,8 @@ class NativeD4PG:
                              (act_dim,))
         for j in range(act_dim):
             cfg.action_min[j], cfg.action_max[j] = float(lo[j]), float(hi[j])
-        cfg.num_atoms, cfg.vmin, cfg.vmax = int(num_atoms), vmin, vmax
+        for k, v in extra.items():  # the fields only this learner has
+            setattr(cfg, k, v)
         cfg.discount, cfg.target_update_period = discount, int(target_update_period)
         cfg.policy_learning_rate, cfg.critic_learning_rate = policy_learning_rate, critic_learning_rate
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
@@ -700,26 +706,25 @@ class NativeD4PG:
         self.obs_dim, self.act_dim, self.max_batch = int(obs_dim), int(act_dim), int(max_batch)
         self.device = torch.device(device or "cuda")
         h = ctypes.c_void_p()
-        L = lib()
         with torch.cuda.device(self.device):
-            check(L.acme_d4pg_create(ctypes.byref(cfg), ctypes.byref(h)), "d4pg create")
+            check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)), f"{self._tag} create")
         self._h = h
-        self.flat_size = int(L.acme_d4pg_flat_size(h))
-        self.policy_size = int(L.acme_d4pg_policy_size(h))
+        self.flat_size = int(self._fn("flat_size")(h))
+        self.policy_size = int(self._fn("policy_size")(h))
         self.tensors: List[Tuple[str, int, Tuple[int, ...]]] = []
-        for i in range(L.acme_d4pg_num_tensors(h)):
+        for i in range(self._fn("num_tensors")(h)):
             off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
             shape = (ctypes.c_int64 * 4)()
             name = ctypes.c_char_p()
-            check(L.acme_d4pg_tensor_info(h, i, ctypes.byref(off), ctypes.byref(numel),
+            check(self._fn("tensor_info")(h, i, ctypes.byref(off), ctypes.byref(numel),
                                           ctypes.byref(nd), shape, ctypes.byref(name)))
             self.tensors.append((name.value.decode(), int(off.value),
                                  tuple(int(shape[k]) for k in range(nd.value))))
         d = self.device
         z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=d)  # noqa: E731
         self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
-        check(L.acme_d4pg_bind(h, ptr(self.params), ptr(self.target), ptr(self.grads),
-                               ptr(self.m), ptr(self.v)), "d4pg bind")
+        check(self._fn("bind")(h, ptr(self.params), ptr(self.target), ptr(self.grads),
+                               ptr(self.m), ptr(self.v)), f"{self._tag} bind")
         self.critic_loss = torch.zeros(1, dtype=torch.float32, device=d)
         self.policy_loss = torch.zeros(1, dtype=torch.float32, device=d)
 
@@ -727,7 +732,7 @@ class NativeD4PG:
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             try:
-                lib().acme_d4pg_destroy(h)
+                self._fn("destroy")(h)
             except Exception:
                 pass
             self._h = None
@@ -736,20 +741,20 @@ class NativeD4PG:
     set_params = NativeDQN.set_params
     get_params = NativeDQN.get_params
 
-    def params_changed(self) -> None:  # the D4PG step reads the f32 buffers directly
+    def params_changed(self) -> None:  # the step reads the f32 buffers directly
         pass
 
     @property
     def num_steps(self) -> int:
-        return int(lib().acme_d4pg_num_steps(self._h))
+        return int(self._fn("num_steps")(self._h))
 
     @num_steps.setter
     def num_steps(self, n: int) -> None:
-        check(lib().acme_d4pg_set_num_steps(self._h, int(n)))
+        check(self._fn("set_num_steps")(self._h, int(n)))
 
     def debug_buffer(self, name: str) -> np.ndarray:
         p, n = ctypes.c_void_p(), ctypes.c_int64()
-        check(lib().acme_d4pg_debug_buffer(self._h, name.encode(), ctypes.byref(p),
+        check(self._fn("debug_buffer")(self._h, name.encode(), ctypes.byref(p),
                                            ctypes.byref(n)))
         return _device_array(p.value, n.value, np.float32, self.device).cpu().numpy().view(
             np.float32).copy()
@@ -769,8 +774,8 @@ class NativeD4PG:
         b.batch = B
         out = _lib.D4PGOutputs()
         out.critic_loss, out.policy_loss = ptr(self.critic_loss), ptr(self.policy_loss)
-        check(lib().acme_d4pg_step(self._h, ctypes.byref(b), ctypes.byref(out),
-                                   stream_ptr(stream)), "d4pg step")
+        check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(out),
+                                   stream_ptr(stream)), f"{self._tag} step")
 
     def policy(self, obs: torch.Tensor, use_target: bool = False, stream=None) -> torch.Tensor:
         rows = int(obs.shape[0])
@@ -778,9 +783,56 @@ class NativeD4PG:
         if obs.shape[1] != self.obs_dim:
             raise ValueError(f"observations must have {self.obs_dim} features")
         a = torch.empty(rows, self.act_dim, dtype=torch.float32, device=self.device)
-        check(lib().acme_d4pg_policy(self._h, ptr(obs), rows, 1 if use_target else 0, ptr(a),
-                                     stream_ptr(stream)), "d4pg policy")
+        check(self._fn("policy")(self._h, ptr(obs), rows, 1 if use_target else 0, ptr(a),
+                                     stream_ptr(stream)), f"{self._tag} policy")
         return a
+
+
+class NativeD4PG(_NativeActorCritic):
+    """acme_d4pg learner + its flat buffers (policy tensors first, then critic tensors)."""
+
+    _prefix, _tag, _config = "acme_d4pg", "d4pg", _lib.D4PGConfig
+
+    def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int,
+                 policy_sizes: Sequence[int] = (256, 256, 256),
+                 critic_sizes: Sequence[int] = (512, 512, 256), num_atoms: int = 51,
+                 vmin: float = -150.0, vmax: float = 150.0, action_min=None, action_max=None,
+                 discount: float = 0.99, target_update_period: int = 100,
+                 policy_learning_rate: float = 1e-4, critic_learning_rate: float = 1e-4,
+                 clipping: bool = True, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_epsilon: float = 1e-8, layer_norm_epsilon: float = 1e-5, device=None):
+        self._setup(obs_dim=obs_dim, act_dim=act_dim, max_batch=max_batch,
+                    policy_sizes=policy_sizes, critic_sizes=critic_sizes,
+                    action_min=action_min, action_max=action_max, discount=discount,
+                    target_update_period=target_update_period,
+                    policy_learning_rate=policy_learning_rate,
+                    critic_learning_rate=critic_learning_rate, clipping=clipping,
+                    adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
+                    layer_norm_epsilon=layer_norm_epsilon, device=device,
+                    num_atoms=int(num_atoms), vmin=vmin, vmax=vmax)
+
+
+class NativeDDPG(_NativeActorCritic):
+    """acme_ddpg learner (scalar critic LayerNormMLP(critic_sizes + (1,)), TD loss) + its
+    flat buffers; the surface of NativeD4PG."""
+
+    _prefix, _tag, _config = "acme_ddpg", "ddpg", _lib.DDPGConfig
+
+    def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int,
+                 policy_sizes: Sequence[int] = (256, 256, 256),
+                 critic_sizes: Sequence[int] = (512, 512, 256), action_min=None,
+                 action_max=None, discount: float = 0.99, target_update_period: int = 100,
+                 policy_learning_rate: float = 1e-4, critic_learning_rate: float = 1e-4,
+                 clipping: bool = True, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_epsilon: float = 1e-8, layer_norm_epsilon: float = 1e-5, device=None):
+        self._setup(obs_dim=obs_dim, act_dim=act_dim, max_batch=max_batch,
+                    policy_sizes=policy_sizes, critic_sizes=critic_sizes,
+                    action_min=action_min, action_max=action_max, discount=discount,
+                    target_update_period=target_update_period,
+                    policy_learning_rate=policy_learning_rate,
+                    critic_learning_rate=critic_learning_rate, clipping=clipping,
+                    adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
+                    layer_norm_epsilon=layer_norm_epsilon, device=device)
 
 
 class NativeIMPALA:

@@ -268,6 +268,53 @@ def make_d4pg_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 
     }
 
 
+@dataclasses.dataclass(frozen=True)
+class LayerNormMLPCritic:
+    """snt.Sequential([CriticMultiplexer(), LayerNormMLP(layer_sizes + (1,))]): DDPG's scalar
+    critic (acme/agents/tf/ddpg/agent_test.py:41-47).  `layer_sizes` are the hidden widths; the
+    width-1 output layer (no activation) is the LayerNormMLP's own last linear."""
+
+    obs_dim: int
+    act_dim: int
+    layer_sizes: Tuple[int, ...] = (512, 512, 256)
+
+    def __init__(self, obs_dim: int, act_dim: int, layer_sizes: Sequence[int] = (512, 512, 256)):
+        object.__setattr__(self, "obs_dim", int(obs_dim))
+        object.__setattr__(self, "act_dim", int(act_dim))
+        object.__setattr__(self, "layer_sizes", tuple(int(s) for s in layer_sizes))
+
+    def tensor_shapes(self):
+        s = list(self.layer_sizes)
+        n = len(s)
+        return _layer_norm_mlp_shapes("critic", self.obs_dim + self.act_dim, s) + [
+            (f"critic/layer_norm_mlp/mlp/linear_{n - 1}/w", (s[-1], 1)),
+            (f"critic/layer_norm_mlp/mlp/linear_{n - 1}/b", (1,))]
+
+    def init(self, seed: int = 0) -> Dict[str, np.ndarray]:
+        rng = np.random.default_rng(seed)
+        out: Dict[str, np.ndarray] = {}
+        shapes = self.tensor_shapes()
+        _init_layer_norm_mlp(rng, shapes[:-2], out)
+        # The output layer: snt.Linear's default, TruncatedNormal(1 / sqrt(fan_in)).
+        (wn, ws), (bn, bs) = shapes[-2:]
+        out[wn] = truncated_normal(rng, ws, 1.0 / np.sqrt(ws[0]))
+        out[bn] = np.zeros(bs, np.float32)
+        return out
+
+
+def make_ddpg_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 256),
+                       critic_layer_sizes=(512, 512, 256)) -> Dict[str, object]:
+    """DDPG's networks: D4PG's policy and a scalar LayerNormMLP critic (observation network =
+    identity)."""
+    act_dim = int(np.prod(action_spec.shape))
+    return {
+        "policy": LayerNormMLPPolicy(obs_dim, act_dim, policy_layer_sizes,
+                                     action_spec.minimum, action_spec.maximum),
+        "critic": LayerNormMLPCritic(obs_dim, act_dim, critic_layer_sizes),
+        "observation": "identity",
+    }
+
+
 # ------------------------------------------------------------------ IMPALA (Atari)
 
 

@@ -121,10 +121,13 @@ class DiscreteEnvironment(Environment):
 
 class ContinuousEnvironment(Environment):
     def __init__(self, obs_dim: int = 24, action_dim: int = 6, episode_length: int = 25,
-                 seed: int = 0):
+                 seed: int = 0, bounded: bool = True):
+        # bounded=False: an unbounded action spec (the reference fake's default).
+        actions = (specs.BoundedArray((action_dim,), np.float32, -1.0, 1.0, "action") if bounded
+                   else specs.Array((action_dim,), np.float32, "action"))
         spec = specs.EnvironmentSpec(
             observations=specs.Array((obs_dim,), np.float32, "observation"),
-            actions=specs.BoundedArray((action_dim,), np.float32, -1.0, 1.0, "action"),
+            actions=actions,
             rewards=specs.Array((), np.float32, "reward"),
             discounts=specs.BoundedArray((), np.float32, 0.0, 1.0, "discount"))
         super().__init__(spec, episode_length, seed)

@@ -581,6 +581,57 @@ int acme_d4pg_set_num_steps(acme_d4pg* l, int64_t n);
 int acme_d4pg_debug_buffer(const acme_d4pg* l, const char* name, const float** out,
                            int64_t* count);
 
+/* ------------------------------------------------------------------ DDPG -- */
+/* Replaces DDPGLearner._step (acme/agents/tf/ddpg/learning.py:143-237): D4PG's step with a
+ * scalar critic, critic = concat(obs, action) -> LayerNormMLP(critic_sizes + (1,)) (the
+ * last linear without activation), and the TD loss mean(0.5 (r + discount d q_t - q_tm1)^2)
+ * in place of the categorical one.  The policy, the identity observation network, the
+ * flat-buffer layout (policy tensors, then critic tensors) and every call's meaning are
+ * D4PG's; the size limits are ACME_D4PG_MAX_LAYERS / ACME_D4PG_MAX_ACT. */
+typedef struct acme_ddpg acme_ddpg;
+
+typedef struct acme_ddpg_config {
+  int32_t obs_dim;              /* flat observation size (<= 64 - act_dim) */
+  int32_t act_dim;              /* <= ACME_D4PG_MAX_ACT */
+  int32_t max_batch;
+  int32_t num_policy_layers;    /* LayerNormMLP sizes, 1..ACME_D4PG_MAX_LAYERS */
+  int32_t policy_sizes[ACME_D4PG_MAX_LAYERS];
+  int32_t num_critic_layers;    /* hidden sizes; the width-1 output layer is implied */
+  int32_t critic_sizes[ACME_D4PG_MAX_LAYERS];
+  float action_min[ACME_D4PG_MAX_ACT];  /* TanhToSpec bounds (spec.minimum / maximum) */
+  float action_max[ACME_D4PG_MAX_ACT];
+  float discount;
+  int32_t target_update_period;
+  float policy_learning_rate, critic_learning_rate;
+  float adam_beta1, adam_beta2, adam_epsilon;
+  int32_t clipping;             /* dqda norm clip 1.0 + global-norm clip 40 (learning.py:201-228) */
+  float layer_norm_epsilon;     /* Sonnet LayerNorm default 1e-5 */
+} acme_ddpg_config;
+
+typedef acme_d4pg_batch acme_ddpg_batch;
+typedef acme_d4pg_outputs acme_ddpg_outputs;
+
+int acme_ddpg_create(const acme_ddpg_config* cfg, acme_ddpg** out);
+int acme_ddpg_destroy(acme_ddpg* l);
+int64_t acme_ddpg_flat_size(const acme_ddpg* l);
+int64_t acme_ddpg_policy_size(const acme_ddpg* l);
+int32_t acme_ddpg_num_tensors(const acme_ddpg* l);
+int acme_ddpg_tensor_info(const acme_ddpg* l, int32_t i, int64_t* offset, int64_t* numel,
+                          int32_t* ndim, int64_t* shape4, const char** name);
+int acme_ddpg_bind(acme_ddpg* l, float* params, float* target, float* grads, float* adam_m,
+                   float* adam_v);
+int acme_ddpg_step(acme_ddpg* l, const acme_ddpg_batch* batch, const acme_ddpg_outputs* out,
+                   void* stream);
+int acme_ddpg_policy(acme_ddpg* l, const float* obs, int64_t rows, int32_t use_target,
+                     float* actions, void* stream);
+int64_t acme_ddpg_num_steps(const acme_ddpg* l);
+int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n);
+/* Internal device workspaces (tests): "p_a" (dpg actions), "t_a" (target actions), "c_q"
+ * (online critic values, 2B rows: [q_tm1; dpg]), "t_q" (B), "td" (B), "dq" (dloss/dq of
+ * the 2B online rows: -td / B, then 1 for the dpg rows), "dqda", "norms". */
+int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** out,
+                           int64_t* count);
+
 /* ---------------------------------------------------------------- IMPALA -- */
 /* Replaces IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with
  * IMPALAAtariNetwork (acme/tf/networks/atari.py:115-144): OAREmbedding(AtariTorso) ->
