@@ -98,6 +98,42 @@ class D4PGOutputs(ctypes.Structure):
     _fields_ = [("critic_loss", c_vp), ("policy_loss", c_vp)]
 
 
+MPO_MAX_SAMPLES = 64
+MPO_MAX_ROWS = 131072
+# acme_mpo_outputs.stats, in the header's order.
+MPO_STATS = ("dual_alpha_mean", "dual_alpha_stddev", "dual_temperature", "loss_policy",
+             "loss_alpha", "loss_temperature", "kl_q_rel", "penalty_kl_q_rel", "q_min", "q_max",
+             "pi_stddev_min", "pi_stddev_max", "pi_stddev_cond")
+
+
+class MPOConfig(ctypes.Structure):  # DDPGConfig without target_update_period, plus MPO's fields
+    _fields_ = [("obs_dim", c_i32), ("act_dim", c_i32), ("max_batch", c_i32),
+                ("num_policy_layers", c_i32), ("policy_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("num_critic_layers", c_i32), ("critic_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("action_min", c_f32 * D4PG_MAX_ACT), ("action_max", c_f32 * D4PG_MAX_ACT),
+                ("discount", c_f32),
+                ("policy_learning_rate", c_f32), ("critic_learning_rate", c_f32),
+                ("adam_beta1", c_f32), ("adam_beta2", c_f32), ("adam_epsilon", c_f32),
+                ("clipping", c_i32), ("layer_norm_epsilon", c_f32),
+                ("num_samples", c_i32), ("target_policy_update_period", c_i32),
+                ("target_critic_update_period", c_i32), ("dual_learning_rate", c_f32),
+                ("epsilon", c_f32), ("epsilon_mean", c_f32), ("epsilon_stddev", c_f32),
+                ("epsilon_penalty", c_f32), ("init_log_temperature", c_f32),
+                ("init_log_alpha_mean", c_f32), ("init_log_alpha_stddev", c_f32),
+                ("per_dim_constraining", c_i32), ("action_penalization", c_i32),
+                ("init_scale", c_f32), ("min_scale", c_f32), ("seed", ctypes.c_uint64)]
+
+
+class MPOBatch(ctypes.Structure):
+    _fields_ = [("o_tm1", c_vp), ("a_tm1", c_vp), ("r_t", c_vp), ("d_t", c_vp), ("o_t", c_vp),
+                ("batch", c_i64), ("noise", c_vp)]
+
+
+class MPOOutputs(ctypes.Structure):
+    _fields_ = [("critic_loss", c_vp), ("policy_loss", c_vp), ("stats", c_vp),
+                ("kl_mean_rel", c_vp), ("kl_stddev_rel", c_vp)]
+
+
 IMPALA_TORSO_ATARI = 0
 IMPALA_TORSO_FLAT = 1
 
@@ -318,6 +354,23 @@ _SIGS = {
     "acme_ddpg_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_ddpg_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
                                        ctypes.POINTER(c_i64)]),
+    "acme_mpo_create": (c_i32, [ctypes.POINTER(MPOConfig), ctypes.POINTER(c_vp)]),
+    "acme_mpo_destroy": (c_i32, [c_vp]),
+    "acme_mpo_flat_size": (c_i64, [c_vp]),
+    "acme_mpo_policy_size": (c_i64, [c_vp]),
+    "acme_mpo_dual_offset": (c_i64, [c_vp]),
+    "acme_mpo_num_tensors": (c_i32, [c_vp]),
+    "acme_mpo_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
+                                     ctypes.POINTER(ctypes.c_char_p)]),
+    "acme_mpo_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_mpo_init_duals": (c_i32, [c_vp]),
+    "acme_mpo_step": (c_i32, [c_vp, ctypes.POINTER(MPOBatch), ctypes.POINTER(MPOOutputs), c_vp]),
+    "acme_mpo_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "acme_mpo_num_steps": (c_i64, [c_vp]),
+    "acme_mpo_set_num_steps": (c_i32, [c_vp, c_i64]),
+    "acme_mpo_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
+                                      ctypes.POINTER(c_i64)]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),

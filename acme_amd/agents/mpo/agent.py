@@ -1,0 +1,79 @@
+"""MPO agent — drop-in for acme/agents/tf/mpo/agent.py:34-200.
+
+Same constructor (environment_spec, policy_network, critic_network,
+observation_network=identity, discount=0.99, batch_size=256, prefetch_size=4,
+target_policy_update_period=100, target_critic_update_period=100, min_replay_size=1000,
+max_replay_size=1e6, samples_per_insert=32.0, policy_loss_module=None, policy_optimizer=None,
+critic_optimizer=None, n_step=5, num_samples=20, clipping=True, logger=None, counter=None,
+checkpoint=True, replay_table_name), plus `seed`.  Uniform GPU replay table instead of a Reverb
+server; the behaviour policy samples from the learner's online distribution
+(networks.StochasticSamplingHead, agent.py:143-147)."""
+
+from __future__ import annotations
+
+import copy
+
+import numpy as np
+
+from acme_amd import datasets, replay, specs
+from acme_amd.adders import reverb as adders
+from acme_amd.agents import agent
+from acme_amd.agents.actors import FeedForwardActor
+from acme_amd.agents.mpo import learning
+
+
+class StochasticBehaviourPolicy:
+    """a ~ N(mean(o), stddev(o)): StochasticSamplingHead on the online policy, sampled on the
+    host with a seeded generator.  Like the reference's, it does not clip to the action spec."""
+
+    def __init__(self, distribution_fn, seed: int = 0):
+        self._distribution = distribution_fn
+        self._rng = np.random.default_rng(seed)
+
+    def __call__(self, batched_obs):
+        mean, stddev = self._distribution(batched_obs)
+        noise = self._rng.standard_normal(mean.shape).astype(np.float32)
+        return (mean + stddev * noise).astype(np.float32)
+
+
+class MPO(agent.Agent):
+
+    def __init__(self, environment_spec: specs.EnvironmentSpec, policy_network, critic_network,
+                 observation_network="identity", discount: float = 0.99, batch_size: int = 256,
+                 prefetch_size: int = 4, target_policy_update_period: int = 100,
+                 target_critic_update_period: int = 100, min_replay_size: int = 1000,
+                 max_replay_size: int = 1000000, samples_per_insert: float = 32.0,
+                 policy_loss_module=None, policy_optimizer=None, critic_optimizer=None,
+                 n_step: int = 5, num_samples: int = 20, clipping: bool = True, logger=None,
+                 counter=None, checkpoint: bool = True,
+                 replay_table_name: str = adders.DEFAULT_PRIORITY_TABLE, seed: int = 0):
+        table = replay.Table(
+            name=replay_table_name, sampler=replay.selectors.Uniform(),
+            remover=replay.selectors.Fifo(), max_size=max_replay_size,
+            rate_limiter=replay.rate_limiters.MinSize(1),
+            signature=adders.NStepTransitionAdder.signature(environment_spec), seed=4321 + seed)
+        self._server = replay.Server([table], port=None)
+        address = f"localhost:{self._server.port}"
+        adder = adders.NStepTransitionAdder(priority_fns={replay_table_name: lambda x: 1.},
+                                            client=replay.Client(address), n_step=n_step,
+                                            discount=discount)
+        dataset = datasets.make_reverb_dataset(table=replay_table_name, server_address=address,
+                                               batch_size=batch_size,
+                                               prefetch_size=prefetch_size)
+        learner = learning.MPOLearner(
+            policy_network=policy_network, critic_network=critic_network,
+            target_policy_network=copy.deepcopy(policy_network),
+            target_critic_network=copy.deepcopy(critic_network),
+            observation_network=observation_network,
+            target_observation_network=observation_network,
+            policy_loss_module=policy_loss_module, policy_optimizer=policy_optimizer,
+            critic_optimizer=critic_optimizer, clipping=clipping, discount=discount,
+            num_samples=num_samples, target_policy_update_period=target_policy_update_period,
+            target_critic_update_period=target_critic_update_period, dataset=dataset,
+            counter=counter, logger=logger, checkpoint=checkpoint, batch_size=batch_size,
+            seed=seed)
+        behaviour = StochasticBehaviourPolicy(learner.policy_distribution, seed=seed)
+        actor = FeedForwardActor(behaviour, adder)
+        super().__init__(actor=actor, learner=learner,
+                         min_observations=max(batch_size, min_replay_size),
+                         observations_per_step=float(batch_size) / samples_per_insert)

@@ -1,0 +1,121 @@
+"""MPOLearner — drop-in for acme/agents/tf/mpo/learning.py:34-300.
+
+Same constructor arguments and `step()` contract: one call draws a batch from the dataset
+iterator and runs the whole MPO step on the GPU (acme_mpo_step: the two start-of-step target
+copies, online / target Gaussian policies, num_samples actions per state sampled from the
+target policy on the device, the target critic over all of them, TD loss, the decoupled MPO
+loss of acme/tf/losses/mpo.py with its dual variables, per-network global-norm clipping, three
+Adams), then counts and logs.  Losses and stats are device scalars handed to the logger;
+nothing synchronises the host with the device.
+
+`policy_network` / `critic_network` are descriptors from acme_amd.networks
+(LayerNormMLPGaussianPolicy, LayerNormMLPCritic); the observation networks must be the
+identity.  `policy_loss_module` is an MPOLoss, the settings of losses.MPO: the dual variables
+it would own live in the learner's flat buffers (`mpo/log_*`), so save / restore, the Adam
+moments and `get_params` cover them.  `dual_optimizer` gives the duals' learning rate.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+import time
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from acme_amd.agents.d4pg.learning import D4PGLearner, _is_identity
+from acme_amd.native import NativeMPO
+from acme_amd.utils import counting, loggers
+
+
+@dataclasses.dataclass(frozen=True)
+class MPOLoss:
+    """The constructor arguments of losses.MPO (acme/tf/losses/mpo.py:53-63); the defaults of
+    the arguments it requires are the values MPOLearner passes when it builds its own
+    (learning.py:86-93)."""
+
+    epsilon: float = 1e-1
+    epsilon_mean: float = 1e-3
+    epsilon_stddev: float = 1e-6
+    init_log_temperature: float = 1.0
+    init_log_alpha_mean: float = 1.0
+    init_log_alpha_stddev: float = 10.0
+    per_dim_constraining: bool = True
+    action_penalization: bool = True
+    epsilon_penalty: float = 1e-3
+
+
+class MPOLearner(D4PGLearner):
+    """step / save / restore / get_variables are D4PGLearner's (the native handles have one
+    surface; the duals and their moments are entries of the same buffers); `policy` returns
+    the online distribution's mean."""
+
+    def __init__(self, policy_network, critic_network, target_policy_network,
+                 target_critic_network, discount: float, num_samples: int,
+                 target_policy_update_period: int, target_critic_update_period: int, dataset,
+                 observation_network=lambda x: x, target_observation_network=lambda x: x,
+                 policy_loss_module: Optional[MPOLoss] = None, policy_optimizer=None,
+                 critic_optimizer=None, dual_optimizer=None, clipping: bool = True,
+                 counter: Optional[counting.Counter] = None,
+                 logger: Optional[loggers.Logger] = None, checkpoint: bool = True,
+                 batch_size: Optional[int] = None, seed: int = 0, device=None):
+        if not (_is_identity(observation_network) and _is_identity(target_observation_network)):
+            raise ValueError("acme_amd's MPO learner supports identity observation networks "
+                             "(flat observations) only")
+        if critic_network.obs_dim != policy_network.obs_dim or \
+                critic_network.act_dim != policy_network.act_dim:
+            raise ValueError("policy and critic disagree on observation / action sizes")
+        loss = policy_loss_module or MPOLoss()
+        if not isinstance(loss, MPOLoss):
+            raise ValueError("policy_loss_module must be an acme_amd.agents.mpo.MPOLoss")
+        self._policy_network = policy_network
+        self._critic_network = critic_network
+        self._policy_loss_module = loss
+        self._iterator = iter(dataset)
+        B = batch_size or getattr(dataset, "batch_size", None) or 256
+        lr = lambda opt, d: float(getattr(opt, "learning_rate", d)) if opt is not None else d  # noqa
+        self._native = NativeMPO(
+            obs_dim=policy_network.obs_dim, act_dim=policy_network.act_dim, max_batch=B,
+            policy_sizes=policy_network.layer_sizes, critic_sizes=critic_network.layer_sizes,
+            num_samples=num_samples, discount=discount,
+            target_policy_update_period=target_policy_update_period,
+            target_critic_update_period=target_critic_update_period,
+            policy_learning_rate=lr(policy_optimizer, 1e-4),
+            critic_learning_rate=lr(critic_optimizer, 1e-4),
+            dual_learning_rate=lr(dual_optimizer, 1e-2), clipping=clipping,
+            init_scale=policy_network.init_scale, min_scale=policy_network.min_scale,
+            seed=seed, device=device, **dataclasses.asdict(loss))
+        init = dict(policy_network.init(seed))
+        init.update(critic_network.init(seed + 1))
+        tinit = dict(target_policy_network.init(seed + 2))
+        tinit.update(target_critic_network.init(seed + 3))
+        self._native.set_params(init, tinit)  # the duals keep their init_log_* values
+        self._counter = counter or counting.Counter()
+        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
+        self._timestamp = None
+        self._checkpoint = checkpoint
+
+    def step(self):
+        sample = next(self._iterator)
+        o_tm1, a_tm1, r_t, d_t, o_t = sample.data[:5]
+        B = int(r_t.shape[0])
+        f = lambda x: x.reshape(B, -1).float().contiguous()  # noqa: E731
+        n = self._native
+        n.step(f(o_tm1), f(a_tm1), f(r_t).reshape(B), f(d_t).reshape(B), f(o_t))
+        now = time.time()
+        elapsed = now - self._timestamp if self._timestamp else 0
+        self._timestamp = now
+        result: Dict = {"critic_loss": n.critic_loss, "policy_loss": n.policy_loss}
+        for name in n.stat_names:  # the reference's fetches.update(policy_stats)
+            if name != "penalty_kl_q_rel" or self._policy_loss_module.action_penalization:
+                result[name] = n.stat(name)
+        result["kl_mean_rel"], result["kl_stddev_rel"] = n.kl_mean_rel, n.kl_stddev_rel
+        result.update(self._counter.increment(steps=1, walltime=elapsed))
+        self._logger.write(result)
+
+    def policy_distribution(self, observations, use_target: bool = False):
+        """(mean, stddev) of the policy's diagonal Gaussian as host arrays."""
+        x = torch.as_tensor(np.asarray(observations, np.float32))
+        mean, stddev = self._native.policy_distribution(x, use_target)
+        return mean.cpu().numpy(), stddev.cpu().numpy()

@@ -24,6 +24,13 @@
 // stands where the head GEMMs, the categorical loss kernel and the head's input-gradient
 // problem stand for D4PG; everything else of the step is shared.
 //
+// MPO (acme_mpo_*, acme/agents/tf/mpo/learning.py:145-260, acme/tf/losses/mpo.py) is a third head
+// kind of the same object: a Gaussian policy head, N actions per state sampled from the target
+// policy on the device, the scalar critic over those N B rows, the decoupled MPO loss and its
+// dual variables as a third parameter group.  Its kernels are in mpo_kernels.h, its step is
+// mpo_step_impl below; the LayerNormMLP passes, the backward launches, the clipping and Adam
+// are the shared ones.
+//
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
 // epilogues and masked dgrads; the row-wise work (LayerNorm+tanh, TanhToSpec head,
@@ -38,6 +45,7 @@
 
 #include "common.h"
 #include "conv.h"
+#include "detmath.h"
 #include "gemm.h"
 #include "gemm_direct.h"
 #include "kernels.h"
@@ -53,6 +61,7 @@ constexpr int kRows = 4;      // rows per block of the LayerNorm row kernels
 constexpr int kMaxWidth = 1024;
 constexpr int kMaxIn = 64;    // obs_dim + act_dim
 constexpr int kNormBlocks = 256;
+constexpr int kGraphKeys = 11;  // pointers that key a captured step graph (MPO uses all)
 
 struct Tensor {
   std::string name;
@@ -111,11 +120,28 @@ struct acme_d4pg {
   float* td = nullptr;                    // [B] TD error
   float* dq = nullptr;                    // [2B] dloss/dq (rows < B), 1 (dpg rows)
   int64_t* dev_step = nullptr;            // device mirror of num_steps (Adam t)
-  // Captured step graphs, keyed by the batch / output pointers, B and the target copy.
+  // MPO (acme_mpo_create): Gaussian policy head, N sampled actions per state, scalar critic,
+  // the dual variables as a third parameter group [critic_end, flat).
+  bool mpo = false;
+  acme_mpo_config mcfg;
+  int64_t critic_end = 0;                 // end of the critic's floats (= flat without duals)
+  int sw = -1, sb = -1;                   // the head's scale layer (pol.ow / pol.ob: its mean layer)
+  int t_temp = -1, t_amean = -1, t_astd = -1, t_ptemp = -1;  // dual tensors
+  struct MpoBufs {
+    float *sd_on, *sd_t;                  // [B][A] stddevs (means: pon.out / ptg.out, pre-softplus: .t)
+    float *noise, *act;                   // [N B][A] eps used, sampled actions
+    float *cost, *tiled;                  // [N B] out-of-bound cost, [N B][obs] o_t tiled N times
+    float *w, *pw;                        // [N B] normalized weights, penalty weights
+    float *qt;                            // [B] mean_n of the sampled target values (ctg.out)
+    float *dmean, *dpre;                  // [B][A] dloss / d(online mean, pre-softplus scale)
+    float *part;                          // [ceil(B / 4)][kMpoCols] per-block sums of the loss kernel
+    float *stats, *klm_rel, *kls_rel, *ploss;  // outputs when the caller passes none
+  } mb = {};
+  // Captured step graphs, keyed by the batch / output pointers, B and the target copies.
   struct Graph {
-    const void* key[7];
+    const void* key[kGraphKeys];
     int64_t B;
-    bool copy;
+    int copy;
     hipGraphExec_t exec;
   };
   std::vector<Graph> graphs;
@@ -251,13 +277,10 @@ struct LnFirstPair {
   int Hp;                   // policy hidden width
 };
 
-// One row of the policy head, lane j < A: u_j = h_row . W[:, j] (lane-strided partial sums,
-// then the butterfly sum) and the TanhToSpec action; policy_head_kernel and the fused head
-// of ln_first_kernel share it, so both give the same bits.
-__device__ __forceinline__ void policy_head_row(const float* __restrict__ h, const float* __restrict__ w,
-                                                const float* __restrict__ b, const float* __restrict__ lo,
-                                                const float* __restrict__ scale, int H, int A,
-                                                int lane, float& t, float& act) {
+// One row of a narrow head, lane j < A: h_row . W[:, j] (lane-strided partial sums, then the
+// butterfly sum); lanes >= A get 0.  The policy heads of every learner here go through it.
+__device__ __forceinline__ float head_dot_row(const float* __restrict__ h, const float* __restrict__ w,
+                                              int H, int A, int lane) {
   float acc[ACME_D4PG_MAX_ACT];
 #pragma unroll
   for (int j = 0; j < ACME_D4PG_MAX_ACT; ++j) acc[j] = 0.f;
@@ -286,6 +309,17 @@ __device__ __forceinline__ void policy_head_row(const float* __restrict__ h, con
     const float s = wave_sum(acc[j]);
     if (lane == j) mine = s;
   }
+  return mine;
+}
+
+// One row of the deterministic policy head: u_j = h_row . W[:, j] + b_j and the TanhToSpec
+// action; policy_head_kernel and the fused head of ln_first_kernel share it, so both give the
+// same bits.
+__device__ __forceinline__ void policy_head_row(const float* __restrict__ h, const float* __restrict__ w,
+                                                const float* __restrict__ b, const float* __restrict__ lo,
+                                                const float* __restrict__ scale, int H, int A,
+                                                int lane, float& t, float& act) {
+  const float mine = head_dot_row(h, w, H, A, lane);
   t = 0.f;
   act = 0.f;
   if (lane < A) {
@@ -599,6 +633,8 @@ __global__ void __launch_bounds__(256) ddpg_head_td_kernel(const HeadTdArgs a) {
     dz4[k] = o;
   }
 }
+
+#include "mpo_kernels.h"
 
 // ------------------------------------------------------------------ LayerNorm backward
 // Per row (kRows rows per block): dy = dLoss/d(LayerNorm output) (tanh' already
@@ -1311,6 +1347,165 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
   return ACME_OK;
 }
 
+// ------------------------------------------------------------------ MPO step
+// MPOLearner._step (acme/agents/tf/mpo/learning.py:145-260) on one stream:
+//   target policy / critic <- online under their own periods (at the start)      (:159-165)
+//   online and target policy on o_t, the Gaussian head of both                   (:193-194)
+//   N actions per state from the target policy, their out-of-bound cost, o_t tiled (:197-198)
+//   online critic on [o_tm1, a_tm1] (B rows), target critic on the N B samples   (:201-212)
+//   head + TD loss against q_t = mean_n                                           (:209-217)
+//   MPO loss, its backward into the policy head; dual gradients, stats, dual Adam (:220-224)
+//   policy backward, critic backward, global-norm clipping, two Adams             (:236-251)
+// The policy head's input gradient is formed by the loss kernel (its two linears' weight
+// gradients ride the first policy backward launch), and the policy's backward runs before
+// the critic's so that no launch carries more than kZ weight gradients.
+int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
+                  int copy, hipStream_t st) {
+  const acme_mpo_config& mc = l->mcfg;
+  const int B = (int)bt->batch, N = mc.num_samples, NB = N * B;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const int D = mc.per_dim_constraining ? ad : 1;
+  const NetDesc& pd = l->pol;
+  const NetDesc& cd = l->cri;
+  const int pL = pd.nl - 1, cL = cd.nl - 1;
+  auto& mb = l->mb;
+  int rc;
+  if (copy & 1) {
+    ACME_PROF("mpo_target_copy", st, 0.0, 2.0 * 4.0 * (double)l->policy_flat);
+    ACME_HIP_TRY(hipMemcpyAsync(l->target, l->params, (size_t)l->policy_flat * sizeof(float),
+                                hipMemcpyDeviceToDevice, st));
+  }
+  if (copy & 2) {
+    ACME_PROF("mpo_target_copy", st, 0.0, 2.0 * 4.0 * (double)(l->critic_end - l->policy_flat));
+    ACME_HIP_TRY(hipMemcpyAsync(l->target + l->policy_flat, l->params + l->policy_flat,
+                                (size_t)(l->critic_end - l->policy_flat) * sizeof(float),
+                                hipMemcpyDeviceToDevice, st));
+  }
+  const float scale_mul = (float)((double)mc.init_scale / std::log(2.0));
+  {
+    const NetIn pin[2] = {{l->params, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->pon},
+                          {l->target, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->ptg}};
+    if ((rc = lnmlp_forward_pair(l, pd, pin, od, 0, "mpo_policy_ln", st))) return rc;
+    ACME_PROF("mpo_gauss_head", st, 2.0 * 2.0 * 2.0 * B * (double)pd.sizes[pL] * ad, 0.0);
+    GaussHeadPair h;
+    const float* prm[2] = {l->params, l->target};
+    Acts* acts[2] = {&l->pon, &l->ptg};
+    float* sd[2] = {mb.sd_on, mb.sd_t};
+    for (int i = 0; i < 2; ++i)
+      h.a[i] = {acts[i]->h[pL], P(l, prm[i], pd.ow), P(l, prm[i], pd.ob), P(l, prm[i], l->sw),
+                P(l, prm[i], l->sb), B, acts[i]->out, acts[i]->t, sd[i]};
+    h.H = pd.sizes[pL]; h.A = ad; h.scale_mul = scale_mul; h.min_scale = mc.min_scale;
+    gauss_head_kernel<<<dim3((unsigned)ceil_div(B, 4), 2), 256, 0, st>>>(h);
+    D4_CHECK();
+  }
+  {
+    ACME_PROF("mpo_sample", st, 0.0, 4.0 * NB * (3.0 * ad + od + 1.0));
+    MpoSampleArgs a;
+    a.mean = l->ptg.out; a.sd = mb.sd_t; a.noise_in = bt->noise; a.o_t = bt->o_t;
+    a.dev_step = l->dev_step; a.seed = mc.seed;
+    a.B = B; a.N = N; a.A = ad; a.od = od;
+    a.noise = mb.noise; a.act = mb.act; a.cost = mb.cost; a.tiled = mb.tiled;
+    mpo_sample_kernel<<<(unsigned)ceil_div(NB, 256), 256, 0, st>>>(a);
+    D4_CHECK();
+  }
+  {
+    const NetIn cin[2] = {{l->params, bt->o_tm1, bt->a_tm1, bt->o_tm1, bt->a_tm1, B, B, &l->con},
+                          {l->target, mb.tiled, mb.act, mb.tiled, mb.act, NB, NB, &l->ctg}};
+    if ((rc = lnmlp_forward_pair(l, cd, cin, od, ad, "mpo_critic_ln", st))) return rc;
+  }
+  {
+    ACME_PROF("mpo_head_td", st, 2.0 * (NB + 2.0 * B) * (double)cd.sizes[cL], 0.0);
+    MpoHeadTdArgs a;
+    a.h = l->con.h[cL]; a.w = P(l, l->params, cd.ow); a.b = P(l, l->params, cd.ob);
+    a.th = l->ctg.h[cL]; a.tw = P(l, l->target, cd.ow); a.tb = P(l, l->target, cd.ob);
+    a.r = bt->r_t; a.d = bt->d_t;
+    a.B = B; a.N = N; a.H = cd.sizes[cL]; a.act = act_of_layer(cL); a.discount = l->cfg.discount;
+    a.q = l->con.out; a.sq = l->ctg.out; a.qt = mb.qt; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
+    a.dz = l->cdz[cL];
+    mpo_head_td_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
+    D4_CHECK();
+  }
+  const int nblk = (int)ceil_div(B, 4);
+  float* stats = out && out->stats ? out->stats : mb.stats;
+  float* klm_rel = out && out->kl_mean_rel ? out->kl_mean_rel : mb.klm_rel;
+  float* kls_rel = out && out->kl_stddev_rel ? out->kl_stddev_rel : mb.kls_rel;
+  {
+    ACME_PROF("mpo_loss", st, 0.0, 0.0);
+    MpoLossArgs a;
+    a.sq = l->ctg.out; a.cost = mb.cost; a.act = mb.act;
+    a.mu_on = l->pon.out; a.sd_on = mb.sd_on; a.pre_on = l->pon.t;
+    a.mu_t = l->ptg.out; a.sd_t = mb.sd_t;
+    a.log_temp = P(l, l->params, l->t_temp); a.log_amean = P(l, l->params, l->t_amean);
+    a.log_astd = P(l, l->params, l->t_astd);
+    a.log_ptemp = l->t_ptemp >= 0 ? P(l, l->params, l->t_ptemp) : nullptr;
+    a.B = B; a.N = N; a.A = ad; a.D = D; a.H = pd.sizes[pL]; a.act_fn = act_of_layer(pL);
+    a.scale_mul = scale_mul;
+    a.h = l->pon.h[pL]; a.wm = P(l, l->params, pd.ow); a.ws = P(l, l->params, l->sw);
+    a.dmean = mb.dmean; a.dpre = mb.dpre; a.dz = l->pdz[pL];
+    a.w_out = mb.w; a.pw_out = mb.pw; a.part = mb.part;
+    mpo_loss_kernel<<<(unsigned)nblk, 256, 0, st>>>(a);
+    D4_CHECK();
+  }
+  {
+    ACME_PROF("mpo_finalize", st, 0.0, 0.0);
+    MpoFinalArgs a;
+    a.part = mb.part; a.nblk = nblk; a.B = B; a.N = N; a.A = ad; a.D = D;
+    a.penal = l->t_ptemp >= 0;
+    a.p = l->params; a.g = l->grads; a.m = l->m; a.v = l->v;
+    a.o_temp = l->tensors[l->t_temp].offset; a.o_amean = l->tensors[l->t_amean].offset;
+    a.o_astd = l->tensors[l->t_astd].offset;
+    a.o_ptemp = l->t_ptemp >= 0 ? l->tensors[l->t_ptemp].offset : -1;
+    a.eps = mc.epsilon; a.eps_mean = mc.epsilon_mean; a.eps_std = mc.epsilon_stddev;
+    a.eps_pen = mc.epsilon_penalty;
+    a.lr = mc.dual_learning_rate; a.b1 = l->cfg.adam_beta1; a.b2 = l->cfg.adam_beta2;
+    a.adam_eps = l->cfg.adam_epsilon; a.dev_step = l->dev_step;
+    a.stats = stats; a.klm_rel = klm_rel; a.kls_rel = kls_rel; a.ploss = mb.ploss;
+    mpo_finalize_kernel<<<1, 256, 0, st>>>(a);
+    D4_CHECK();
+  }
+  BwdGroup g;
+  std::vector<LnReduce> ln;
+  // Policy backward from dz[pL] (written by the loss kernel).
+  add_wgrad(g, l->pon.h[pL], B, pd.sizes[pL], mb.dmean, ad, Pm(l, l->grads, pd.ow),
+            Pm(l, l->grads, pd.ob));
+  add_wgrad(g, l->pon.h[pL], B, pd.sizes[pL], mb.dpre, ad, Pm(l, l->grads, l->sw),
+            Pm(l, l->grads, l->sb));
+  if ((rc = lnmlp_backward_mlp(l, pd, l->pon, l->pdz, B, B, g, "mpo_bwd_phead", st, true)) ||
+      (rc = ln_backward(l, pd, l->pon, l->pdz[0], B, B, false, bt->o_t, nullptr, od, 0,
+                        l->lnslab2, g, ln, st)))
+    return rc;
+  // Critic backward over the B TD rows; the head's weight gradient (one live column) and the
+  // policy's first-layer weight gradient ride its first launch.
+  add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dq, 1, Pm(l, l->grads, cd.ow),
+            Pm(l, l->grads, cd.ob));
+  if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, B, B, g, "mpo_bwd_chead", st, true)) ||
+      (rc = ln_backward(l, cd, l->con, l->cdz[0], B, B, false, bt->o_tm1, bt->a_tm1, od, ad,
+                        l->lnslab, g, ln, st)) ||
+      (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
+    return rc;
+  {
+    // Global-norm clipping + Adam of the policy and critic groups; the duals' floats past
+    // critic_end are the finalize kernel's.
+    ACME_PROF("d4pg_adam", st, 0.0, 7.0 * 4.0 * (double)l->critic_end);
+    const int64_t n4 = l->critic_end / 4, pol4 = l->policy_flat / 4;
+    if ((rc = launch_grad_sumsq(l->grads, n4, pol4, l->norm_part, kNormBlocks, l->dev_step, st)))
+      return rc;
+    ClipAdamArgs a;
+    a.p = l->params; a.m = l->m; a.v = l->v; a.g = l->grads; a.n4 = n4; a.group0_4 = pol4;
+    a.part = l->norm_part; a.nparts = kNormBlocks; a.clipping = l->cfg.clipping;
+    a.clip_norm = 40.f;
+    a.lr0 = l->cfg.policy_learning_rate; a.lr1 = l->cfg.critic_learning_rate;
+    a.b1 = l->cfg.adam_beta1; a.b2 = l->cfg.adam_beta2; a.eps = l->cfg.adam_epsilon;
+    a.dev_step = l->dev_step; a.norms = l->norms;
+    a.sum_a = mb.ploss; a.n_a = 1; a.div_a = 1.f;
+    a.out_a = out && out->policy_loss ? out->policy_loss : l->loss_tmp + 1;
+    a.sum_b = l->ce; a.n_b = B; a.div_b = (float)B;
+    a.out_b = out && out->critic_loss ? out->critic_loss : l->loss_tmp;
+    if ((rc = launch_clip_adam(a, st))) return rc;
+  }
+  return ACME_OK;
+}
+
 // ------------------------------------------------------------------ step graphs
 // The ~40 launches of a step are captured once per (batch pointers, outputs, B, target
 // copy) into a hipGraph on a private capture stream and replayed with one
@@ -1322,12 +1517,12 @@ bool graphs_enabled() {
   return on;
 }
 
-int run_graph(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outputs* out, bool copy,
-              hipStream_t st) {
-  const void* key[7] = {bt->o_tm1, bt->a_tm1, bt->r_t, bt->d_t, bt->o_t,
-                        out ? out->critic_loss : nullptr, out ? out->policy_loss : nullptr};
+// `record(stream)` issues the step's launches; `copy` holds the target-copy flags.
+template <class F>
+int run_graph(acme_d4pg* l, const void* const (&key)[kGraphKeys], int64_t B, int copy,
+              hipStream_t st, F&& record) {
   for (auto& g : l->graphs)
-    if (g.B == bt->batch && g.copy == copy && memcmp(g.key, key, sizeof(key)) == 0) {
+    if (g.B == B && g.copy == copy && memcmp(g.key, key, sizeof(key)) == 0) {
       ACME_HIP_TRY(hipGraphLaunch(g.exec, st));
       return ACME_OK;
     }
@@ -1337,7 +1532,7 @@ int run_graph(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outputs* 
   }
   if (!l->capture) ACME_HIP_TRY(hipStreamCreateWithFlags(&l->capture, hipStreamNonBlocking));
   ACME_HIP_TRY(hipStreamBeginCapture(l->capture, hipStreamCaptureModeRelaxed));
-  int rc = d4pg_step_impl(l, bt, out, copy, l->capture);
+  int rc = record(l->capture);
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamEndCapture(l->capture, &graph);
   if (rc != ACME_OK) {
@@ -1357,7 +1552,7 @@ int run_graph(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outputs* 
   }
   acme_d4pg::Graph g;
   memcpy(g.key, key, sizeof(key));
-  g.B = bt->batch;
+  g.B = B;
   g.copy = copy;
   g.exec = exec;
   l->graphs.push_back(g);
@@ -1379,9 +1574,11 @@ int acme_d4pg_destroy(acme_d4pg* l) {
   return ACME_OK;
 }
 
-// The learner behind both acme_d4pg_create (categorical head) and acme_ddpg_create (scalar
-// head: cfg->num_atoms = 1, the support unused).
-static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4pg** out) {
+// The learner behind acme_d4pg_create (categorical head), acme_ddpg_create (scalar head:
+// cfg->num_atoms = 1, the support unused) and acme_mpo_create (`mpo` set: scalar head, Gaussian
+// policy head, N sampled actions per state, dual variables).
+static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4pg** out,
+                          const acme_mpo_config* mpo = nullptr) {
   ACME_CHECK_ARG(cfg && out, "null argument");
   ACME_CHECK_ARG(cfg->obs_dim >= 1 && cfg->act_dim >= 1 && cfg->obs_dim + cfg->act_dim <= kMaxIn,
                  "obs_dim + act_dim must be in [2, %d]", kMaxIn);
@@ -1412,19 +1609,53 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
     return code;
   };
   add_net(l, l->pol, "policy", cfg->obs_dim, cfg->num_policy_layers, cfg->policy_sizes,
-          cfg->act_dim, "near_zero_initialized_linear");
+          cfg->act_dim,
+          mpo ? "multivariate_normal_diag_head/linear" : "near_zero_initialized_linear");
+  if (mpo) {
+    const int64_t hl = cfg->policy_sizes[cfg->num_policy_layers - 1];
+    l->sw = add_tensor(l, "policy/multivariate_normal_diag_head/linear_1/w", {hl, cfg->act_dim});
+    l->sb = add_tensor(l, "policy/multivariate_normal_diag_head/linear_1/b", {cfg->act_dim});
+  }
   l->policy_flat = l->flat;
   add_net(l, l->cri, "critic", cfg->obs_dim + cfg->act_dim, cfg->num_critic_layers,
           cfg->critic_sizes, cfg->num_atoms, scalar_head ? nullptr : "discrete_valued_head/linear");
+  l->critic_end = l->flat;
+  if (mpo) {
+    l->mpo = true;
+    l->mcfg = *mpo;
+    const int64_t D = mpo->per_dim_constraining ? cfg->act_dim : 1;
+    l->t_temp = add_tensor(l, "mpo/log_temperature", {1});
+    l->t_amean = add_tensor(l, "mpo/log_alpha_mean", {D});
+    l->t_astd = add_tensor(l, "mpo/log_alpha_stddev", {D});
+    if (mpo->action_penalization) l->t_ptemp = add_tensor(l, "mpo/log_penalty_temperature", {1});
+  }
   const int B = cfg->max_batch;
+  // MPO: the online critic sees the B TD rows only, the target critic the N B samples.
+  const int con_rows = mpo ? B : 2 * B, ctg_rows = mpo ? B * mpo->num_samples : B;
   int rc;
   int hmax = 0;
   for (int i = 0; i < cfg->num_policy_layers; ++i) hmax = std::max(hmax, cfg->policy_sizes[i]);
   for (int i = 0; i < cfg->num_critic_layers; ++i) hmax = std::max(hmax, cfg->critic_sizes[i]);
   if ((rc = alloc_acts(l, l->pon, l->pol, B, true)) || (rc = alloc_acts(l, l->ptg, l->pol, B, true)) ||
-      (rc = alloc_acts(l, l->con, l->cri, 2 * B, false)) ||
-      (rc = alloc_acts(l, l->ctg, l->cri, B, false)))
+      (rc = alloc_acts(l, l->con, l->cri, con_rows, false)) ||
+      (rc = alloc_acts(l, l->ctg, l->cri, ctg_rows, false)))
     return fail(rc);
+  if (mpo) {
+    const int64_t A = cfg->act_dim, NB = ctg_rows;
+    auto& mb = l->mb;
+    if ((rc = dev_alloc(l, &mb.sd_on, B * A)) || (rc = dev_alloc(l, &mb.sd_t, B * A)) ||
+        (rc = dev_alloc(l, &mb.noise, NB * A)) || (rc = dev_alloc(l, &mb.act, NB * A)) ||
+        (rc = dev_alloc(l, &mb.cost, NB)) || (rc = dev_alloc(l, &mb.tiled, NB * cfg->obs_dim)) ||
+        (rc = dev_alloc(l, &mb.w, NB)) || (rc = dev_alloc(l, &mb.pw, NB)) ||
+        (rc = dev_alloc(l, &mb.qt, B)) || (rc = dev_alloc(l, &mb.dmean, B * A)) ||
+        (rc = dev_alloc(l, &mb.dpre, B * A)) ||
+        (rc = dev_alloc(l, &mb.part, ceil_div(B, 4) * kMpoCols)) ||
+        (rc = dev_alloc(l, &mb.stats, ACME_MPO_NUM_STATS)) || (rc = dev_alloc(l, &mb.klm_rel, A)) ||
+        (rc = dev_alloc(l, &mb.kls_rel, A)) || (rc = dev_alloc(l, &mb.ploss, 1)))
+      return fail(rc);
+    if (hipMemset(mb.pw, 0, (size_t)NB * sizeof(float)) != hipSuccess)
+      return fail((set_error("hipMemset failed"), ACME_ERR_HIP));
+  }
   for (int i = 0; i < l->cri.nl; ++i)
     if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return fail(rc);
   for (int i = 0; i < l->pol.nl; ++i)
@@ -1518,7 +1749,11 @@ int acme_d4pg_step(acme_d4pg* l, const acme_d4pg_batch* batch, const acme_d4pg_o
   const bool copy = l->num_steps % l->cfg.target_update_period == 0;
   int rc;
   if (graphs_enabled() && !prof::enabled()) {
-    rc = run_graph(l, batch, out, copy, st);
+    const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                   batch->o_t, out ? out->critic_loss : nullptr,
+                                   out ? out->policy_loss : nullptr};
+    rc = run_graph(l, key, batch->batch, copy ? 1 : 0, st,
+                   [&](hipStream_t s) { return d4pg_step_impl(l, batch, out, copy, s); });
   } else {
     rc = d4pg_step_impl(l, batch, out, copy, st);
   }
@@ -1659,6 +1894,188 @@ int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n) {
 int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** out,
                            int64_t* count) {
   return acme_d4pg_debug_buffer(as_cd4pg(l), name, out, count);
+}
+
+// ------------------------------------------------------------------ MPO
+// The same learner object with the Gaussian policy head and the MPO loss (MPOLearner._step,
+// acme/agents/tf/mpo/learning.py:145-260).
+
+static acme_d4pg* as_d4pg(acme_mpo* l) { return reinterpret_cast<acme_d4pg*>(l); }
+static const acme_d4pg* as_cd4pg(const acme_mpo* l) {
+  return reinterpret_cast<const acme_d4pg*>(l);
+}
+
+int acme_mpo_create(const acme_mpo_config* cfg, acme_mpo** out) {
+  ACME_CHECK_ARG(cfg && out, "null argument");
+  ACME_CHECK_ARG(cfg->num_samples >= 1 && cfg->num_samples <= ACME_MPO_MAX_SAMPLES,
+                 "num_samples must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
+  // The target critic runs max_batch * num_samples rows through the GEMM engine and the
+  // LayerNorm row kernels, which take what D4PG's 2 * 65536 rows ask of them.
+  ACME_CHECK_ARG(cfg->max_batch >= 1 &&
+                     (int64_t)cfg->max_batch * cfg->num_samples <= ACME_MPO_MAX_ROWS,
+                 "max_batch * num_samples must be in [1, %d]", ACME_MPO_MAX_ROWS);
+  ACME_CHECK_ARG(cfg->target_policy_update_period >= 1 && cfg->target_critic_update_period >= 1,
+                 "target update periods must be >= 1");
+  ACME_CHECK_ARG(cfg->epsilon > 0.f && cfg->epsilon_mean > 0.f && cfg->epsilon_stddev > 0.f &&
+                     cfg->epsilon_penalty > 0.f,
+                 "the KL bounds (epsilon*) must be positive");
+  ACME_CHECK_ARG(cfg->init_scale > 0.f && cfg->min_scale >= 0.f,
+                 "init_scale must be positive and min_scale non-negative");
+  acme_d4pg_config c;
+  memset(&c, 0, sizeof(c));
+  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
+  c.num_policy_layers = cfg->num_policy_layers;
+  c.num_critic_layers = cfg->num_critic_layers;
+  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
+  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
+  c.num_atoms = 1; c.vmin = 0.f; c.vmax = 0.f;
+  memcpy(c.action_min, cfg->action_min, sizeof(c.action_min));
+  memcpy(c.action_max, cfg->action_max, sizeof(c.action_max));
+  c.discount = cfg->discount; c.target_update_period = 1;  // unused: MPO has its own two
+  c.policy_learning_rate = cfg->policy_learning_rate;
+  c.critic_learning_rate = cfg->critic_learning_rate;
+  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
+  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
+  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
+  acme_d4pg* l = nullptr;
+  const int rc = create_learner(&c, true, &l, cfg);
+  if (rc == ACME_OK) *out = reinterpret_cast<acme_mpo*>(l);
+  return rc;
+}
+
+int acme_mpo_destroy(acme_mpo* l) { return acme_d4pg_destroy(as_d4pg(l)); }
+int64_t acme_mpo_flat_size(const acme_mpo* l) { return acme_d4pg_flat_size(as_cd4pg(l)); }
+int64_t acme_mpo_policy_size(const acme_mpo* l) { return acme_d4pg_policy_size(as_cd4pg(l)); }
+int64_t acme_mpo_dual_offset(const acme_mpo* l) { return l ? as_cd4pg(l)->critic_end : 0; }
+int32_t acme_mpo_num_tensors(const acme_mpo* l) { return acme_d4pg_num_tensors(as_cd4pg(l)); }
+int acme_mpo_tensor_info(const acme_mpo* l, int32_t i, int64_t* offset, int64_t* numel,
+                         int32_t* ndim, int64_t* shape4, const char** name) {
+  return acme_d4pg_tensor_info(as_cd4pg(l), i, offset, numel, ndim, shape4, name);
+}
+int acme_mpo_bind(acme_mpo* l, float* params, float* target, float* grads, float* adam_m,
+                  float* adam_v) {
+  return acme_d4pg_bind(as_d4pg(l), params, target, grads, adam_m, adam_v);
+}
+
+int acme_mpo_init_duals(acme_mpo* h) {
+  acme_d4pg* l = as_d4pg(h);
+  ACME_CHECK_ARG(l && l->mpo, "not an MPO learner");
+  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
+  ACME_HIP_TRY(hipDeviceSynchronize());
+  const acme_mpo_config& mc = l->mcfg;
+  const std::pair<int, float> init[] = {{l->t_temp, mc.init_log_temperature},
+                                        {l->t_amean, mc.init_log_alpha_mean},
+                                        {l->t_astd, mc.init_log_alpha_stddev},
+                                        {l->t_ptemp, mc.init_log_temperature}};
+  for (const auto& it : init) {
+    if (it.first < 0) continue;
+    const Tensor& t = l->tensors[it.first];
+    const std::vector<float> v((size_t)t.numel, it.second);
+    ACME_HIP_TRY(hipMemcpy(l->params + t.offset, v.data(), v.size() * sizeof(float),
+                           hipMemcpyHostToDevice));
+  }
+  return ACME_OK;
+}
+
+int acme_mpo_step(acme_mpo* h, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
+                  void* stream) {
+  acme_d4pg* l = as_d4pg(h);
+  ACME_CHECK_ARG(l && batch, "null argument");
+  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
+  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
+  ACME_CHECK_ARG(batch->batch >= 1 && batch->batch <= l->cfg.max_batch,
+                 "batch %lld outside [1, max_batch=%d]", (long long)batch->batch,
+                 l->cfg.max_batch);
+  ACME_CHECK_ARG(batch->o_tm1 && batch->a_tm1 && batch->r_t && batch->d_t && batch->o_t,
+                 "null batch field");
+  hipStream_t st = as_stream(stream);
+  const int copy = (l->num_steps % l->mcfg.target_policy_update_period == 0 ? 1 : 0) |
+                   (l->num_steps % l->mcfg.target_critic_update_period == 0 ? 2 : 0);
+  int rc;
+  if (graphs_enabled() && !prof::enabled()) {
+    const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                   batch->o_t, batch->noise,
+                                   out ? out->critic_loss : nullptr,
+                                   out ? out->policy_loss : nullptr,
+                                   out ? out->stats : nullptr,
+                                   out ? out->kl_mean_rel : nullptr,
+                                   out ? out->kl_stddev_rel : nullptr};
+    rc = run_graph(l, key, batch->batch, copy, st,
+                   [&](hipStream_t s) { return mpo_step_impl(l, batch, out, copy, s); });
+  } else {
+    rc = mpo_step_impl(l, batch, out, copy, st);
+  }
+  if (rc != ACME_OK) return rc;
+  l->num_steps += 1;
+  return ACME_OK;
+}
+
+int acme_mpo_policy(acme_mpo* h, const float* obs, int64_t rows, int32_t use_target,
+                    float* mean_out, float* stddev_out, void* stream) {
+  acme_d4pg* l = as_d4pg(h);
+  ACME_CHECK_ARG(l && obs && mean_out && stddev_out, "null argument");
+  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
+  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
+  ACME_CHECK_ARG(rows >= 0, "negative row count");
+  hipStream_t st = as_stream(stream);
+  const int B = l->cfg.max_batch, A = l->cfg.act_dim;
+  const NetDesc& pd = l->pol;
+  const float* prm = use_target ? l->target : l->params;
+  for (int64_t r0 = 0; r0 < rows; r0 += B) {
+    const int n = (int)std::min<int64_t>(B, rows - r0);
+    const float* o = obs + r0 * l->cfg.obs_dim;
+    const NetIn in[2] = {{prm, o, nullptr, o, nullptr, n, n, &l->ptg},
+                         {l->params, o, nullptr, o, nullptr, n, 0, &l->ptg}};
+    int rc = lnmlp_forward_pair(l, pd, in, l->cfg.obs_dim, 0, "mpo_policy_ln", st);
+    if (rc != ACME_OK) return rc;
+    GaussHeadPair g;
+    g.a[0] = {l->ptg.h[pd.nl - 1], P(l, prm, pd.ow), P(l, prm, pd.ob), P(l, prm, l->sw),
+              P(l, prm, l->sb), n, mean_out + r0 * A, nullptr, stddev_out + r0 * A};
+    g.a[1] = g.a[0];
+    g.H = pd.sizes[pd.nl - 1]; g.A = A;
+    g.scale_mul = (float)((double)l->mcfg.init_scale / std::log(2.0));
+    g.min_scale = l->mcfg.min_scale;
+    gauss_head_kernel<<<dim3((unsigned)ceil_div(n, 4), 1), 256, 0, st>>>(g);
+    D4_CHECK();
+  }
+  return ACME_OK;
+}
+
+int64_t acme_mpo_num_steps(const acme_mpo* l) { return acme_d4pg_num_steps(as_cd4pg(l)); }
+int acme_mpo_set_num_steps(acme_mpo* l, int64_t n) {
+  return acme_d4pg_set_num_steps(as_d4pg(l), n);
+}
+
+int acme_mpo_debug_buffer(const acme_mpo* h, const char* name, const float** out,
+                          int64_t* count) {
+  const acme_d4pg* l = as_cd4pg(h);
+  ACME_CHECK_ARG(l && name && out && count, "null argument");
+  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
+  const int64_t B = l->cfg.max_batch, A = l->cfg.act_dim, NB = B * l->mcfg.num_samples;
+  const auto& mb = l->mb;
+  const struct {
+    const char* n;
+    const float* p;
+    int64_t c;
+  } items[] = {
+      {"mean_on", l->pon.out, B * A}, {"std_on", mb.sd_on, B * A}, {"pre_on", l->pon.t, B * A},
+      {"mean_t", l->ptg.out, B * A},  {"std_t", mb.sd_t, B * A},   {"noise", mb.noise, NB * A},
+      {"actions", mb.act, NB * A},    {"cost", mb.cost, NB},       {"sampled_q", l->ctg.out, NB},
+      {"weights", mb.w, NB},          {"penalty_weights", mb.pw, NB},
+      {"q_tm1", l->con.out, B},       {"q_t", mb.qt, B},           {"td", l->td, B},
+      {"dq", l->dq, B},               {"dmean", mb.dmean, B * A},  {"dpre", mb.dpre, B * A},
+      {"norms", l->norms, 2},         {"losses", l->loss_tmp, 2},
+      {"stats", mb.stats, ACME_MPO_NUM_STATS},
+      {"kl_mean_rel", mb.klm_rel, A}, {"kl_stddev_rel", mb.kls_rel, A},
+  };
+  for (const auto& it : items)
+    if (strcmp(it.n, name) == 0) {
+      *out = it.p;
+      *count = it.c;
+      return ACME_OK;
+    }
+  set_error("unknown debug buffer '%s'", name);
+  return ACME_ERR_INVALID;
 }
 
 }  // extern "C"

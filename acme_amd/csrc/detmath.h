@@ -67,6 +67,8 @@ ACME_HD double u01_53(uint32_t a, uint32_t b) {
 // Counter layout for replay sampling: (sample index, step lo, step hi, stream tag).
 constexpr uint32_t kSampleTag = 0x534D504Cu;  // "SMPL"
 constexpr uint32_t kFillTag = 0x46494C4Cu;    // "FILL"
+// MPO's action-sampling noise (d4pg.hip): counter (element / 4, step lo, step hi, tag).
+constexpr uint32_t kMpoNoiseTag = 0x4D504F4Eu;  // "MPON"
 
 ACME_HD double sample_uniform(uint64_t seed, uint64_t step, uint32_t j) {
   u32x4 c = {j, (uint32_t)step, (uint32_t)(step >> 32), kSampleTag};

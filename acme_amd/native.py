@@ -697,7 +697,9 @@ class _NativeActorCritic:
             cfg.action_min[j], cfg.action_max[j] = float(lo[j]), float(hi[j])
         for k, v in extra.items():  # the fields only this learner has
             setattr(cfg, k, v)
-        cfg.discount, cfg.target_update_period = discount, int(target_update_period)
+        cfg.discount = discount
+        if target_update_period is not None:  # MPO has two periods of its own
+            cfg.target_update_period = int(target_update_period)
         cfg.policy_learning_rate, cfg.critic_learning_rate = policy_learning_rate, critic_learning_rate
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
         cfg.clipping = 1 if clipping else 0
@@ -833,6 +835,123 @@ class NativeDDPG(_NativeActorCritic):
                     critic_learning_rate=critic_learning_rate, clipping=clipping,
                     adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
                     layer_norm_epsilon=layer_norm_epsilon, device=device)
+
+
+class NativeMPO(_NativeActorCritic):
+    """acme_mpo learner (Gaussian policy head, N sampled actions per state, scalar critic,
+    decoupled MPO loss) + its flat buffers: policy tensors, critic tensors, then the dual
+    variables `mpo/log_*`, which so share `views`, `get_params` and the Adam moment buffers.
+    The step's stats are device tensors: `stats` (in `stat_names` order), `kl_mean_rel` and
+    `kl_stddev_rel` ([act_dim] with per_dim_constraining, else [1])."""
+
+    _prefix, _tag, _config = "acme_mpo", "mpo", _lib.MPOConfig
+    stat_names = _lib.MPO_STATS
+
+    def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int,
+                 policy_sizes: Sequence[int] = (256, 256, 256),
+                 critic_sizes: Sequence[int] = (512, 512, 256), num_samples: int = 20,
+                 discount: float = 0.99, target_policy_update_period: int = 100,
+                 target_critic_update_period: int = 100, policy_learning_rate: float = 1e-4,
+                 critic_learning_rate: float = 1e-4, dual_learning_rate: float = 1e-2,
+                 clipping: bool = True, epsilon: float = 1e-1, epsilon_mean: float = 1e-3,
+                 epsilon_stddev: float = 1e-6, epsilon_penalty: float = 1e-3,
+                 init_log_temperature: float = 1.0, init_log_alpha_mean: float = 1.0,
+                 init_log_alpha_stddev: float = 10.0, per_dim_constraining: bool = True,
+                 action_penalization: bool = True, init_scale: float = 0.3,
+                 min_scale: float = 1e-6, seed: int = 0, adam_beta1: float = 0.9,
+                 adam_beta2: float = 0.999, adam_epsilon: float = 1e-8,
+                 layer_norm_epsilon: float = 1e-5, device=None):
+        if not 1 <= num_samples <= _lib.MPO_MAX_SAMPLES:
+            raise ValueError(f"num_samples must be in [1, {_lib.MPO_MAX_SAMPLES}]")
+        self.num_samples = int(num_samples)
+        self._setup(obs_dim=obs_dim, act_dim=act_dim, max_batch=max_batch,
+                    policy_sizes=policy_sizes, critic_sizes=critic_sizes, action_min=None,
+                    action_max=None, discount=discount, target_update_period=None,
+                    policy_learning_rate=policy_learning_rate,
+                    critic_learning_rate=critic_learning_rate, clipping=clipping,
+                    adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
+                    layer_norm_epsilon=layer_norm_epsilon, device=device,
+                    num_samples=int(num_samples),
+                    target_policy_update_period=int(target_policy_update_period),
+                    target_critic_update_period=int(target_critic_update_period),
+                    dual_learning_rate=dual_learning_rate, epsilon=epsilon,
+                    epsilon_mean=epsilon_mean, epsilon_stddev=epsilon_stddev,
+                    epsilon_penalty=epsilon_penalty, init_log_temperature=init_log_temperature,
+                    init_log_alpha_mean=init_log_alpha_mean,
+                    init_log_alpha_stddev=init_log_alpha_stddev,
+                    per_dim_constraining=1 if per_dim_constraining else 0,
+                    action_penalization=1 if action_penalization else 0,
+                    init_scale=init_scale, min_scale=min_scale,
+                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self.dual_offset = int(self._fn("dual_offset")(self._h))
+        self.dual_dim = self.act_dim if per_dim_constraining else 1
+        check(self._fn("init_duals")(self._h), "mpo init_duals")
+        d = self.device
+        self.stats = torch.zeros(len(self.stat_names), dtype=torch.float32, device=d)
+        self.kl_mean_rel = torch.zeros(self.dual_dim, dtype=torch.float32, device=d)
+        self.kl_stddev_rel = torch.zeros(self.dual_dim, dtype=torch.float32, device=d)
+
+    def set_params(self, params: Dict[str, np.ndarray], target: Optional[Dict] = None) -> None:
+        """As the other learners'; dual variables absent from `params` keep their values (the
+        initial ones after construction), and the target buffer's dual slots are never used."""
+        for flat, src in ((self.params, params), (self.target, target if target is not None else params)):
+            for name, t in self.views(flat).items():
+                if name in src:
+                    t.copy_(torch.as_tensor(np.asarray(src[name], np.float32)).view(t.shape))
+                elif not name.startswith("mpo/"):
+                    raise KeyError(name)
+
+    def stat(self, name: str) -> torch.Tensor:
+        """One entry of the reference's stats dict as a device scalar (a view of `stats`)."""
+        if name in ("kl_mean_rel", "kl_stddev_rel"):
+            return getattr(self, name)
+        return self.stats[self.stat_names.index(name)]
+
+    def step(self, o_tm1, a_tm1, r_t, d_t, o_t, noise=None, stream=None):
+        """One learner step.  `noise`: eps [num_samples, B, act_dim] to sample the target
+        policy's actions with (tests); None: generated on the device from (seed, step)."""
+        B = int(r_t.shape[0])
+        checks = [("o_tm1", o_tm1, self.obs_dim), ("a_tm1", a_tm1, self.act_dim),
+                  ("r_t", r_t, None), ("d_t", d_t, None), ("o_t", o_t, self.obs_dim)]
+        for name, t, cols in checks:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
+                    and t.dtype == torch.float32):
+                raise ValueError(f"{name} must be a contiguous float32 device tensor")
+            if t.shape[0] != B or (cols is not None and t.numel() != B * cols):
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {cols}]")
+        b = _lib.MPOBatch()
+        b.o_tm1, b.a_tm1, b.r_t, b.d_t, b.o_t = (ptr(o_tm1), ptr(a_tm1), ptr(r_t), ptr(d_t),
+                                                 ptr(o_t))
+        b.batch = B
+        if noise is not None:
+            if not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.is_contiguous()
+                    and noise.dtype == torch.float32
+                    and noise.numel() == self.num_samples * B * self.act_dim):
+                raise ValueError(f"noise must be a contiguous float32 device tensor of shape "
+                                 f"[{self.num_samples}, {B}, {self.act_dim}]")
+            b.noise = ptr(noise)
+        out = _lib.MPOOutputs()
+        out.critic_loss, out.policy_loss = ptr(self.critic_loss), ptr(self.policy_loss)
+        out.stats, out.kl_mean_rel = ptr(self.stats), ptr(self.kl_mean_rel)
+        out.kl_stddev_rel = ptr(self.kl_stddev_rel)
+        check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(out), stream_ptr(stream)),
+              "mpo step")
+
+    def policy_distribution(self, obs: torch.Tensor, use_target: bool = False, stream=None):
+        """(mean, stddev) [rows, act_dim] of the policy's diagonal Gaussian."""
+        rows = int(obs.shape[0])
+        obs = obs.reshape(rows, -1).to(self.device, torch.float32).contiguous()
+        if obs.shape[1] != self.obs_dim:
+            raise ValueError(f"observations must have {self.obs_dim} features")
+        mean = torch.empty(rows, self.act_dim, dtype=torch.float32, device=self.device)
+        stddev = torch.empty_like(mean)
+        check(self._fn("policy")(self._h, ptr(obs), rows, 1 if use_target else 0, ptr(mean),
+                                 ptr(stddev), stream_ptr(stream)), "mpo policy")
+        return mean, stddev
+
+    def policy(self, obs: torch.Tensor, use_target: bool = False, stream=None) -> torch.Tensor:
+        """The distribution's mean (the greedy action)."""
+        return self.policy_distribution(obs, use_target, stream)[0]
 
 
 class NativeIMPALA:

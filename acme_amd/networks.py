@@ -315,6 +315,66 @@ def make_ddpg_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 
     }
 
 
+@dataclasses.dataclass(frozen=True)
+class LayerNormMLPGaussianPolicy:
+    """snt.Sequential([LayerNormMLP(sizes, activate_final=True),
+    MultivariateNormalDiagHead(act_dim, init_scale, min_scale)]): MPO's policy
+    (acme/agents/tf/mpo/agent_test.py:34-40, acme/tf/networks/distributional.py:70-129 with
+    tanh_mean, fixed_scale and use_tfd_independent off).  The head's mean layer is
+    `.../linear`, its scale layer `.../linear_1`; stddev = softplus(scale layer) * init_scale /
+    softplus(0) + min_scale."""
+
+    obs_dim: int
+    act_dim: int
+    layer_sizes: Tuple[int, ...] = (256, 256, 256)
+    init_scale: float = 0.3
+    min_scale: float = 1e-6
+
+    def __init__(self, obs_dim: int, act_dim: int, layer_sizes: Sequence[int] = (256, 256, 256),
+                 init_scale: float = 0.3, min_scale: float = 1e-6):
+        object.__setattr__(self, "obs_dim", int(obs_dim))
+        object.__setattr__(self, "act_dim", int(act_dim))
+        object.__setattr__(self, "layer_sizes", tuple(int(s) for s in layer_sizes))
+        object.__setattr__(self, "init_scale", float(init_scale))
+        object.__setattr__(self, "min_scale", float(min_scale))
+
+    def tensor_shapes(self):
+        s = list(self.layer_sizes)
+        head = "policy/multivariate_normal_diag_head"
+        return _layer_norm_mlp_shapes("policy", self.obs_dim, s) + [
+            (head + "/linear/w", (s[-1], self.act_dim)), (head + "/linear/b", (self.act_dim,)),
+            (head + "/linear_1/w", (s[-1], self.act_dim)), (head + "/linear_1/b", (self.act_dim,))]
+
+    def init(self, seed: int = 0) -> Dict[str, np.ndarray]:
+        rng = np.random.default_rng(seed)
+        out: Dict[str, np.ndarray] = {}
+        shapes = self.tensor_shapes()
+        _init_layer_norm_mlp(rng, shapes[:-4], out)
+        # Both head layers: tf.initializers.VarianceScaling(1e-4) = truncated normal, fan_in
+        # (distributional.py:81-82); stddev corrected for the 2-sigma truncation.  Zero biases.
+        for name, shape in shapes[-4:]:
+            if name.endswith("/w"):
+                out[name] = truncated_normal(rng, shape,
+                                             np.sqrt(1e-4 / shape[0]) / 0.87962566103423978)
+            else:
+                out[name] = np.zeros(shape, np.float32)
+        return out
+
+
+def make_mpo_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 256),
+                      critic_layer_sizes=(512, 512, 256), init_scale: float = 0.3,
+                      min_scale: float = 1e-6) -> Dict[str, object]:
+    """MPO's networks: a Gaussian LayerNormMLP policy and DDPG's scalar LayerNormMLP critic
+    (observation network = identity)."""
+    act_dim = int(np.prod(action_spec.shape))
+    return {
+        "policy": LayerNormMLPGaussianPolicy(obs_dim, act_dim, policy_layer_sizes, init_scale,
+                                             min_scale),
+        "critic": LayerNormMLPCritic(obs_dim, act_dim, critic_layer_sizes),
+        "observation": "identity",
+    }
+
+
 # ------------------------------------------------------------------ IMPALA (Atari)
 
 

@@ -632,6 +632,128 @@ int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n);
 int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** out,
                            int64_t* count);
 
+/* ------------------------------------------------------------------- MPO -- */
+/* Replaces MPOLearner._step (acme/agents/tf/mpo/learning.py:145-260) with the decoupled MPO
+ * loss (acme/tf/losses/mpo.py:145-430): policy = LayerNormMLP(policy_sizes, activate_final) ->
+ * MultivariateNormalDiagHead(act_dim) (acme/tf/networks/distributional.py:70-129; tanh_mean,
+ * fixed_scale and use_tfd_independent off), critic = DDPG's scalar LayerNormMLP(critic_sizes +
+ * (1,)), identity observation network.  The same native learner object as D4PG and DDPG with a
+ * third head kind; the size limits are ACME_D4PG_MAX_LAYERS / ACME_D4PG_MAX_ACT.
+ *
+ * Flat buffers: policy tensors (the head's mean layer "policy/multivariate_normal_diag_head/
+ * linear/{w,b}", then its scale layer ".../linear_1/{w,b}"), critic tensors, then the dual
+ * variables "mpo/log_temperature" [1], "mpo/log_alpha_mean" [D], "mpo/log_alpha_stddev" [D]
+ * (D = act_dim with per_dim_constraining, else 1) and, with action_penalization,
+ * "mpo/log_penalty_temperature" [1].  The target buffer has the duals' slots too; the step
+ * neither reads nor writes them.
+ *
+ * Sampling noise: eps[n][b][d] ~ N(0, 1), element e = (n B + b) act_dim + d.  With
+ * batch->noise null it is generated on the device: Philox4x32-10 with key = seed and counter
+ * (e / 4, step lo, step hi, 0x4D504F4E), step = the learner's num_steps before the step; the
+ * call's words (x, y, z, w) give elements 4 (e / 4) .. + 3 by Box-Muller on (x, y) and (z, w):
+ * u1 = ((x >> 8) + 1) 2^-24 in (0, 1], u2 = (y >> 8) 2^-24, rad = sqrt(-2 log u1),
+ * (rad cospi(2 u2), rad sinpi(2 u2)). */
+#define ACME_MPO_MAX_SAMPLES 64
+#define ACME_MPO_MAX_ROWS 131072 /* max_batch * num_samples */
+
+/* acme_mpo_outputs.stats, in this order (the reference's stats dict, mpo.py:285-313). */
+enum {
+  ACME_MPO_STAT_DUAL_ALPHA_MEAN = 0,
+  ACME_MPO_STAT_DUAL_ALPHA_STDDEV,
+  ACME_MPO_STAT_DUAL_TEMPERATURE,
+  ACME_MPO_STAT_LOSS_POLICY,
+  ACME_MPO_STAT_LOSS_ALPHA,
+  ACME_MPO_STAT_LOSS_TEMPERATURE,
+  ACME_MPO_STAT_KL_Q_REL,
+  ACME_MPO_STAT_PENALTY_KL_Q_REL, /* 0 without action_penalization */
+  ACME_MPO_STAT_Q_MIN,
+  ACME_MPO_STAT_Q_MAX,
+  ACME_MPO_STAT_PI_STDDEV_MIN,
+  ACME_MPO_STAT_PI_STDDEV_MAX,
+  ACME_MPO_STAT_PI_STDDEV_COND,
+  ACME_MPO_NUM_STATS
+};
+
+typedef struct acme_mpo acme_mpo;
+
+typedef struct acme_mpo_config {
+  int32_t obs_dim;              /* flat observation size (<= 64 - act_dim) */
+  int32_t act_dim;              /* <= ACME_D4PG_MAX_ACT */
+  int32_t max_batch;            /* max_batch * num_samples <= ACME_MPO_MAX_ROWS */
+  int32_t num_policy_layers;    /* LayerNormMLP sizes, 1..ACME_D4PG_MAX_LAYERS */
+  int32_t policy_sizes[ACME_D4PG_MAX_LAYERS];
+  int32_t num_critic_layers;    /* hidden sizes; the width-1 output layer is implied */
+  int32_t critic_sizes[ACME_D4PG_MAX_LAYERS];
+  float action_min[ACME_D4PG_MAX_ACT];  /* unused: the Gaussian policy is unbounded and the */
+  float action_max[ACME_D4PG_MAX_ACT];  /* out-of-bound cost is taken against [-1, 1] */
+  float discount;
+  float policy_learning_rate, critic_learning_rate;
+  float adam_beta1, adam_beta2, adam_epsilon;   /* of all three optimizers */
+  int32_t clipping;             /* global-norm clip 40 of the policy and of the critic gradients */
+  float layer_norm_epsilon;
+  int32_t num_samples;          /* N in [1, ACME_MPO_MAX_SAMPLES] */
+  int32_t target_policy_update_period, target_critic_update_period;
+  float dual_learning_rate;
+  float epsilon, epsilon_mean, epsilon_stddev, epsilon_penalty;
+  float init_log_temperature, init_log_alpha_mean, init_log_alpha_stddev;
+  int32_t per_dim_constraining, action_penalization;
+  float init_scale, min_scale;  /* MultivariateNormalDiagHead */
+  uint64_t seed;                /* key of the generated sampling noise */
+} acme_mpo_config;
+
+typedef struct acme_mpo_batch {
+  const float* o_tm1;  /* [B, obs_dim] */
+  const float* a_tm1;  /* [B, act_dim] */
+  const float* r_t;    /* [B] */
+  const float* d_t;    /* [B] */
+  const float* o_t;    /* [B, obs_dim] */
+  int64_t batch;
+  const float* noise;  /* [N, B, act_dim] eps to sample with (tests), or null: generated */
+} acme_mpo_batch;
+
+typedef struct acme_mpo_outputs {
+  float* critic_loss;    /* [1] device (optional) */
+  float* policy_loss;    /* [1] the MPO loss, dual losses included (optional) */
+  float* stats;          /* [ACME_MPO_NUM_STATS] (optional) */
+  float* kl_mean_rel;    /* [D] (optional) */
+  float* kl_stddev_rel;  /* [D] (optional) */
+} acme_mpo_outputs;
+
+int acme_mpo_create(const acme_mpo_config* cfg, acme_mpo** out);
+int acme_mpo_destroy(acme_mpo* l);
+int64_t acme_mpo_flat_size(const acme_mpo* l);
+/* Floats [0, policy_size) are the policy's, [policy_size, dual_offset) the critic's,
+ * [dual_offset, flat_size) the duals' (unclipped, dual_learning_rate). */
+int64_t acme_mpo_policy_size(const acme_mpo* l);
+int64_t acme_mpo_dual_offset(const acme_mpo* l);
+int32_t acme_mpo_num_tensors(const acme_mpo* l);
+int acme_mpo_tensor_info(const acme_mpo* l, int32_t i, int64_t* offset, int64_t* numel,
+                         int32_t* ndim, int64_t* shape4, const char** name);
+int acme_mpo_bind(acme_mpo* l, float* params, float* target, float* grads, float* adam_m,
+                  float* adam_v);
+/* Writes the config's init_log_* into the bound params' dual slots (create_dual_variables_once,
+ * mpo.py:110-143; the penalty temperature starts at init_log_temperature). */
+int acme_mpo_init_duals(acme_mpo* l);
+/* One learner step: the two target copies under their own periods, num_steps += 1, the
+ * critic's TD loss against the mean of N sampled target values, the MPO loss, global-norm
+ * clipping of the policy and critic gradients, three Adams; the log-duals are left projected
+ * to >= -18 and updated. */
+int acme_mpo_step(acme_mpo* l, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
+                  void* stream);
+/* Policy forward (actor / evaluation): the distribution's parameters, [rows, act_dim] each. */
+int acme_mpo_policy(acme_mpo* l, const float* obs, int64_t rows, int32_t use_target,
+                    float* mean_out, float* stddev_out, void* stream);
+int64_t acme_mpo_num_steps(const acme_mpo* l);
+int acme_mpo_set_num_steps(acme_mpo* l, int64_t n);
+/* Internal device workspaces (tests), sized for max_batch (the step packs B rows densely):
+ * "mean_on" "std_on" "pre_on" "mean_t" "std_t" (B x act_dim), "noise" (the eps used) "actions"
+ * (N B x act_dim), "cost" "sampled_q" "weights" "penalty_weights" (N B), "q_tm1" "q_t" "td" "dq"
+ * (B), "dmean" "dpre" (B x act_dim, dloss / d online mean and pre-softplus scale), "norms"
+ * (policy / critic gradient global norms before clipping), "losses", "stats", "kl_mean_rel",
+ * "kl_stddev_rel". */
+int acme_mpo_debug_buffer(const acme_mpo* l, const char* name, const float** out,
+                          int64_t* count);
+
 /* ---------------------------------------------------------------- IMPALA -- */
 /* Replaces IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with
  * IMPALAAtariNetwork (acme/tf/networks/atari.py:115-144): OAREmbedding(AtariTorso) ->
