@@ -39,6 +39,25 @@ class GaussianBehaviourPolicy:
         return np.clip(a, self._min, self._max)
 
 
+def make_transition_replay(environment_spec, table_name: str, max_size: int, n_step: int,
+                           discount: float, batch_size: int, prefetch_size: int, seed: int):
+    """The replay side of the D4PG, DDPG and MPO agents: a uniform-sample, FIFO-remove table
+    of n-step transitions behind a server, the adder that fills it and the dataset the
+    learner draws from.  Returns (server, adder, dataset)."""
+    table = replay.Table(
+        name=table_name, sampler=replay.selectors.Uniform(), remover=replay.selectors.Fifo(),
+        max_size=max_size, rate_limiter=replay.rate_limiters.MinSize(1),
+        signature=adders.NStepTransitionAdder.signature(environment_spec), seed=4321 + seed)
+    server = replay.Server([table], port=None)
+    address = f"localhost:{server.port}"
+    adder = adders.NStepTransitionAdder(priority_fns={table_name: lambda x: 1.},
+                                        client=replay.Client(address), n_step=n_step,
+                                        discount=discount)
+    dataset = datasets.make_reverb_dataset(table=table_name, server_address=address,
+                                           batch_size=batch_size, prefetch_size=prefetch_size)
+    return server, adder, dataset
+
+
 class D4PG(agent.Agent):
 
     def __init__(self, environment_spec: specs.EnvironmentSpec, policy_network, critic_network,
@@ -49,19 +68,9 @@ class D4PG(agent.Agent):
                  n_step: int = 5, sigma: float = 0.3, clipping: bool = True, logger=None,
                  counter=None, checkpoint: bool = True,
                  replay_table_name: str = adders.DEFAULT_PRIORITY_TABLE, seed: int = 0):
-        table = replay.Table(
-            name=replay_table_name, sampler=replay.selectors.Uniform(),
-            remover=replay.selectors.Fifo(), max_size=max_replay_size,
-            rate_limiter=replay.rate_limiters.MinSize(1),
-            signature=adders.NStepTransitionAdder.signature(environment_spec), seed=4321 + seed)
-        self._server = replay.Server([table], port=None)
-        address = f"localhost:{self._server.port}"
-        adder = adders.NStepTransitionAdder(priority_fns={replay_table_name: lambda x: 1.},
-                                            client=replay.Client(address), n_step=n_step,
-                                            discount=discount)
-        dataset = datasets.make_reverb_dataset(table=replay_table_name, server_address=address,
-                                               batch_size=batch_size,
-                                               prefetch_size=prefetch_size)
+        self._server, adder, dataset = make_transition_replay(
+            environment_spec, replay_table_name, max_replay_size, n_step, discount, batch_size,
+            prefetch_size, seed)
         learner = learning.D4PGLearner(
             policy_network=policy_network, critic_network=critic_network,
             target_policy_network=copy.deepcopy(policy_network),

@@ -37,7 +37,15 @@ def _is_identity(fn) -> bool:
         return False
 
 
+def _learning_rate(optimizer, default: float = 1e-4) -> float:
+    return float(getattr(optimizer, "learning_rate", default)) if optimizer is not None else default
+
+
 class D4PGLearner(core.Learner, core.Saveable):
+    """Also the base of DDPGLearner and MPOLearner, which build another native handle from
+    the same pieces (`_check_networks`, `_init_params`, `_init_bookkeeping`)."""
+
+    _algorithm = "D4PG"  # names the learner in messages
 
     def __init__(self, policy_network, critic_network, target_policy_network,
                  target_critic_network, discount: float, target_update_period: int, dataset,
@@ -46,17 +54,8 @@ class D4PGLearner(core.Learner, core.Saveable):
                  counter: Optional[counting.Counter] = None,
                  logger: Optional[loggers.Logger] = None, checkpoint: bool = True,
                  batch_size: Optional[int] = None, seed: int = 0, device=None):
-        if not (_is_identity(observation_network) and _is_identity(target_observation_network)):
-            raise ValueError("acme_amd's D4PG learner supports identity observation networks "
-                             "(flat observations) only")
-        if critic_network.obs_dim != policy_network.obs_dim or \
-                critic_network.act_dim != policy_network.act_dim:
-            raise ValueError("policy and critic disagree on observation / action sizes")
-        self._policy_network = policy_network
-        self._critic_network = critic_network
-        self._iterator = iter(dataset)
-        B = batch_size or getattr(dataset, "batch_size", None) or 256
-        lr = lambda opt: float(getattr(opt, "learning_rate", 1e-4)) if opt is not None else 1e-4  # noqa
+        B = self._check_networks(policy_network, critic_network, observation_network,
+                                 target_observation_network, dataset, batch_size)
         self._native = NativeD4PG(
             obs_dim=policy_network.obs_dim, act_dim=policy_network.act_dim, max_batch=B,
             policy_sizes=policy_network.layer_sizes, critic_sizes=critic_network.layer_sizes,
@@ -64,13 +63,36 @@ class D4PGLearner(core.Learner, core.Saveable):
             vmax=critic_network.vmax, action_min=policy_network.action_min,
             action_max=policy_network.action_max, discount=discount,
             target_update_period=target_update_period,
-            policy_learning_rate=lr(policy_optimizer), critic_learning_rate=lr(critic_optimizer),
+            policy_learning_rate=_learning_rate(policy_optimizer),
+            critic_learning_rate=_learning_rate(critic_optimizer),
             clipping=clipping, device=device)
-        init = dict(policy_network.init(seed))
-        init.update(critic_network.init(seed + 1))
+        self._init_params(target_policy_network, target_critic_network, seed)
+        self._init_bookkeeping(counter, logger, checkpoint)
+
+    def _check_networks(self, policy_network, critic_network, observation_network,
+                        target_observation_network, dataset, batch_size) -> int:
+        """The identity and size checks; keeps the networks and the dataset iterator and
+        returns the batch size the native learner is built for."""
+        if not (_is_identity(observation_network) and _is_identity(target_observation_network)):
+            raise ValueError(f"acme_amd's {self._algorithm} learner supports identity "
+                             "observation networks (flat observations) only")
+        if critic_network.obs_dim != policy_network.obs_dim or \
+                critic_network.act_dim != policy_network.act_dim:
+            raise ValueError("policy and critic disagree on observation / action sizes")
+        self._policy_network = policy_network
+        self._critic_network = critic_network
+        self._iterator = iter(dataset)
+        return batch_size or getattr(dataset, "batch_size", None) or 256
+
+    def _init_params(self, target_policy_network, target_critic_network, seed: int) -> None:
+        """Online and target parameters from init(seed + 0..3), into the native buffers."""
+        init = dict(self._policy_network.init(seed))
+        init.update(self._critic_network.init(seed + 1))
         tinit = dict(target_policy_network.init(seed + 2))
         tinit.update(target_critic_network.init(seed + 3))
         self._native.set_params(init, tinit)
+
+    def _init_bookkeeping(self, counter, logger, checkpoint) -> None:
         self._counter = counter or counting.Counter()
         self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
         self._timestamp = None

@@ -12,11 +12,11 @@ from __future__ import annotations
 
 import copy
 
-from acme_amd import datasets, replay, specs
+from acme_amd import specs
 from acme_amd.adders import reverb as adders
 from acme_amd.agents import agent
 from acme_amd.agents.actors import FeedForwardActor
-from acme_amd.agents.d4pg.agent import GaussianBehaviourPolicy
+from acme_amd.agents.d4pg.agent import GaussianBehaviourPolicy, make_transition_replay
 from acme_amd.agents.ddpg import learning
 
 
@@ -29,19 +29,9 @@ class DDPG(agent.Agent):
                  samples_per_insert: float = 32.0, n_step: int = 5, sigma: float = 0.3,
                  clipping: bool = True, logger=None, counter=None, checkpoint: bool = True,
                  replay_table_name: str = adders.DEFAULT_PRIORITY_TABLE, seed: int = 0):
-        table = replay.Table(
-            name=replay_table_name, sampler=replay.selectors.Uniform(),
-            remover=replay.selectors.Fifo(), max_size=max_replay_size,
-            rate_limiter=replay.rate_limiters.MinSize(1),
-            signature=adders.NStepTransitionAdder.signature(environment_spec), seed=4321 + seed)
-        self._server = replay.Server([table], port=None)
-        address = f"localhost:{self._server.port}"
-        adder = adders.NStepTransitionAdder(priority_fns={replay_table_name: lambda x: 1.},
-                                            client=replay.Client(address), n_step=n_step,
-                                            discount=discount)
-        dataset = datasets.make_reverb_dataset(table=replay_table_name, server_address=address,
-                                               batch_size=batch_size,
-                                               prefetch_size=prefetch_size)
+        self._server, adder, dataset = make_transition_replay(
+            environment_spec, replay_table_name, max_replay_size, n_step, discount, batch_size,
+            prefetch_size, seed)
         learner = learning.DDPGLearner(
             policy_network=policy_network, critic_network=critic_network,
             target_policy_network=copy.deepcopy(policy_network),

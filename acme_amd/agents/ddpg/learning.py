@@ -17,12 +17,14 @@ from __future__ import annotations
 
 from typing import Optional
 
-from acme_amd.agents.d4pg.learning import D4PGLearner, _is_identity
+from acme_amd.agents.d4pg.learning import D4PGLearner, _learning_rate
 from acme_amd.native import NativeDDPG
 from acme_amd.utils import counting, loggers
 
 
 class DDPGLearner(D4PGLearner):
+
+    _algorithm = "DDPG"
 
     def __init__(self, policy_network, critic_network, target_policy_network,
                  target_critic_network, discount: float, target_update_period: int, dataset,
@@ -31,30 +33,15 @@ class DDPGLearner(D4PGLearner):
                  counter: Optional[counting.Counter] = None,
                  logger: Optional[loggers.Logger] = None, checkpoint: bool = True,
                  batch_size: Optional[int] = None, seed: int = 0, device=None):
-        if not (_is_identity(observation_network) and _is_identity(target_observation_network)):
-            raise ValueError("acme_amd's DDPG learner supports identity observation networks "
-                             "(flat observations) only")
-        if critic_network.obs_dim != policy_network.obs_dim or \
-                critic_network.act_dim != policy_network.act_dim:
-            raise ValueError("policy and critic disagree on observation / action sizes")
-        self._policy_network = policy_network
-        self._critic_network = critic_network
-        self._iterator = iter(dataset)
-        B = batch_size or getattr(dataset, "batch_size", None) or 256
-        lr = lambda opt: float(getattr(opt, "learning_rate", 1e-4)) if opt is not None else 1e-4  # noqa
+        B = self._check_networks(policy_network, critic_network, observation_network,
+                                 target_observation_network, dataset, batch_size)
         self._native = NativeDDPG(
             obs_dim=policy_network.obs_dim, act_dim=policy_network.act_dim, max_batch=B,
             policy_sizes=policy_network.layer_sizes, critic_sizes=critic_network.layer_sizes,
             action_min=policy_network.action_min, action_max=policy_network.action_max,
             discount=discount, target_update_period=target_update_period,
-            policy_learning_rate=lr(policy_optimizer), critic_learning_rate=lr(critic_optimizer),
+            policy_learning_rate=_learning_rate(policy_optimizer),
+            critic_learning_rate=_learning_rate(critic_optimizer),
             clipping=clipping, device=device)
-        init = dict(policy_network.init(seed))
-        init.update(critic_network.init(seed + 1))
-        tinit = dict(target_policy_network.init(seed + 2))
-        tinit.update(target_critic_network.init(seed + 3))
-        self._native.set_params(init, tinit)
-        self._counter = counter or counting.Counter()
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
-        self._timestamp = None
-        self._checkpoint = checkpoint
+        self._init_params(target_policy_network, target_critic_network, seed)
+        self._init_bookkeeping(counter, logger, checkpoint)

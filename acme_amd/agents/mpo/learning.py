@@ -24,7 +24,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from acme_amd.agents.d4pg.learning import D4PGLearner, _is_identity
+from acme_amd.agents.d4pg.learning import D4PGLearner, _learning_rate
 from acme_amd.native import NativeMPO
 from acme_amd.utils import counting, loggers
 
@@ -51,6 +51,8 @@ class MPOLearner(D4PGLearner):
     surface; the duals and their moments are entries of the same buffers); `policy` returns
     the online distribution's mean."""
 
+    _algorithm = "MPO"
+
     def __init__(self, policy_network, critic_network, target_policy_network,
                  target_critic_network, discount: float, num_samples: int,
                  target_policy_update_period: int, target_critic_update_period: int, dataset,
@@ -60,41 +62,26 @@ class MPOLearner(D4PGLearner):
                  counter: Optional[counting.Counter] = None,
                  logger: Optional[loggers.Logger] = None, checkpoint: bool = True,
                  batch_size: Optional[int] = None, seed: int = 0, device=None):
-        if not (_is_identity(observation_network) and _is_identity(target_observation_network)):
-            raise ValueError("acme_amd's MPO learner supports identity observation networks "
-                             "(flat observations) only")
-        if critic_network.obs_dim != policy_network.obs_dim or \
-                critic_network.act_dim != policy_network.act_dim:
-            raise ValueError("policy and critic disagree on observation / action sizes")
+        B = self._check_networks(policy_network, critic_network, observation_network,
+                                 target_observation_network, dataset, batch_size)
         loss = policy_loss_module or MPOLoss()
         if not isinstance(loss, MPOLoss):
             raise ValueError("policy_loss_module must be an acme_amd.agents.mpo.MPOLoss")
-        self._policy_network = policy_network
-        self._critic_network = critic_network
         self._policy_loss_module = loss
-        self._iterator = iter(dataset)
-        B = batch_size or getattr(dataset, "batch_size", None) or 256
-        lr = lambda opt, d: float(getattr(opt, "learning_rate", d)) if opt is not None else d  # noqa
         self._native = NativeMPO(
             obs_dim=policy_network.obs_dim, act_dim=policy_network.act_dim, max_batch=B,
             policy_sizes=policy_network.layer_sizes, critic_sizes=critic_network.layer_sizes,
             num_samples=num_samples, discount=discount,
             target_policy_update_period=target_policy_update_period,
             target_critic_update_period=target_critic_update_period,
-            policy_learning_rate=lr(policy_optimizer, 1e-4),
-            critic_learning_rate=lr(critic_optimizer, 1e-4),
-            dual_learning_rate=lr(dual_optimizer, 1e-2), clipping=clipping,
+            policy_learning_rate=_learning_rate(policy_optimizer),
+            critic_learning_rate=_learning_rate(critic_optimizer),
+            dual_learning_rate=_learning_rate(dual_optimizer, 1e-2), clipping=clipping,
             init_scale=policy_network.init_scale, min_scale=policy_network.min_scale,
             seed=seed, device=device, **dataclasses.asdict(loss))
-        init = dict(policy_network.init(seed))
-        init.update(critic_network.init(seed + 1))
-        tinit = dict(target_policy_network.init(seed + 2))
-        tinit.update(target_critic_network.init(seed + 3))
-        self._native.set_params(init, tinit)  # the duals keep their init_log_* values
-        self._counter = counter or counting.Counter()
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
-        self._timestamp = None
-        self._checkpoint = checkpoint
+        # The duals keep their init_log_* values.
+        self._init_params(target_policy_network, target_critic_network, seed)
+        self._init_bookkeeping(counter, logger, checkpoint)
 
     def step(self):
         sample = next(self._iterator)

@@ -18,18 +18,23 @@
 // activate_final); policy head NearZeroInitializedLinear + TanhToSpec
 // (rescaling.py:55-74); critic head DiscreteValuedHead (distributional.py:36-67).
 //
-// DDPG (acme_ddpg_*, acme/agents/tf/ddpg/learning.py:143-237) is the same learner object with
-// a scalar head: the critic is LayerNormMLP(critic_sizes + (1,)), and ddpg_head_td_kernel
-// (head forward, TD loss 0.5 (r + discount d q_t - q_tm1)^2, the head's input gradient)
-// stands where the head GEMMs, the categorical loss kernel and the head's input-gradient
-// problem stand for D4PG; everything else of the step is shared.
+// One learner core, three handle types.  acme_d4pg, acme_ddpg and acme_mpo derive from
+// acme_actor_critic, whose Head says which step it takes; the flat-buffer layout, bind, the
+// step entry (checks, graph or eager, step count), the LayerNormMLP passes, the backward
+// launches, clip_and_adam and the debug-buffer lookup are written once over that core, and
+// the exports are one-line calls into them.
 //
-// MPO (acme_mpo_*, acme/agents/tf/mpo/learning.py:145-260, acme/tf/losses/mpo.py) is a third head
-// kind of the same object: a Gaussian policy head, N actions per state sampled from the target
-// policy on the device, the scalar critic over those N B rows, the decoupled MPO loss and its
-// dual variables as a third parameter group.  Its kernels are in mpo_kernels.h, its step is
-// mpo_step_impl below; the LayerNormMLP passes, the backward launches, the clipping and Adam
-// are the shared ones.
+// DDPG (acme_ddpg_*, acme/agents/tf/ddpg/learning.py:143-237) is Head::kScalar: the critic
+// is LayerNormMLP(critic_sizes + (1,)), and ddpg_head_td_kernel (head forward, TD loss
+// 0.5 (r + discount d q_t - q_tm1)^2, the head's input gradient) stands where the head GEMMs,
+// the categorical loss kernel and the head's input-gradient problem stand for D4PG;
+// everything else of d4pg_step_impl is shared.
+//
+// MPO (acme_mpo_*, acme/agents/tf/mpo/learning.py:145-260, acme/tf/losses/mpo.py) is
+// Head::kMpo: a Gaussian policy head, N actions per state sampled from the target policy on
+// the device, the scalar critic over those N B rows, the decoupled MPO loss and its dual
+// variables as a third parameter group.  Its kernels are in mpo_kernels.h, its step is
+// mpo_step_impl below.
 //
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
@@ -49,6 +54,7 @@
 #include "gemm.h"
 #include "gemm_direct.h"
 #include "kernels.h"
+#include "learner_common.h"
 #include "profiler.h"
 
 
@@ -62,13 +68,6 @@ constexpr int kMaxWidth = 1024;
 constexpr int kMaxIn = 64;    // obs_dim + act_dim
 constexpr int kNormBlocks = 256;
 constexpr int kGraphKeys = 11;  // pointers that key a captured step graph (MPO uses all)
-
-struct Tensor {
-  std::string name;
-  int64_t offset = 0, numel = 0;
-  int ndim = 0;
-  int64_t shape[4] = {1, 1, 1, 1};
-};
 
 // Tensor indices of one LayerNormMLP + output layer.
 struct NetDesc {
@@ -89,9 +88,20 @@ struct Acts {
   float* t = nullptr;     // policy: tanh of the head [rows][act]
 };
 
+// What the critic ends in, and with it which step the learner takes.
+enum class Head {
+  kCategorical,  // D4PG: DiscreteValuedHead, categorical projection loss
+  kScalar,       // DDPG: one scalar, TD loss
+  kMpo,          // MPO: scalar critic, Gaussian policy head, the dual variables
+};
+
 }  // namespace
 
-struct acme_d4pg {
+// The learner behind the three handle types of this file (below): the LayerNormMLP policy and
+// critic in one flat buffer, their workspaces and the captured step graphs.
+struct acme_actor_critic {
+  virtual ~acme_actor_critic() = default;
+  Head head = Head::kCategorical;
   acme_d4pg_config cfg;
   std::vector<Tensor> tensors;
   int64_t flat = 0, policy_flat = 0;
@@ -115,14 +125,12 @@ struct acme_d4pg {
   float* norms = nullptr;                 // [2] global norms (policy, critic)
   float* loss_tmp = nullptr;              // [2] critic / policy loss
   float* ce = nullptr;                    // [B] per-row cross-entropy (DDPG: 0.5 td^2)
-  // DDPG (acme_ddpg_create): the critic ends in one scalar, con.out / ctg.out hold q.
-  bool scalar_head = false;
+  // Scalar heads (DDPG, MPO): the critic ends in one scalar, con.out / ctg.out hold q.
   float* td = nullptr;                    // [B] TD error
   float* dq = nullptr;                    // [2B] dloss/dq (rows < B), 1 (dpg rows)
   int64_t* dev_step = nullptr;            // device mirror of num_steps (Adam t)
   // MPO (acme_mpo_create): Gaussian policy head, N sampled actions per state, scalar critic,
   // the dual variables as a third parameter group [critic_end, flat).
-  bool mpo = false;
   acme_mpo_config mcfg;
   int64_t critic_end = 0;                 // end of the critic's floats (= flat without duals)
   int sw = -1, sb = -1;                   // the head's scale layer (pol.ow / pol.ob: its mean layer)
@@ -148,40 +156,16 @@ struct acme_d4pg {
   hipStream_t capture = nullptr;
 };
 
+// The handle types of the C ABI: each *_create allocates its own, everything else works on
+// the learner they share.
+struct acme_d4pg : acme_actor_critic {};
+struct acme_ddpg : acme_actor_critic {};
+struct acme_mpo : acme_actor_critic {};
+
 namespace {
 
-int64_t align64(int64_t x) { return (x + 63) & ~int64_t(63); }
-
-int add_tensor(acme_d4pg* l, const std::string& name, std::initializer_list<int64_t> shape) {
-  Tensor t;
-  t.name = name;
-  t.ndim = (int)shape.size();
-  t.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) {
-    t.shape[i++] = s;
-    t.numel *= s;
-  }
-  t.offset = l->flat;
-  l->flat = align64(l->flat + t.numel);
-  l->tensors.push_back(t);
-  return (int)l->tensors.size() - 1;
-}
-
-template <class T>
-int dev_alloc(acme_d4pg* l, T** p, int64_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %lld bytes failed", (long long)(count * sizeof(T)));
-    return ACME_ERR_OOM;
-  }
-  l->allocs.push_back(q);
-  *p = static_cast<T*>(q);
-  return ACME_OK;
-}
-
-void add_net(acme_d4pg* l, NetDesc& d, const char* prefix, int din, int nl, const int32_t* sizes,
-             int nout, const char* head) {
+void add_net(acme_actor_critic* l, NetDesc& d, const char* prefix, int din, int nl,
+             const int32_t* sizes, int nout, const char* head) {
   d.din = din;
   d.nl = nl;
   d.nout = nout;
@@ -204,7 +188,7 @@ void add_net(acme_d4pg* l, NetDesc& d, const char* prefix, int din, int nl, cons
   d.ob = add_tensor(l, h + "/b", {nout});
 }
 
-int alloc_acts(acme_d4pg* l, Acts& a, const NetDesc& d, int rows, bool policy) {
+int alloc_acts(acme_actor_critic* l, Acts& a, const NetDesc& d, int rows, bool policy) {
   int rc;
   if ((rc = dev_alloc(l, &a.z1, (int64_t)rows * d.sizes[0])) ||
       (rc = dev_alloc(l, &a.mean, rows)) || (rc = dev_alloc(l, &a.rstd, rows)) ||
@@ -216,23 +200,7 @@ int alloc_acts(acme_d4pg* l, Acts& a, const NetDesc& d, int rows, bool policy) {
   return ACME_OK;
 }
 
-inline const float* P(const acme_d4pg* l, const float* base, int t) {
-  return base + l->tensors[t].offset;
-}
-inline float* Pm(const acme_d4pg* l, float* base, int t) { return base + l->tensors[t].offset; }
-
 // ------------------------------------------------------------------ device helpers
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // Sums N per-thread values over a 256-thread block; every thread gets the totals.
 template <int N>
@@ -811,15 +779,6 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdArgs a) {
     }                                                                                         \
   } while (0)
 
-#define D4_CHECK()                                                                            \
-  do {                                                                                        \
-    hipError_t _e = hipGetLastError();                                                        \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-
 // Dense layer forward y = act(x @ W + b) over `rows` rows.
 int dense_fwd(const char* name, const float* x, int rows, int K, const float* w, const float* b,
               int N, int act, float* y, hipStream_t st) {
@@ -884,7 +843,7 @@ struct NetIn {
 
 // Two evaluations of one LayerNormMLP (the online and the target network) in one launch
 // per layer: the LayerNorm first layer, the ELU layers.
-int lnmlp_forward_pair(acme_d4pg* l, const NetDesc& d, const NetIn (&in)[2], int da, int db,
+int lnmlp_forward_pair(acme_actor_critic* l, const NetDesc& d, const NetIn (&in)[2], int da, int db,
                        const char* tag, hipStream_t st) {
   {
     ACME_PROF(tag, st, 2.0 * (in[0].rows + in[1].rows) * (double)(da + db) * d.sizes[0], 0.0);
@@ -908,7 +867,7 @@ int lnmlp_forward_pair(acme_d4pg* l, const NetDesc& d, const NetIn (&in)[2], int
     const int H = d.sizes[0];
     auto k = H <= 256 ? ln_first_kernel<1> : H <= 512 ? ln_first_kernel<2> : ln_first_kernel<4>;
     k<<<dim3((unsigned)ceil_div(rows, kRows), in[1].rows > 0 ? 2 : 1), 256, 0, st>>>(f);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   for (int i = 1; i < d.nl; ++i) {
     Acts &a0 = *in[0].acts, &a1 = *in[1].acts;
@@ -922,7 +881,7 @@ int lnmlp_forward_pair(acme_d4pg* l, const NetDesc& d, const NetIn (&in)[2], int
 }
 
 // Up to two policy evaluations (TanhToSpec actions into out[i]); in[1].rows = 0: one.
-int policy_forward_pair(acme_d4pg* l, const NetIn (&in)[2], float* const (&out)[2],
+int policy_forward_pair(acme_actor_critic* l, const NetIn (&in)[2], float* const (&out)[2],
                         hipStream_t st) {
   const NetDesc& d = l->pol;
   int rc = lnmlp_forward_pair(l, d, in, l->cfg.obs_dim, 0, "d4pg_policy_ln", st);
@@ -942,13 +901,13 @@ int policy_forward_pair(acme_d4pg* l, const NetIn (&in)[2], float* const (&out)[
   h.lo = l->act_lo; h.scale = l->act_scale; h.H = d.sizes[d.nl - 1]; h.A = d.nout;
   policy_head_kernel<<<dim3((unsigned)ceil_div(rows, 4), in[1].rows > 0 ? 2 : 1), 256, 0,
                        st>>>(h);
-  D4_CHECK();
+  ACME_LAUNCH_CHECK();
   return ACME_OK;
 }
 
 // The online critic (2B rows: [o_tm1, a_tm1 ; o_t, dpg actions]) and the target critic
 // (B rows: [o_t, target actions]).
-int critic_forward_pair(acme_d4pg* l, const NetIn (&in)[2], hipStream_t st) {
+int critic_forward_pair(acme_actor_critic* l, const NetIn (&in)[2], hipStream_t st) {
   const NetDesc& d = l->cri;
   int rc = lnmlp_forward_pair(l, d, in, l->cfg.obs_dim, l->cfg.act_dim, "d4pg_critic_ln", st);
   if (rc != ACME_OK) return rc;
@@ -1052,7 +1011,7 @@ int launch_multi(const char* name, hipStream_t st, const std::vector<Q>&... qs) 
     set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
     return ACME_ERR_HIP;
   }
-  D4_CHECK();
+  ACME_LAUNCH_CHECK();
   return ACME_OK;
 }
 
@@ -1071,46 +1030,14 @@ int launch_bwd(const char* name, BwdGroup& g, hipStream_t st) {
   return rc;
 }
 
-// LayerNorm scale / offset gradients of the step's LayerNorms: the block partials
-// [nblk][2][H] of ln_bwd_kernel, summed for both networks in one launch after the last
-// one (blockIdx.y = network): 16 float4 columns x 16 partial groups per block, group g
-// sums partials g, g+16, ... in order, then the groups are added in order.
+// LayerNorm scale / offset gradients of one LayerNorm: the block partials [nblk][2][H] of
+// ln_bwd_kernel, summed after the last one.
 struct LnReduce {
   const float* slab;
   int nblk, H;
   float *scale, *offset;
 };
-struct LnReducePair {
-  LnReduce r[2];
-};
-
-__global__ void __launch_bounds__(256) ln_param_reduce_kernel(const LnReducePair q) {
-  using f32x4 = gemm::f32x4;
-  const LnReduce a = q.r[blockIdx.y];
-  __shared__ f32x4 red[16][16];
-  const int c = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int count4 = a.H / 2;  // 2H floats per partial row
-  const int e = blockIdx.x * 16 + c;
-  if (blockIdx.x * 16 >= count4) return;  // block-uniform
-  const f32x4* s4 = reinterpret_cast<const f32x4*>(a.slab);
-  f32x4 acc{0.f, 0.f, 0.f, 0.f};
-  if (e < count4) {
-#pragma unroll 8
-    for (int sp = g; sp < a.nblk; sp += 16) acc += s4[(size_t)sp * count4 + e];
-  }
-  red[g][c] = acc;
-  __syncthreads();
-  if (g == 0 && e < count4) {
-    f32x4 v = red[0][c];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) v += red[k][c];
-    const int h4 = a.H / 4;
-    if (e < h4) reinterpret_cast<f32x4*>(a.scale)[e] = v;
-    else reinterpret_cast<f32x4*>(a.offset)[e - h4] = v;
-  }
-}
-
-// The same reduction as a member of the last backward launch (gemm_direct.h kCustom): a
+// The reduction as a member of the last backward launch (gemm_direct.h kCustom): a
 // 512-thread block sums 16 float4 columns over 32 partial groups (group g: partials g, g+32,
 // ...), then the groups in order.  M x N = 32 x (32 blocks) sizes the launch's grid.
 struct LnReduceBlock {
@@ -1144,25 +1071,8 @@ struct LnReduceBlock {
   }
 };
 
-int run_ln_reduces(const std::vector<LnReduce>& ln, hipStream_t st) {
-  if (ln.empty()) return ACME_OK;
-  if (ln.size() > 2) return (set_error("too many LayerNorm reductions"), ACME_ERR_INVALID);
-  LnReducePair q;
-  int cols = 0;
-  double bytes = 0.0;
-  for (size_t i = 0; i < ln.size(); ++i) {
-    q.r[i] = ln[i];
-    cols = std::max(cols, ln[i].H / 2);
-    bytes += 4.0 * (ln[i].nblk + 1) * 2.0 * ln[i].H;
-  }
-  ACME_PROF("d4pg_ln_param_reduce", st, 0.0, bytes);
-  ln_param_reduce_kernel<<<dim3((unsigned)ceil_div(cols, 16), (unsigned)ln.size()), 256, 0, st>>>(q);
-  D4_CHECK();
-  return ACME_OK;
-}
-
-// The step's last backward launch and the LayerNorm parameter reductions: one launch
-// (direct engine; the reductions read only ln_bwd's partials), else two.
+// The step's last backward launch and the LayerNorm parameter reductions in one launch of
+// the direct engine (the reductions read only ln_bwd's partials).
 int launch_bwd_last(const char* name, BwdGroup& g, const std::vector<LnReduce>& ln,
                     hipStream_t st) {
   std::vector<LnReduceBlock> lr;
@@ -1189,8 +1099,8 @@ int launch_bwd_last(const char* name, BwdGroup& g, const std::vector<LnReduce>& 
 // with that layer's weight gradient's predecessor problems.  Each layer's launch: its input
 // gradient and its weight gradient (over the first `wrows` rows).  Leaves dLoss/d(LayerNorm
 // output) in dz[0].
-int lnmlp_backward_mlp(acme_d4pg* l, const NetDesc& d, const Acts& a, float* const* dz, int rows,
-                       int wrows, BwdGroup& g, const char* tag, hipStream_t st,
+int lnmlp_backward_mlp(acme_actor_critic* l, const NetDesc& d, const Acts& a, float* const* dz,
+                       int rows, int wrows, BwdGroup& g, const char* tag, hipStream_t st,
                        bool dz_ready = false) {
   // dz_ready (DDPG: the head kernel wrote dz[nl-1]): what `g` holds rides with the first
   // layer launch instead of taking one of its own.
@@ -1207,9 +1117,9 @@ int lnmlp_backward_mlp(acme_d4pg* l, const NetDesc& d, const Acts& a, float* con
 
 // LayerNorm backward of the first layer; its weight gradient (concat inputs) joins the next
 // backward launch, its scale/offset partials the final reductions.
-int ln_backward(acme_d4pg* l, const NetDesc& d, const Acts& a, float* dy, int rows, int ce_rows,
-                bool dpg, const float* xa, const float* xb, int da, int db, float* slab,
-                BwdGroup& g, std::vector<LnReduce>& ln, hipStream_t st) {
+int ln_backward(acme_actor_critic* l, const NetDesc& d, const Acts& a, float* dy, int rows,
+                int ce_rows, bool dpg, const float* xa, const float* xb, int da, int db,
+                float* slab, BwdGroup& g, std::vector<LnReduce>& ln, hipStream_t st) {
   const int H = d.sizes[0];
   const int nblk = (int)ceil_div(rows, kRows);
   {
@@ -1228,7 +1138,7 @@ int ln_backward(acme_d4pg* l, const NetDesc& d, const Acts& a, float* dy, int ro
            : c == 2 ? (am == 4 ? ln_bwd_kernel<2, 4> : am == 8 ? ln_bwd_kernel<2, 8> : ln_bwd_kernel<2, 16>)
                     : (am == 4 ? ln_bwd_kernel<4, 4> : am == 8 ? ln_bwd_kernel<4, 8> : ln_bwd_kernel<4, 16>);
     k<<<(unsigned)nblk, 256, 0, st>>>(b);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   ln.push_back({slab, nblk, H, Pm(l, l->grads, d.scale), Pm(l, l->grads, d.offset)});
   // dW1 = concat(xa, xb)^T dz: the xa rows and the xb rows of dW1 as two weight gradients
@@ -1239,12 +1149,37 @@ int ln_backward(acme_d4pg* l, const NetDesc& d, const Acts& a, float* dy, int ro
   return ACME_OK;
 }
 
-int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outputs* out,
+// Global-norm clipping + Adam (t = steps taken including this one) of the policy and critic
+// groups in the first `floats` floats.  The policy loss is the sum of ploss[0, n_ploss) over
+// div_ploss, the critic loss the mean of ce[0, B); a null output goes to loss_tmp.
+int clip_and_adam(acme_actor_critic* l, int64_t floats, const float* ploss, int n_ploss,
+                  float div_ploss, int B, float* policy_loss, float* critic_loss,
+                  hipStream_t st) {
+  ACME_PROF("d4pg_adam", st, 0.0, 7.0 * 4.0 * (double)floats);
+  const int64_t n4 = floats / 4, pol4 = l->policy_flat / 4;
+  int rc = launch_grad_sumsq(l->grads, n4, pol4, l->norm_part, kNormBlocks, l->dev_step, st);
+  if (rc != ACME_OK) return rc;
+  ClipAdamArgs a;
+  a.p = l->params; a.m = l->m; a.v = l->v; a.g = l->grads; a.n4 = n4; a.group0_4 = pol4;
+  a.part = l->norm_part; a.nparts = kNormBlocks; a.clipping = l->cfg.clipping;
+  a.clip_norm = 40.f;
+  a.lr0 = l->cfg.policy_learning_rate; a.lr1 = l->cfg.critic_learning_rate;
+  a.b1 = l->cfg.adam_beta1; a.b2 = l->cfg.adam_beta2; a.eps = l->cfg.adam_epsilon;
+  a.dev_step = l->dev_step; a.norms = l->norms;
+  a.sum_a = ploss; a.n_a = n_ploss; a.div_a = div_ploss;
+  a.out_a = policy_loss ? policy_loss : l->loss_tmp + 1;
+  a.sum_b = l->ce; a.n_b = B; a.div_b = (float)B;
+  a.out_b = critic_loss ? critic_loss : l->loss_tmp;
+  return launch_clip_adam(a, st);
+}
+
+int d4pg_step_impl(acme_actor_critic* l, const acme_d4pg_batch* bt, const acme_d4pg_outputs* out,
                    bool copy_target, hipStream_t st) {
   const int B = (int)bt->batch;
   const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
   const NetDesc& pd = l->pol;
   const NetDesc& cd = l->cri;
+  const bool scalar = l->head == Head::kScalar;
   int rc;
   if (copy_target) {
     ACME_PROF("d4pg_target_copy", st, 0.0, 2.0 * 4.0 * (double)l->flat);
@@ -1268,7 +1203,7 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
     cin[0].head_prm = l->params;
     cin[1].head[0] = {l->ptg.h[pd.nl - 1], l->ptg.t, l->ptg.out};
     cin[1].head_prm = l->target;
-    if (l->scalar_head)
+    if (scalar)
       rc = lnmlp_forward_pair(l, cd, cin, od, ad, "d4pg_critic_ln", st);
     else
       rc = critic_forward_pair(l, cin, st);
@@ -1277,7 +1212,7 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
   BwdGroup g;
   std::vector<LnReduce> ln;
   const int cL = cd.nl - 1;
-  if (l->scalar_head) {
+  if (scalar) {
     // DDPG: head forward, TD loss and the head's input gradient in one launch; the head's
     // weight gradient (one live column) joins the first backward launch.
     ACME_PROF("ddpg_head_td", st, 2.0 * 5.0 * B * (double)cd.sizes[cL], 0.0);
@@ -1289,7 +1224,7 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
     a.q = l->con.out; a.tq = l->ctg.out; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
     a.dz = l->cdz[cL];
     ddpg_head_td_kernel<<<(unsigned)ceil_div(2 * B, 4), 256, 0, st>>>(a);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
     add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dq, 1, Pm(l, l->grads, cd.ow),
               Pm(l, l->grads, cd.ob));
   } else {
@@ -1297,18 +1232,18 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
     d4pg_loss_kernel<<<(unsigned)ceil_div(2 * B, 4), 256, 0, st>>>(
         l->con.out, l->ctg.out, bt->r_t, bt->d_t, l->values, B, cd.nout, l->cfg.discount,
         l->dlogits, l->ce);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   // Critic backward: 2B rows of input gradients (CE rows + dpg rows), weight gradients from
   // the first B.  Launch k carries layer k's input gradient and weight gradient.
-  if (!l->scalar_head) {
+  if (!scalar) {
     add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dlogits, cd.nout, Pm(l, l->grads, cd.ow),
               Pm(l, l->grads, cd.ob));
     add_dgrad(g, l->dlogits, 2 * B, cd.nout, P(l, l->params, cd.ow), cd.sizes[cL], l->con.h[cL],
               act_of_layer(cL), l->cdz[cL]);
   }
   if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, 2 * B, B, g, "d4pg_bwd_head", st,
-                               l->scalar_head)) ||
+                               scalar)) ||
       (rc = ln_backward(l, cd, l->con, l->cdz[0], 2 * B, B, true, bt->o_tm1, bt->a_tm1, od, ad,
                         l->lnslab, g, ln, st)))
     return rc;
@@ -1324,30 +1259,27 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
                         l->lnslab2, g, ln, st)) ||
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
-  // Global-norm clipping + Adam (t = steps taken including this one).
-  {
-    ACME_PROF("d4pg_adam", st, 0.0, 7.0 * 4.0 * (double)l->flat);
-    const int64_t n4 = l->flat / 4, pol4 = l->policy_flat / 4;
-    int rc2 = launch_grad_sumsq(l->grads, n4, pol4, l->norm_part, kNormBlocks, l->dev_step, st);
-    if (rc2 != ACME_OK) return rc2;
-    ClipAdamArgs a;
-    a.p = l->params; a.m = l->m; a.v = l->v; a.g = l->grads; a.n4 = n4; a.group0_4 = pol4;
-    a.part = l->norm_part; a.nparts = kNormBlocks; a.clipping = l->cfg.clipping;
-    a.clip_norm = 40.f;
-    a.lr0 = l->cfg.policy_learning_rate; a.lr1 = l->cfg.critic_learning_rate;
-    a.b1 = l->cfg.adam_beta1; a.b2 = l->cfg.adam_beta2; a.eps = l->cfg.adam_epsilon;
-    a.dev_step = l->dev_step; a.norms = l->norms;
-    a.sum_a = l->ploss_part; a.n_a = (int)ceil_div(2 * B, kRows); a.div_a = (float)B;
-    a.out_a = out && out->policy_loss ? out->policy_loss : l->loss_tmp + 1;
-    a.sum_b = l->ce; a.n_b = B; a.div_b = (float)B;
-    a.out_b = out && out->critic_loss ? out->critic_loss : l->loss_tmp;
-    rc2 = launch_clip_adam(a, st);
-    if (rc2 != ACME_OK) return rc2;
-  }
-  return ACME_OK;
+  return clip_and_adam(l, l->flat, l->ploss_part, (int)ceil_div(2 * B, kRows), (float)B, B,
+                       out ? out->policy_loss : nullptr, out ? out->critic_loss : nullptr, st);
 }
 
 // ------------------------------------------------------------------ MPO step
+// init_scale / softplus(0): what the Gaussian head multiplies its softplus by.
+float mpo_scale_mul(const acme_actor_critic* l) {
+  return (float)((double)l->mcfg.init_scale / std::log(2.0));
+}
+
+// Slot i of a gauss_head_kernel launch (`rows` rows of h, the head's two linears from `prm`)
+// and the launch's constants.
+void set_gauss_head(const acme_actor_critic* l, GaussHeadPair& p, int i, const float* prm,
+                    const float* h, int rows, float* mean, float* pre, float* sd) {
+  const NetDesc& pd = l->pol;
+  p.a[i] = {h, P(l, prm, pd.ow), P(l, prm, pd.ob), P(l, prm, l->sw), P(l, prm, l->sb), rows,
+            mean, pre, sd};
+  p.H = pd.sizes[pd.nl - 1]; p.A = l->cfg.act_dim;
+  p.scale_mul = mpo_scale_mul(l); p.min_scale = l->mcfg.min_scale;
+}
+
 // MPOLearner._step (acme/agents/tf/mpo/learning.py:145-260) on one stream:
 //   target policy / critic <- online under their own periods (at the start)      (:159-165)
 //   online and target policy on o_t, the Gaussian head of both                   (:193-194)
@@ -1359,7 +1291,7 @@ int d4pg_step_impl(acme_d4pg* l, const acme_d4pg_batch* bt, const acme_d4pg_outp
 // The policy head's input gradient is formed by the loss kernel (its two linears' weight
 // gradients ride the first policy backward launch), and the policy's backward runs before
 // the critic's so that no launch carries more than kZ weight gradients.
-int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
+int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
                   int copy, hipStream_t st) {
   const acme_mpo_config& mc = l->mcfg;
   const int B = (int)bt->batch, N = mc.num_samples, NB = N * B;
@@ -1381,22 +1313,17 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
                                 (size_t)(l->critic_end - l->policy_flat) * sizeof(float),
                                 hipMemcpyDeviceToDevice, st));
   }
-  const float scale_mul = (float)((double)mc.init_scale / std::log(2.0));
+  const float scale_mul = mpo_scale_mul(l);
   {
     const NetIn pin[2] = {{l->params, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->pon},
                           {l->target, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->ptg}};
     if ((rc = lnmlp_forward_pair(l, pd, pin, od, 0, "mpo_policy_ln", st))) return rc;
     ACME_PROF("mpo_gauss_head", st, 2.0 * 2.0 * 2.0 * B * (double)pd.sizes[pL] * ad, 0.0);
     GaussHeadPair h;
-    const float* prm[2] = {l->params, l->target};
-    Acts* acts[2] = {&l->pon, &l->ptg};
-    float* sd[2] = {mb.sd_on, mb.sd_t};
-    for (int i = 0; i < 2; ++i)
-      h.a[i] = {acts[i]->h[pL], P(l, prm[i], pd.ow), P(l, prm[i], pd.ob), P(l, prm[i], l->sw),
-                P(l, prm[i], l->sb), B, acts[i]->out, acts[i]->t, sd[i]};
-    h.H = pd.sizes[pL]; h.A = ad; h.scale_mul = scale_mul; h.min_scale = mc.min_scale;
+    set_gauss_head(l, h, 0, l->params, l->pon.h[pL], B, l->pon.out, l->pon.t, mb.sd_on);
+    set_gauss_head(l, h, 1, l->target, l->ptg.h[pL], B, l->ptg.out, l->ptg.t, mb.sd_t);
     gauss_head_kernel<<<dim3((unsigned)ceil_div(B, 4), 2), 256, 0, st>>>(h);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   {
     ACME_PROF("mpo_sample", st, 0.0, 4.0 * NB * (3.0 * ad + od + 1.0));
@@ -1406,7 +1333,7 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
     a.B = B; a.N = N; a.A = ad; a.od = od;
     a.noise = mb.noise; a.act = mb.act; a.cost = mb.cost; a.tiled = mb.tiled;
     mpo_sample_kernel<<<(unsigned)ceil_div(NB, 256), 256, 0, st>>>(a);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   {
     const NetIn cin[2] = {{l->params, bt->o_tm1, bt->a_tm1, bt->o_tm1, bt->a_tm1, B, B, &l->con},
@@ -1423,7 +1350,7 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
     a.q = l->con.out; a.sq = l->ctg.out; a.qt = mb.qt; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
     a.dz = l->cdz[cL];
     mpo_head_td_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   const int nblk = (int)ceil_div(B, 4);
   float* stats = out && out->stats ? out->stats : mb.stats;
@@ -1444,7 +1371,7 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
     a.dmean = mb.dmean; a.dpre = mb.dpre; a.dz = l->pdz[pL];
     a.w_out = mb.w; a.pw_out = mb.pw; a.part = mb.part;
     mpo_loss_kernel<<<(unsigned)nblk, 256, 0, st>>>(a);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   {
     ACME_PROF("mpo_finalize", st, 0.0, 0.0);
@@ -1461,7 +1388,7 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
     a.adam_eps = l->cfg.adam_epsilon; a.dev_step = l->dev_step;
     a.stats = stats; a.klm_rel = klm_rel; a.kls_rel = kls_rel; a.ploss = mb.ploss;
     mpo_finalize_kernel<<<1, 256, 0, st>>>(a);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   BwdGroup g;
   std::vector<LnReduce> ln;
@@ -1483,32 +1410,14 @@ int mpo_step_impl(acme_d4pg* l, const acme_mpo_batch* bt, const acme_mpo_outputs
                         l->lnslab, g, ln, st)) ||
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
-  {
-    // Global-norm clipping + Adam of the policy and critic groups; the duals' floats past
-    // critic_end are the finalize kernel's.
-    ACME_PROF("d4pg_adam", st, 0.0, 7.0 * 4.0 * (double)l->critic_end);
-    const int64_t n4 = l->critic_end / 4, pol4 = l->policy_flat / 4;
-    if ((rc = launch_grad_sumsq(l->grads, n4, pol4, l->norm_part, kNormBlocks, l->dev_step, st)))
-      return rc;
-    ClipAdamArgs a;
-    a.p = l->params; a.m = l->m; a.v = l->v; a.g = l->grads; a.n4 = n4; a.group0_4 = pol4;
-    a.part = l->norm_part; a.nparts = kNormBlocks; a.clipping = l->cfg.clipping;
-    a.clip_norm = 40.f;
-    a.lr0 = l->cfg.policy_learning_rate; a.lr1 = l->cfg.critic_learning_rate;
-    a.b1 = l->cfg.adam_beta1; a.b2 = l->cfg.adam_beta2; a.eps = l->cfg.adam_epsilon;
-    a.dev_step = l->dev_step; a.norms = l->norms;
-    a.sum_a = mb.ploss; a.n_a = 1; a.div_a = 1.f;
-    a.out_a = out && out->policy_loss ? out->policy_loss : l->loss_tmp + 1;
-    a.sum_b = l->ce; a.n_b = B; a.div_b = (float)B;
-    a.out_b = out && out->critic_loss ? out->critic_loss : l->loss_tmp;
-    if ((rc = launch_clip_adam(a, st))) return rc;
-  }
-  return ACME_OK;
+  // The duals' floats past critic_end are the finalize kernel's.
+  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, out ? out->policy_loss : nullptr,
+                       out ? out->critic_loss : nullptr, st);
 }
 
 // ------------------------------------------------------------------ step graphs
-// The ~40 launches of a step are captured once per (batch pointers, outputs, B, target
-// copy) into a hipGraph on a private capture stream and replayed with one
+// The 20 launches of a step (18 for DDPG) are captured once per (batch pointers, outputs, B,
+// target copy) into a hipGraph on a private capture stream and replayed with one
 // hipGraphLaunch on the caller's stream: the launch cost leaves the host critical path.
 // ACME_NO_GRAPH=1 disables capture; the section profiler also bypasses it (its event
 // records belong to individual launches).
@@ -1519,7 +1428,7 @@ bool graphs_enabled() {
 
 // `record(stream)` issues the step's launches; `copy` holds the target-copy flags.
 template <class F>
-int run_graph(acme_d4pg* l, const void* const (&key)[kGraphKeys], int64_t B, int copy,
+int run_graph(acme_actor_critic* l, const void* const (&key)[kGraphKeys], int64_t B, int copy,
               hipStream_t st, F&& record) {
   for (auto& g : l->graphs)
     if (g.B == B && g.copy == copy && memcmp(g.key, key, sizeof(key)) == 0) {
@@ -1550,7 +1459,7 @@ int run_graph(acme_d4pg* l, const void* const (&key)[kGraphKeys], int64_t B, int
     set_error("step graph instantiation failed: %s", hipGetErrorString(e));
     return ACME_ERR_HIP;
   }
-  acme_d4pg::Graph g;
+  acme_actor_critic::Graph g;
   memcpy(g.key, key, sizeof(key));
   g.B = B;
   g.copy = copy;
@@ -1560,11 +1469,32 @@ int run_graph(acme_d4pg* l, const void* const (&key)[kGraphKeys], int64_t B, int
   return ACME_OK;
 }
 
-}  // namespace
+// The entry of every step (l and batch non-null, l of the right head kind): the checks the
+// batch types share, then `record(stream)` replayed from the graph keyed by `key`, B and the
+// target-copy flags `copy`, or issued eagerly; a step that was issued is counted.  `api`
+// names the caller's family in the messages.
+template <class Batch, class F>
+int run_step(acme_actor_critic* l, const char* api, const Batch* batch,
+             const void* const (&key)[kGraphKeys], int copy, void* stream, F&& record) {
+  ACME_CHECK_ARG(l->params, "%s_bind must be called first", api);
+  ACME_CHECK_ARG(batch->batch >= 1 && batch->batch <= l->cfg.max_batch,
+                 "batch %lld outside [1, max_batch=%d]", (long long)batch->batch,
+                 l->cfg.max_batch);
+  ACME_CHECK_ARG(batch->o_tm1 && batch->a_tm1 && batch->r_t && batch->d_t && batch->o_t,
+                 "null batch field");
+  hipStream_t st = as_stream(stream);
+  const int rc = graphs_enabled() && !prof::enabled()
+                     ? run_graph(l, key, batch->batch, copy, st, record)
+                     : record(st);
+  if (rc != ACME_OK) return rc;
+  l->num_steps += 1;
+  return ACME_OK;
+}
 
-extern "C" {
+// ------------------------------------------------------------------ the shared learner
+// The bodies behind the acme_d4pg_*, acme_ddpg_* and acme_mpo_* exports.
 
-int acme_d4pg_destroy(acme_d4pg* l) {
+int ac_destroy(acme_actor_critic* l) {
   if (!l) return ACME_OK;
   (void)hipDeviceSynchronize();  // queued work of this learner finishes before its buffers go
   for (auto& g : l->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1574,17 +1504,12 @@ int acme_d4pg_destroy(acme_d4pg* l) {
   return ACME_OK;
 }
 
-// The learner behind acme_d4pg_create (categorical head), acme_ddpg_create (scalar head:
-// cfg->num_atoms = 1, the support unused) and acme_mpo_create (`mpo` set: scalar head, Gaussian
-// policy head, N sampled actions per state, dual variables).
-static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4pg** out,
-                          const acme_mpo_config* mpo = nullptr) {
-  ACME_CHECK_ARG(cfg && out, "null argument");
+int check_config(const acme_d4pg_config* cfg, Head head) {
   ACME_CHECK_ARG(cfg->obs_dim >= 1 && cfg->act_dim >= 1 && cfg->obs_dim + cfg->act_dim <= kMaxIn,
                  "obs_dim + act_dim must be in [2, %d]", kMaxIn);
   ACME_CHECK_ARG(cfg->act_dim <= ACME_D4PG_MAX_ACT, "act_dim must be <= %d", ACME_D4PG_MAX_ACT);
   ACME_CHECK_ARG(cfg->max_batch >= 1 && cfg->max_batch <= 65536, "max_batch must be in [1, 65536]");
-  if (!scalar_head) {
+  if (head == Head::kCategorical) {
     ACME_CHECK_ARG(cfg->num_atoms >= 2 && cfg->num_atoms <= ACME_D4PG_MAX_ATOMS,
                    "num_atoms must be in [2, %d]", ACME_D4PG_MAX_ATOMS);
     ACME_CHECK_ARG(cfg->vmax > cfg->vmin, "vmax must exceed vmin");
@@ -1601,13 +1526,15 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
     ACME_CHECK_ARG(cfg->critic_sizes[i] >= 4 && cfg->critic_sizes[i] <= kMaxWidth &&
                        cfg->critic_sizes[i] % 4 == 0,
                    "critic layer sizes must be multiples of 4 in [4, %d]", kMaxWidth);
-  acme_d4pg* l = new acme_d4pg();
+  return ACME_OK;
+}
+
+// Lays out the tensors and allocates the workspaces of a fresh learner.  Head::kScalar and
+// Head::kMpo come with cfg->num_atoms = 1 (the support unused); Head::kMpo with `mpo`.
+int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
+                 const acme_mpo_config* mpo) {
   l->cfg = *cfg;
-  l->scalar_head = scalar_head;
-  auto fail = [&](int code) {
-    acme_d4pg_destroy(l);
-    return code;
-  };
+  l->head = head;
   add_net(l, l->pol, "policy", cfg->obs_dim, cfg->num_policy_layers, cfg->policy_sizes,
           cfg->act_dim,
           mpo ? "multivariate_normal_diag_head/linear" : "near_zero_initialized_linear");
@@ -1618,10 +1545,10 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
   }
   l->policy_flat = l->flat;
   add_net(l, l->cri, "critic", cfg->obs_dim + cfg->act_dim, cfg->num_critic_layers,
-          cfg->critic_sizes, cfg->num_atoms, scalar_head ? nullptr : "discrete_valued_head/linear");
+          cfg->critic_sizes, cfg->num_atoms,
+          head == Head::kCategorical ? "discrete_valued_head/linear" : nullptr);
   l->critic_end = l->flat;
   if (mpo) {
-    l->mpo = true;
     l->mcfg = *mpo;
     const int64_t D = mpo->per_dim_constraining ? cfg->act_dim : 1;
     l->t_temp = add_tensor(l, "mpo/log_temperature", {1});
@@ -1639,7 +1566,7 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
   if ((rc = alloc_acts(l, l->pon, l->pol, B, true)) || (rc = alloc_acts(l, l->ptg, l->pol, B, true)) ||
       (rc = alloc_acts(l, l->con, l->cri, con_rows, false)) ||
       (rc = alloc_acts(l, l->ctg, l->cri, ctg_rows, false)))
-    return fail(rc);
+    return rc;
   if (mpo) {
     const int64_t A = cfg->act_dim, NB = ctg_rows;
     auto& mb = l->mb;
@@ -1652,14 +1579,14 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
         (rc = dev_alloc(l, &mb.part, ceil_div(B, 4) * kMpoCols)) ||
         (rc = dev_alloc(l, &mb.stats, ACME_MPO_NUM_STATS)) || (rc = dev_alloc(l, &mb.klm_rel, A)) ||
         (rc = dev_alloc(l, &mb.kls_rel, A)) || (rc = dev_alloc(l, &mb.ploss, 1)))
-      return fail(rc);
+      return rc;
     if (hipMemset(mb.pw, 0, (size_t)NB * sizeof(float)) != hipSuccess)
-      return fail((set_error("hipMemset failed"), ACME_ERR_HIP));
+      return (set_error("hipMemset failed"), ACME_ERR_HIP);
   }
   for (int i = 0; i < l->cri.nl; ++i)
-    if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return fail(rc);
+    if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return rc;
   for (int i = 0; i < l->pol.nl; ++i)
-    if ((rc = dev_alloc(l, &l->pdz[i], (int64_t)B * l->pol.sizes[i]))) return fail(rc);
+    if ((rc = dev_alloc(l, &l->pdz[i], (int64_t)B * l->pol.sizes[i]))) return rc;
   const int64_t nblk = ceil_div(2 * B, kRows);
   if ((rc = dev_alloc(l, &l->dlogits, (int64_t)2 * B * cfg->num_atoms)) ||
       (rc = dev_alloc(l, &l->du, (int64_t)B * cfg->act_dim)) ||
@@ -1673,9 +1600,10 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
       (rc = dev_alloc(l, &l->norm_part, 2 * kNormBlocks)) ||
       (rc = dev_alloc(l, &l->norms, 2)) || (rc = dev_alloc(l, &l->loss_tmp, 2)) ||
       (rc = dev_alloc(l, &l->ce, B)) || (rc = dev_alloc(l, &l->dev_step, 1)))
-    return fail(rc);
-  if (scalar_head && ((rc = dev_alloc(l, &l->td, B)) || (rc = dev_alloc(l, &l->dq, 2 * B))))
-    return fail(rc);
+    return rc;
+  if (head != Head::kCategorical &&
+      ((rc = dev_alloc(l, &l->td, B)) || (rc = dev_alloc(l, &l->dq, 2 * B))))
+    return rc;
   // Support: tf.linspace(vmin, vmax, K) (computed in f64, rounded once to f32).
   std::vector<float> vals(cfg->num_atoms), lo(cfg->act_dim), sc(cfg->act_dim);
   const double step = ((double)cfg->vmax - (double)cfg->vmin) / std::max(cfg->num_atoms - 1, 1);
@@ -1688,35 +1616,50 @@ static int create_learner(const acme_d4pg_config* cfg, bool scalar_head, acme_d4
       hipMemcpy(l->values, vals.data(), vals.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(l->act_lo, lo.data(), lo.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(l->act_scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-    return fail((set_error("hipMemcpy of the D4PG constants failed"), ACME_ERR_HIP));
+    return (set_error("hipMemcpy of the D4PG constants failed"), ACME_ERR_HIP);
+  return ACME_OK;
+}
+
+// A learner of handle type L (acme_d4pg, acme_ddpg, acme_mpo) with the given head kind.
+template <class L>
+int create_learner(const acme_d4pg_config* cfg, Head head, const acme_mpo_config* mpo, L** out) {
+  int rc = check_config(cfg, head);
+  if (rc != ACME_OK) return rc;
+  L* l = new L();
+  if ((rc = init_learner(l, cfg, head, mpo)) != ACME_OK) return (ac_destroy(l), rc);
   *out = l;
   return ACME_OK;
 }
 
-int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
-  return create_learner(cfg, false, out);
+// The learner configuration of a DDPG or MPO config (the shared fields carry the same
+// names): a critic that ends in one scalar, no support.
+template <class C>
+acme_d4pg_config scalar_head_config(const C* cfg, int target_update_period) {
+  acme_d4pg_config c;
+  memset(&c, 0, sizeof(c));
+  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
+  c.num_policy_layers = cfg->num_policy_layers;
+  c.num_critic_layers = cfg->num_critic_layers;
+  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
+  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
+  c.num_atoms = 1; c.vmin = 0.f; c.vmax = 0.f;
+  memcpy(c.action_min, cfg->action_min, sizeof(c.action_min));
+  memcpy(c.action_max, cfg->action_max, sizeof(c.action_max));
+  c.discount = cfg->discount; c.target_update_period = target_update_period;
+  c.policy_learning_rate = cfg->policy_learning_rate;
+  c.critic_learning_rate = cfg->critic_learning_rate;
+  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
+  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
+  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
+  return c;
 }
 
-int64_t acme_d4pg_flat_size(const acme_d4pg* l) { return l ? l->flat : 0; }
-int64_t acme_d4pg_policy_size(const acme_d4pg* l) { return l ? l->policy_flat : 0; }
-int32_t acme_d4pg_num_tensors(const acme_d4pg* l) { return l ? (int32_t)l->tensors.size() : 0; }
+int64_t ac_flat_size(const acme_actor_critic* l) { return l ? l->flat : 0; }
+int64_t ac_policy_size(const acme_actor_critic* l) { return l ? l->policy_flat : 0; }
+int32_t ac_num_tensors(const acme_actor_critic* l) { return l ? (int32_t)l->tensors.size() : 0; }
 
-int acme_d4pg_tensor_info(const acme_d4pg* l, int32_t i, int64_t* offset, int64_t* numel,
-                          int32_t* ndim, int64_t* shape4, const char** name) {
-  ACME_CHECK_ARG(l, "null learner");
-  ACME_CHECK_ARG(i >= 0 && i < (int32_t)l->tensors.size(), "tensor index %d out of range", i);
-  const Tensor& t = l->tensors[i];
-  if (offset) *offset = t.offset;
-  if (numel) *numel = t.numel;
-  if (ndim) *ndim = t.ndim;
-  if (shape4)
-    for (int k = 0; k < 4; ++k) shape4[k] = t.shape[k];
-  if (name) *name = t.name.c_str();
-  return ACME_OK;
-}
-
-int acme_d4pg_bind(acme_d4pg* l, float* params, float* target, float* grads, float* adam_m,
-                   float* adam_v) {
+int ac_bind(acme_actor_critic* l, float* params, float* target, float* grads, float* adam_m,
+            float* adam_v) {
   ACME_CHECK_ARG(l, "null learner");
   ACME_CHECK_ARG(params && target && grads && adam_m && adam_v, "null buffer");
   for (const void* p : {(const void*)params, (const void*)target, (const void*)grads,
@@ -1736,34 +1679,31 @@ int acme_d4pg_bind(acme_d4pg* l, float* params, float* target, float* grads, flo
   return ACME_OK;
 }
 
-int acme_d4pg_step(acme_d4pg* l, const acme_d4pg_batch* batch, const acme_d4pg_outputs* out,
-                   void* stream) {
-  ACME_CHECK_ARG(l && batch, "null argument");
-  ACME_CHECK_ARG(l->params, "acme_d4pg_bind must be called first");
-  ACME_CHECK_ARG(batch->batch >= 1 && batch->batch <= l->cfg.max_batch,
-                 "batch %lld outside [1, max_batch=%d]", (long long)batch->batch,
-                 l->cfg.max_batch);
-  ACME_CHECK_ARG(batch->o_tm1 && batch->a_tm1 && batch->r_t && batch->d_t && batch->o_t,
-                 "null batch field");
-  hipStream_t st = as_stream(stream);
-  const bool copy = l->num_steps % l->cfg.target_update_period == 0;
-  int rc;
-  if (graphs_enabled() && !prof::enabled()) {
-    const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
-                                   batch->o_t, out ? out->critic_loss : nullptr,
-                                   out ? out->policy_loss : nullptr};
-    rc = run_graph(l, key, batch->batch, copy ? 1 : 0, st,
-                   [&](hipStream_t s) { return d4pg_step_impl(l, batch, out, copy, s); });
-  } else {
-    rc = d4pg_step_impl(l, batch, out, copy, st);
-  }
-  if (rc != ACME_OK) return rc;
-  l->num_steps += 1;
+int64_t ac_num_steps(const acme_actor_critic* l) { return l ? l->num_steps : 0; }
+int ac_set_num_steps(acme_actor_critic* l, int64_t n) {
+  ACME_CHECK_ARG(l && n >= 0, "bad argument");
+  ACME_HIP_TRY(hipDeviceSynchronize());
+  ACME_HIP_TRY(hipMemcpy(l->dev_step, &n, sizeof(n), hipMemcpyHostToDevice));
+  l->num_steps = n;
   return ACME_OK;
 }
 
-int acme_d4pg_policy(acme_d4pg* l, const float* obs, int64_t rows, int32_t use_target,
-                     float* actions, void* stream) {
+// acme_d4pg_step and acme_ddpg_step (the batch and output types are the same).
+int d4pg_step(acme_actor_critic* l, const acme_d4pg_batch* batch, const acme_d4pg_outputs* out,
+              void* stream) {
+  ACME_CHECK_ARG(l && batch, "null argument");
+  ACME_CHECK_ARG(l->head != Head::kMpo, "an MPO learner steps through acme_mpo_step");
+  const bool copy = l->num_steps % l->cfg.target_update_period == 0;
+  const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                 batch->o_t, out ? out->critic_loss : nullptr,
+                                 out ? out->policy_loss : nullptr};
+  return run_step(l, "acme_d4pg", batch, key, copy ? 1 : 0, stream,
+                  [&](hipStream_t s) { return d4pg_step_impl(l, batch, out, copy, s); });
+}
+
+// acme_d4pg_policy and acme_ddpg_policy.
+int d4pg_policy(acme_actor_critic* l, const float* obs, int64_t rows, int32_t use_target,
+                float* actions, void* stream) {
   ACME_CHECK_ARG(l && obs && actions, "null argument");
   ACME_CHECK_ARG(l->params, "acme_d4pg_bind must be called first");
   ACME_CHECK_ARG(rows >= 0, "negative row count");
@@ -1782,128 +1722,123 @@ int acme_d4pg_policy(acme_d4pg* l, const float* obs, int64_t rows, int32_t use_t
   return ACME_OK;
 }
 
-int64_t acme_d4pg_num_steps(const acme_d4pg* l) { return l ? l->num_steps : 0; }
-int acme_d4pg_set_num_steps(acme_d4pg* l, int64_t n) {
-  ACME_CHECK_ARG(l && n >= 0, "bad argument");
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  ACME_HIP_TRY(hipMemcpy(l->dev_step, &n, sizeof(n), hipMemcpyHostToDevice));
-  l->num_steps = n;
-  return ACME_OK;
+// The workspace buffers each head kind shows to tests and diagnostics.
+int ac_debug_buffer(const acme_actor_critic* l, const char* name, const float** out,
+                    int64_t* count) {
+  ACME_CHECK_ARG(l && name && out && count, "null argument");
+  const int64_t B = l->cfg.max_batch, A = l->cfg.act_dim, K = l->cfg.num_atoms;
+  if (l->head == Head::kCategorical) {
+    const DebugItem items[] = {
+        {"p_a", l->pon.out, B * A},          {"t_a", l->ptg.out, B * A},
+        {"c_logits", l->con.out, 2 * B * K}, {"t_logits", l->ctg.out, B * K},
+        {"dlogits", l->dlogits, 2 * B * K},  {"dqda", l->dqda, B * A},
+        {"du", l->du, B * A},                {"norms", l->norms, 2},
+        {"losses", l->loss_tmp, 2},
+    };
+    return find_debug_buffer(items, name, out, count);
+  }
+  if (l->head == Head::kScalar) {
+    const DebugItem items[] = {
+        {"p_a", l->pon.out, B * A}, {"t_a", l->ptg.out, B * A},
+        {"c_q", l->con.out, 2 * B}, {"t_q", l->ctg.out, B},
+        {"td", l->td, B},           {"dq", l->dq, 2 * B},
+        {"dqda", l->dqda, B * A},   {"du", l->du, B * A},
+        {"norms", l->norms, 2},     {"losses", l->loss_tmp, 2},
+    };
+    return find_debug_buffer(items, name, out, count);
+  }
+  const int64_t NB = B * l->mcfg.num_samples;
+  const auto& mb = l->mb;
+  const DebugItem items[] = {
+      {"mean_on", l->pon.out, B * A}, {"std_on", mb.sd_on, B * A}, {"pre_on", l->pon.t, B * A},
+      {"mean_t", l->ptg.out, B * A},  {"std_t", mb.sd_t, B * A},   {"noise", mb.noise, NB * A},
+      {"actions", mb.act, NB * A},    {"cost", mb.cost, NB},       {"sampled_q", l->ctg.out, NB},
+      {"weights", mb.w, NB},          {"penalty_weights", mb.pw, NB},
+      {"q_tm1", l->con.out, B},       {"q_t", mb.qt, B},           {"td", l->td, B},
+      {"dq", l->dq, B},               {"dmean", mb.dmean, B * A},  {"dpre", mb.dpre, B * A},
+      {"norms", l->norms, 2},         {"losses", l->loss_tmp, 2},
+      {"stats", mb.stats, ACME_MPO_NUM_STATS},
+      {"kl_mean_rel", mb.klm_rel, A}, {"kl_stddev_rel", mb.kls_rel, A},
+  };
+  return find_debug_buffer(items, name, out, count);
 }
 
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ D4PG
+
+int acme_d4pg_create(const acme_d4pg_config* cfg, acme_d4pg** out) {
+  ACME_CHECK_ARG(cfg && out, "null argument");
+  return create_learner(cfg, Head::kCategorical, nullptr, out);
+}
+int acme_d4pg_destroy(acme_d4pg* l) { return ac_destroy(l); }
+int64_t acme_d4pg_flat_size(const acme_d4pg* l) { return ac_flat_size(l); }
+int64_t acme_d4pg_policy_size(const acme_d4pg* l) { return ac_policy_size(l); }
+int32_t acme_d4pg_num_tensors(const acme_d4pg* l) { return ac_num_tensors(l); }
+int acme_d4pg_tensor_info(const acme_d4pg* l, int32_t i, int64_t* offset, int64_t* numel,
+                          int32_t* ndim, int64_t* shape4, const char** name) {
+  return tensor_info<acme_actor_critic>(l, i, offset, numel, ndim, shape4, name);
+}
+int acme_d4pg_bind(acme_d4pg* l, float* params, float* target, float* grads, float* adam_m,
+                   float* adam_v) {
+  return ac_bind(l, params, target, grads, adam_m, adam_v);
+}
+int acme_d4pg_step(acme_d4pg* l, const acme_d4pg_batch* batch, const acme_d4pg_outputs* out,
+                   void* stream) {
+  return d4pg_step(l, batch, out, stream);
+}
+int acme_d4pg_policy(acme_d4pg* l, const float* obs, int64_t rows, int32_t use_target,
+                     float* actions, void* stream) {
+  return d4pg_policy(l, obs, rows, use_target, actions, stream);
+}
+int64_t acme_d4pg_num_steps(const acme_d4pg* l) { return ac_num_steps(l); }
+int acme_d4pg_set_num_steps(acme_d4pg* l, int64_t n) { return ac_set_num_steps(l, n); }
 int acme_d4pg_debug_buffer(const acme_d4pg* l, const char* name, const float** out,
                            int64_t* count) {
-  ACME_CHECK_ARG(l && name && out && count, "null argument");
-  const int B = l->cfg.max_batch, A = l->cfg.act_dim, K = l->cfg.num_atoms;
-  struct Item {
-    const char* n;
-    const float* p;
-    int64_t c;
-  };
-  if (l->scalar_head) {
-    const Item items[] = {
-        {"p_a", l->pon.out, (int64_t)B * A}, {"t_a", l->ptg.out, (int64_t)B * A},
-        {"c_q", l->con.out, (int64_t)2 * B}, {"t_q", l->ctg.out, (int64_t)B},
-        {"td", l->td, (int64_t)B},           {"dq", l->dq, (int64_t)2 * B},
-        {"dqda", l->dqda, (int64_t)B * A},   {"du", l->du, (int64_t)B * A},
-        {"norms", l->norms, 2},              {"losses", l->loss_tmp, 2},
-    };
-    for (const Item& it : items)
-      if (strcmp(it.n, name) == 0) {
-        *out = it.p;
-        *count = it.c;
-        return ACME_OK;
-      }
-    set_error("unknown debug buffer '%s'", name);
-    return ACME_ERR_INVALID;
-  }
-  const Item items[] = {
-      {"p_a", l->pon.out, (int64_t)B * A},      {"t_a", l->ptg.out, (int64_t)B * A},
-      {"c_logits", l->con.out, (int64_t)2 * B * K}, {"t_logits", l->ctg.out, (int64_t)B * K},
-      {"dlogits", l->dlogits, (int64_t)2 * B * K},  {"dqda", l->dqda, (int64_t)B * A},
-      {"du", l->du, (int64_t)B * A},             {"norms", l->norms, 2},
-      {"losses", l->loss_tmp, 2},
-  };
-  for (const Item& it : items)
-    if (strcmp(it.n, name) == 0) {
-      *out = it.p;
-      *count = it.c;
-      return ACME_OK;
-    }
-  set_error("unknown debug buffer '%s'", name);
-  return ACME_ERR_INVALID;
+  return ac_debug_buffer(l, name, out, count);
 }
 
 // ------------------------------------------------------------------ DDPG
-// The same learner object with the scalar head (DDPGLearner._step,
+// The shared learner with the scalar head (DDPGLearner._step,
 // acme/agents/tf/ddpg/learning.py:143-237).
 
 int acme_ddpg_create(const acme_ddpg_config* cfg, acme_ddpg** out) {
   ACME_CHECK_ARG(cfg && out, "null argument");
-  acme_d4pg_config c;
-  memset(&c, 0, sizeof(c));
-  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
-  c.num_policy_layers = cfg->num_policy_layers;
-  c.num_critic_layers = cfg->num_critic_layers;
-  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
-  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
-  c.num_atoms = 1; c.vmin = 0.f; c.vmax = 0.f;
-  memcpy(c.action_min, cfg->action_min, sizeof(c.action_min));
-  memcpy(c.action_max, cfg->action_max, sizeof(c.action_max));
-  c.discount = cfg->discount; c.target_update_period = cfg->target_update_period;
-  c.policy_learning_rate = cfg->policy_learning_rate;
-  c.critic_learning_rate = cfg->critic_learning_rate;
-  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
-  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
-  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
-  acme_d4pg* l = nullptr;
-  const int rc = create_learner(&c, true, &l);
-  if (rc == ACME_OK) *out = reinterpret_cast<acme_ddpg*>(l);
-  return rc;
+  const acme_d4pg_config c = scalar_head_config(cfg, cfg->target_update_period);
+  return create_learner(&c, Head::kScalar, nullptr, out);
 }
-
-static acme_d4pg* as_d4pg(acme_ddpg* l) { return reinterpret_cast<acme_d4pg*>(l); }
-static const acme_d4pg* as_cd4pg(const acme_ddpg* l) {
-  return reinterpret_cast<const acme_d4pg*>(l);
-}
-
-int acme_ddpg_destroy(acme_ddpg* l) { return acme_d4pg_destroy(as_d4pg(l)); }
-int64_t acme_ddpg_flat_size(const acme_ddpg* l) { return acme_d4pg_flat_size(as_cd4pg(l)); }
-int64_t acme_ddpg_policy_size(const acme_ddpg* l) { return acme_d4pg_policy_size(as_cd4pg(l)); }
-int32_t acme_ddpg_num_tensors(const acme_ddpg* l) { return acme_d4pg_num_tensors(as_cd4pg(l)); }
+int acme_ddpg_destroy(acme_ddpg* l) { return ac_destroy(l); }
+int64_t acme_ddpg_flat_size(const acme_ddpg* l) { return ac_flat_size(l); }
+int64_t acme_ddpg_policy_size(const acme_ddpg* l) { return ac_policy_size(l); }
+int32_t acme_ddpg_num_tensors(const acme_ddpg* l) { return ac_num_tensors(l); }
 int acme_ddpg_tensor_info(const acme_ddpg* l, int32_t i, int64_t* offset, int64_t* numel,
                           int32_t* ndim, int64_t* shape4, const char** name) {
-  return acme_d4pg_tensor_info(as_cd4pg(l), i, offset, numel, ndim, shape4, name);
+  return tensor_info<acme_actor_critic>(l, i, offset, numel, ndim, shape4, name);
 }
 int acme_ddpg_bind(acme_ddpg* l, float* params, float* target, float* grads, float* adam_m,
                    float* adam_v) {
-  return acme_d4pg_bind(as_d4pg(l), params, target, grads, adam_m, adam_v);
+  return ac_bind(l, params, target, grads, adam_m, adam_v);
 }
 int acme_ddpg_step(acme_ddpg* l, const acme_ddpg_batch* batch, const acme_ddpg_outputs* out,
                    void* stream) {
-  return acme_d4pg_step(as_d4pg(l), batch, out, stream);
+  return d4pg_step(l, batch, out, stream);
 }
 int acme_ddpg_policy(acme_ddpg* l, const float* obs, int64_t rows, int32_t use_target,
                      float* actions, void* stream) {
-  return acme_d4pg_policy(as_d4pg(l), obs, rows, use_target, actions, stream);
+  return d4pg_policy(l, obs, rows, use_target, actions, stream);
 }
-int64_t acme_ddpg_num_steps(const acme_ddpg* l) { return acme_d4pg_num_steps(as_cd4pg(l)); }
-int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n) {
-  return acme_d4pg_set_num_steps(as_d4pg(l), n);
-}
+int64_t acme_ddpg_num_steps(const acme_ddpg* l) { return ac_num_steps(l); }
+int acme_ddpg_set_num_steps(acme_ddpg* l, int64_t n) { return ac_set_num_steps(l, n); }
 int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** out,
                            int64_t* count) {
-  return acme_d4pg_debug_buffer(as_cd4pg(l), name, out, count);
+  return ac_debug_buffer(l, name, out, count);
 }
 
 // ------------------------------------------------------------------ MPO
-// The same learner object with the Gaussian policy head and the MPO loss (MPOLearner._step,
+// The shared learner with the Gaussian policy head and the MPO loss (MPOLearner._step,
 // acme/agents/tf/mpo/learning.py:145-260).
-
-static acme_d4pg* as_d4pg(acme_mpo* l) { return reinterpret_cast<acme_d4pg*>(l); }
-static const acme_d4pg* as_cd4pg(const acme_mpo* l) {
-  return reinterpret_cast<const acme_d4pg*>(l);
-}
 
 int acme_mpo_create(const acme_mpo_config* cfg, acme_mpo** out) {
   ACME_CHECK_ARG(cfg && out, "null argument");
@@ -1921,45 +1856,26 @@ int acme_mpo_create(const acme_mpo_config* cfg, acme_mpo** out) {
                  "the KL bounds (epsilon*) must be positive");
   ACME_CHECK_ARG(cfg->init_scale > 0.f && cfg->min_scale >= 0.f,
                  "init_scale must be positive and min_scale non-negative");
-  acme_d4pg_config c;
-  memset(&c, 0, sizeof(c));
-  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
-  c.num_policy_layers = cfg->num_policy_layers;
-  c.num_critic_layers = cfg->num_critic_layers;
-  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
-  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
-  c.num_atoms = 1; c.vmin = 0.f; c.vmax = 0.f;
-  memcpy(c.action_min, cfg->action_min, sizeof(c.action_min));
-  memcpy(c.action_max, cfg->action_max, sizeof(c.action_max));
-  c.discount = cfg->discount; c.target_update_period = 1;  // unused: MPO has its own two
-  c.policy_learning_rate = cfg->policy_learning_rate;
-  c.critic_learning_rate = cfg->critic_learning_rate;
-  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
-  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
-  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
-  acme_d4pg* l = nullptr;
-  const int rc = create_learner(&c, true, &l, cfg);
-  if (rc == ACME_OK) *out = reinterpret_cast<acme_mpo*>(l);
-  return rc;
+  // target_update_period is unused: MPO has its own two.
+  const acme_d4pg_config c = scalar_head_config(cfg, 1);
+  return create_learner(&c, Head::kMpo, cfg, out);
 }
-
-int acme_mpo_destroy(acme_mpo* l) { return acme_d4pg_destroy(as_d4pg(l)); }
-int64_t acme_mpo_flat_size(const acme_mpo* l) { return acme_d4pg_flat_size(as_cd4pg(l)); }
-int64_t acme_mpo_policy_size(const acme_mpo* l) { return acme_d4pg_policy_size(as_cd4pg(l)); }
-int64_t acme_mpo_dual_offset(const acme_mpo* l) { return l ? as_cd4pg(l)->critic_end : 0; }
-int32_t acme_mpo_num_tensors(const acme_mpo* l) { return acme_d4pg_num_tensors(as_cd4pg(l)); }
+int acme_mpo_destroy(acme_mpo* l) { return ac_destroy(l); }
+int64_t acme_mpo_flat_size(const acme_mpo* l) { return ac_flat_size(l); }
+int64_t acme_mpo_policy_size(const acme_mpo* l) { return ac_policy_size(l); }
+int64_t acme_mpo_dual_offset(const acme_mpo* l) { return l ? l->critic_end : 0; }
+int32_t acme_mpo_num_tensors(const acme_mpo* l) { return ac_num_tensors(l); }
 int acme_mpo_tensor_info(const acme_mpo* l, int32_t i, int64_t* offset, int64_t* numel,
                          int32_t* ndim, int64_t* shape4, const char** name) {
-  return acme_d4pg_tensor_info(as_cd4pg(l), i, offset, numel, ndim, shape4, name);
+  return tensor_info<acme_actor_critic>(l, i, offset, numel, ndim, shape4, name);
 }
 int acme_mpo_bind(acme_mpo* l, float* params, float* target, float* grads, float* adam_m,
                   float* adam_v) {
-  return acme_d4pg_bind(as_d4pg(l), params, target, grads, adam_m, adam_v);
+  return ac_bind(l, params, target, grads, adam_m, adam_v);
 }
 
-int acme_mpo_init_duals(acme_mpo* h) {
-  acme_d4pg* l = as_d4pg(h);
-  ACME_CHECK_ARG(l && l->mpo, "not an MPO learner");
+int acme_mpo_init_duals(acme_mpo* l) {
+  ACME_CHECK_ARG(l && l->head == Head::kMpo, "not an MPO learner");
   ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
   ACME_HIP_TRY(hipDeviceSynchronize());
   const acme_mpo_config& mc = l->mcfg;
@@ -1977,44 +1893,27 @@ int acme_mpo_init_duals(acme_mpo* h) {
   return ACME_OK;
 }
 
-int acme_mpo_step(acme_mpo* h, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
+int acme_mpo_step(acme_mpo* l, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
                   void* stream) {
-  acme_d4pg* l = as_d4pg(h);
   ACME_CHECK_ARG(l && batch, "null argument");
-  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
-  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
-  ACME_CHECK_ARG(batch->batch >= 1 && batch->batch <= l->cfg.max_batch,
-                 "batch %lld outside [1, max_batch=%d]", (long long)batch->batch,
-                 l->cfg.max_batch);
-  ACME_CHECK_ARG(batch->o_tm1 && batch->a_tm1 && batch->r_t && batch->d_t && batch->o_t,
-                 "null batch field");
-  hipStream_t st = as_stream(stream);
+  ACME_CHECK_ARG(l->head == Head::kMpo, "not an MPO learner");
   const int copy = (l->num_steps % l->mcfg.target_policy_update_period == 0 ? 1 : 0) |
                    (l->num_steps % l->mcfg.target_critic_update_period == 0 ? 2 : 0);
-  int rc;
-  if (graphs_enabled() && !prof::enabled()) {
-    const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
-                                   batch->o_t, batch->noise,
-                                   out ? out->critic_loss : nullptr,
-                                   out ? out->policy_loss : nullptr,
-                                   out ? out->stats : nullptr,
-                                   out ? out->kl_mean_rel : nullptr,
-                                   out ? out->kl_stddev_rel : nullptr};
-    rc = run_graph(l, key, batch->batch, copy, st,
-                   [&](hipStream_t s) { return mpo_step_impl(l, batch, out, copy, s); });
-  } else {
-    rc = mpo_step_impl(l, batch, out, copy, st);
-  }
-  if (rc != ACME_OK) return rc;
-  l->num_steps += 1;
-  return ACME_OK;
+  const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                 batch->o_t, batch->noise,
+                                 out ? out->critic_loss : nullptr,
+                                 out ? out->policy_loss : nullptr,
+                                 out ? out->stats : nullptr,
+                                 out ? out->kl_mean_rel : nullptr,
+                                 out ? out->kl_stddev_rel : nullptr};
+  return run_step(l, "acme_mpo", batch, key, copy, stream,
+                  [&](hipStream_t s) { return mpo_step_impl(l, batch, out, copy, s); });
 }
 
-int acme_mpo_policy(acme_mpo* h, const float* obs, int64_t rows, int32_t use_target,
+int acme_mpo_policy(acme_mpo* l, const float* obs, int64_t rows, int32_t use_target,
                     float* mean_out, float* stddev_out, void* stream) {
-  acme_d4pg* l = as_d4pg(h);
   ACME_CHECK_ARG(l && obs && mean_out && stddev_out, "null argument");
-  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
+  ACME_CHECK_ARG(l->head == Head::kMpo, "not an MPO learner");
   ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
   ACME_CHECK_ARG(rows >= 0, "negative row count");
   hipStream_t st = as_stream(stream);
@@ -2029,53 +1928,20 @@ int acme_mpo_policy(acme_mpo* h, const float* obs, int64_t rows, int32_t use_tar
     int rc = lnmlp_forward_pair(l, pd, in, l->cfg.obs_dim, 0, "mpo_policy_ln", st);
     if (rc != ACME_OK) return rc;
     GaussHeadPair g;
-    g.a[0] = {l->ptg.h[pd.nl - 1], P(l, prm, pd.ow), P(l, prm, pd.ob), P(l, prm, l->sw),
-              P(l, prm, l->sb), n, mean_out + r0 * A, nullptr, stddev_out + r0 * A};
+    set_gauss_head(l, g, 0, prm, l->ptg.h[pd.nl - 1], n, mean_out + r0 * A, nullptr,
+                   stddev_out + r0 * A);
     g.a[1] = g.a[0];
-    g.H = pd.sizes[pd.nl - 1]; g.A = A;
-    g.scale_mul = (float)((double)l->mcfg.init_scale / std::log(2.0));
-    g.min_scale = l->mcfg.min_scale;
     gauss_head_kernel<<<dim3((unsigned)ceil_div(n, 4), 1), 256, 0, st>>>(g);
-    D4_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   return ACME_OK;
 }
 
-int64_t acme_mpo_num_steps(const acme_mpo* l) { return acme_d4pg_num_steps(as_cd4pg(l)); }
-int acme_mpo_set_num_steps(acme_mpo* l, int64_t n) {
-  return acme_d4pg_set_num_steps(as_d4pg(l), n);
-}
-
-int acme_mpo_debug_buffer(const acme_mpo* h, const char* name, const float** out,
+int64_t acme_mpo_num_steps(const acme_mpo* l) { return ac_num_steps(l); }
+int acme_mpo_set_num_steps(acme_mpo* l, int64_t n) { return ac_set_num_steps(l, n); }
+int acme_mpo_debug_buffer(const acme_mpo* l, const char* name, const float** out,
                           int64_t* count) {
-  const acme_d4pg* l = as_cd4pg(h);
-  ACME_CHECK_ARG(l && name && out && count, "null argument");
-  ACME_CHECK_ARG(l->mpo, "not an MPO learner");
-  const int64_t B = l->cfg.max_batch, A = l->cfg.act_dim, NB = B * l->mcfg.num_samples;
-  const auto& mb = l->mb;
-  const struct {
-    const char* n;
-    const float* p;
-    int64_t c;
-  } items[] = {
-      {"mean_on", l->pon.out, B * A}, {"std_on", mb.sd_on, B * A}, {"pre_on", l->pon.t, B * A},
-      {"mean_t", l->ptg.out, B * A},  {"std_t", mb.sd_t, B * A},   {"noise", mb.noise, NB * A},
-      {"actions", mb.act, NB * A},    {"cost", mb.cost, NB},       {"sampled_q", l->ctg.out, NB},
-      {"weights", mb.w, NB},          {"penalty_weights", mb.pw, NB},
-      {"q_tm1", l->con.out, B},       {"q_t", mb.qt, B},           {"td", l->td, B},
-      {"dq", l->dq, B},               {"dmean", mb.dmean, B * A},  {"dpre", mb.dpre, B * A},
-      {"norms", l->norms, 2},         {"losses", l->loss_tmp, 2},
-      {"stats", mb.stats, ACME_MPO_NUM_STATS},
-      {"kl_mean_rel", mb.klm_rel, A}, {"kl_stddev_rel", mb.kls_rel, A},
-  };
-  for (const auto& it : items)
-    if (strcmp(it.n, name) == 0) {
-      *out = it.p;
-      *count = it.c;
-      return ACME_OK;
-    }
-  set_error("unknown debug buffer '%s'", name);
-  return ACME_ERR_INVALID;
+  return ac_debug_buffer(l, name, out, count);
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include "gemm_p3.h"
 #include "gemm_x6.h"
 #include "kernels.h"
+#include "learner_common.h"
 #include "profiler.h"
 #include "rccl_dyn.h"
 #include "torso.h"
@@ -45,13 +46,6 @@ using torso::G1;
 constexpr int kFlat = torso::kFlat;  // 7744
 constexpr int kHidden = 512;          // DuellingMLP hidden size
 constexpr int kObsBytes = 84 * 84 * 4;
-
-struct Tensor {
-  std::string name;
-  int64_t offset = 0, numel = 0;
-  int ndim = 0;
-  int64_t shape[4] = {1, 1, 1, 1};
-};
 
 struct Layer {  // dense layer of the MLP network
   int in = 0, out = 0;
@@ -187,8 +181,6 @@ struct acme_dqn {
 
 namespace {
 
-int64_t align64(int64_t x) { return (x + 63) & ~int64_t(63); }
-
 // Scale records (gemm_p3.h PScale) of the plane tensors: the transient activations and
 // gradients of one step first, then the two persistent parameter-plane buffers.
 enum {
@@ -200,33 +192,11 @@ enum {
 constexpr int64_t kParamAmaxPeriod = 8;
 constexpr int kVerdictRing = 64;  // the pinned ring of step verdicts (acme_dqn_step_verdict)
 
-int add_tensor(acme_dqn* l, const char* name, std::initializer_list<int64_t> shape) {
-  Tensor t;
-  t.name = name;
-  t.ndim = (int)shape.size();
-  t.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) {
-    t.shape[i++] = s;
-    t.numel *= s;
-  }
-  t.offset = l->flat;
-  l->flat = align64(l->flat + t.numel);
-  l->logical += t.numel;
-  l->tensors.push_back(t);
-  return (int)l->tensors.size() - 1;
-}
-
-template <class T>
-int dev_alloc(acme_dqn* l, T** p, int64_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %lld bytes failed", (long long)(count * sizeof(T)));
-    return ACME_ERR_OOM;
-  }
-  l->allocs.push_back(q);
-  *p = static_cast<T*>(q);
-  return ACME_OK;
+// The shared add_tensor, and the count of floats without the alignment padding.
+int add_tensor(acme_dqn* l, const std::string& name, std::initializer_list<int64_t> shape) {
+  const int t = acme::add_tensor<acme_dqn>(l, name, shape);
+  l->logical += l->tensors[t].numel;
+  return t;
 }
 
 int plane_alloc(acme_dqn* l, torso::Plane* x, int64_t count, int rec) {
@@ -238,10 +208,6 @@ int plane_alloc(acme_dqn* l, torso::Plane* x, int64_t count, int rec) {
   return ACME_OK;
 }
 
-inline const float* P(const acme_dqn* l, const float* base, int t) {
-  return base + l->tensors[t].offset;
-}
-inline float* Pm(const acme_dqn* l, float* base, int t) { return base + l->tensors[t].offset; }
 // Plane view of parameter tensor t in a [2][flat] parameter-plane buffer (wpl or tpl, whose
 // scale records are kScParams / kScTarget).
 inline torso::Plane WP(const acme_dqn* l, uint16_t* base, int t) {
@@ -964,15 +930,7 @@ int32_t acme_dqn_num_tensors(const acme_dqn* l) { return l ? (int32_t)l->tensors
 
 int acme_dqn_tensor_info(const acme_dqn* l, int32_t i, int64_t* offset, int64_t* numel,
                          int32_t* ndim, int64_t* shape4, const char** name) {
-  ACME_CHECK_ARG(l && i >= 0 && i < (int32_t)l->tensors.size(), "tensor index out of range");
-  const Tensor& t = l->tensors[i];
-  if (offset) *offset = t.offset;
-  if (numel) *numel = t.numel;
-  if (ndim) *ndim = t.ndim;
-  if (shape4)
-    for (int k = 0; k < 4; ++k) shape4[k] = t.shape[k];
-  if (name) *name = t.name.c_str();
-  return ACME_OK;
+  return tensor_info(l, i, offset, numel, ndim, shape4, name);
 }
 
 int acme_dqn_bind(acme_dqn* l, float* params, float* target, float* grads, float* adam_m,

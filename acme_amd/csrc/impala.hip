@@ -29,6 +29,7 @@
 #include "gemm_p3.h"
 #include "gemm_x6.h"
 #include "kernels.h"
+#include "learner_common.h"
 #include "profiler.h"
 #include "torso.h"
 #include "lstm.h"
@@ -43,13 +44,6 @@ constexpr int kNormBlocks = 256;
 constexpr int kOarSplits = 8;    // split-K of the Atari OAR projection (K = 7744 + A + 1)
 constexpr int kOarSplitsP3 = 8;  // split-K of the plane-engine OAR projection (K = 7744)
 constexpr int kP3MinRows = 64;   // learner steps of at least this many frames use the planes
-
-struct Tensor {
-  std::string name;
-  int64_t offset = 0, numel = 0;
-  int ndim = 0;
-  int64_t shape[4] = {1, 1, 1, 1};
-};
 
 }  // namespace
 
@@ -111,46 +105,11 @@ struct acme_impala {
 
 namespace {
 
-int64_t align64(int64_t x) { return (x + 63) & ~int64_t(63); }
-
 // Every record is transient (written and read within a step, rescaled at its end from the
 // step's maxima): the activations, their gradients, dgates and the parameter planes (split
 // from the f32 parameters at the start of each forward).
 enum { kScX1, kScX2, kScX3, kScDz3, kScDz2, kScDz1, kScDgates, kScParams, kScTransient,
        kScCount = kScTransient };
-
-int add_tensor(acme_impala* l, const std::string& name, std::initializer_list<int64_t> shape) {
-  Tensor t;
-  t.name = name;
-  t.ndim = (int)shape.size();
-  t.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) {
-    t.shape[i++] = s;
-    t.numel *= s;
-  }
-  t.offset = l->flat;
-  l->flat = align64(l->flat + t.numel);
-  l->tensors.push_back(t);
-  return (int)l->tensors.size() - 1;
-}
-
-template <class T>
-int dev_alloc(acme_impala* l, T** p, int64_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %lld bytes failed", (long long)(count * sizeof(T)));
-    return ACME_ERR_OOM;
-  }
-  l->allocs.push_back(q);
-  *p = static_cast<T*>(q);
-  return ACME_OK;
-}
-
-inline const float* P(const acme_impala* l, const float* base, int t) {
-  return base + l->tensors[t].offset;
-}
-inline float* Pm(const acme_impala* l, float* base, int t) { return base + l->tensors[t].offset; }
 
 // dW_h = h_prev^T dgates: h_prev of row m = b*T + t is h[m - 1] (t > 0) or h0[b] (t = 0).
 struct HPrevWgrad {
@@ -922,16 +881,7 @@ int32_t acme_impala_num_tensors(const acme_impala* l) { return l ? (int32_t)l->t
 
 int acme_impala_tensor_info(const acme_impala* l, int32_t i, int64_t* offset, int64_t* numel,
                             int32_t* ndim, int64_t* shape4, const char** name) {
-  ACME_CHECK_ARG(l, "null learner");
-  ACME_CHECK_ARG(i >= 0 && i < (int32_t)l->tensors.size(), "tensor index %d out of range", i);
-  const Tensor& t = l->tensors[i];
-  if (offset) *offset = t.offset;
-  if (numel) *numel = t.numel;
-  if (ndim) *ndim = t.ndim;
-  if (shape4)
-    for (int k = 0; k < 4; ++k) shape4[k] = t.shape[k];
-  if (name) *name = t.name.c_str();
-  return ACME_OK;
+  return tensor_info(l, i, offset, numel, ndim, shape4, name);
 }
 
 int acme_impala_bind(acme_impala* l, float* params, float* grads, float* adam_m, float* adam_v) {

@@ -17,12 +17,6 @@
 namespace acme {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
 // Duelling head epilogue: one wave per row; lane j <= A sums the split-K partials of
 // output j (fixed split order) and adds its bias; lane A holds the value.
 __global__ void __launch_bounds__(256) duel_head_finish_kernel(const float* __restrict__ slab,

@@ -20,17 +20,6 @@ constexpr int kUnits = 8;  // LSTM units per block of the backward cell kernel
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ------------------------------------------------------------------ OAR embedding loaders
 // Embedding row m = [feat[m][0:F] | one_hot(prev_a[m], A) | tanh(prev_r[m])], D = F + A + 1.
 struct Oar {

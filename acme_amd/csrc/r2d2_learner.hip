@@ -40,6 +40,7 @@
 #include "gemm_p3.h"
 #include "conv_p3.h"
 #include "kernels.h"
+#include "learner_common.h"
 #include "profiler.h"
 #include "torso.h"
 #include "lstm.h"
@@ -62,15 +63,6 @@ constexpr int kOarSplitsP3 = 2;     // split-K of the plane-engine OAR projectio
 // online passes write the same activation planes: one record each, the maximum of both),
 // then the online and the target parameter planes (split at the start of every pass).
 enum { kScX1, kScX2, kScX3, kScDz3, kScDz2, kScDz1, kScDg, kScParams, kScTParams, kScCount };
-
-struct Tensor {
-  std::string name;
-  int64_t offset = 0, numel = 0;
-  int ndim = 0;
-  int64_t shape[4] = {1, 1, 1, 1};
-};
-
-int64_t align64(int64_t x) { return (x + 63) & ~int64_t(63); }
 
 }  // namespace
 
@@ -154,39 +146,6 @@ unsigned next_lstm_tags(acme_r2d2* l, hipStream_t st) {
   }
   return l->lstm_epoch << 8;
 }
-
-int add_tensor(acme_r2d2* l, const std::string& name, std::initializer_list<int64_t> shape) {
-  Tensor t;
-  t.name = name;
-  t.ndim = (int)shape.size();
-  t.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) {
-    t.shape[i++] = s;
-    t.numel *= s;
-  }
-  t.offset = l->flat;
-  l->flat = align64(l->flat + t.numel);
-  l->tensors.push_back(t);
-  return (int)l->tensors.size() - 1;
-}
-
-template <class T>
-int dev_alloc(acme_r2d2* l, T** p, int64_t count) {
-  void* q = nullptr;
-  if (hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %lld bytes failed", (long long)(count * sizeof(T)));
-    return ACME_ERR_OOM;
-  }
-  l->allocs.push_back(q);
-  *p = static_cast<T*>(q);
-  return ACME_OK;
-}
-
-inline const float* P(const acme_r2d2* l, const float* base, int t) {
-  return base + l->tensors[t].offset;
-}
-inline float* Pm(const acme_r2d2* l, float* base, int t) { return base + l->tensors[t].offset; }
 
 bool atari(const acme_r2d2* l) { return l->cfg.torso == ACME_IMPALA_TORSO_ATARI; }
 
@@ -1088,16 +1047,7 @@ int32_t acme_r2d2_num_tensors(const acme_r2d2* l) { return l ? (int32_t)l->tenso
 
 int acme_r2d2_tensor_info(const acme_r2d2* l, int32_t i, int64_t* offset, int64_t* numel,
                           int32_t* ndim, int64_t* shape4, const char** name) {
-  ACME_CHECK_ARG(l, "null learner");
-  ACME_CHECK_ARG(i >= 0 && i < (int32_t)l->tensors.size(), "tensor index %d out of range", i);
-  const Tensor& t = l->tensors[i];
-  if (offset) *offset = t.offset;
-  if (numel) *numel = t.numel;
-  if (ndim) *ndim = t.ndim;
-  if (shape4)
-    for (int k = 0; k < 4; ++k) shape4[k] = t.shape[k];
-  if (name) *name = t.name.c_str();
-  return ACME_OK;
+  return tensor_info(l, i, offset, numel, ndim, shape4, name);
 }
 
 int acme_r2d2_bind(acme_r2d2* l, float* params, float* target, float* grads, float* adam_m,

@@ -310,6 +310,28 @@ def _memcpy_htod(dst: int, host: np.ndarray) -> None:
         _hip_memcpy(dst, a.ctypes.data, a.nbytes, 1)
 
 
+def _read_tensor_table(num_fn, info_fn, handle) -> List[Tuple[str, int, Tuple[int, ...]]]:
+    """(name, offset, shape) of every tensor of a learner's flat buffer, in buffer order."""
+    tensors = []
+    for i in range(num_fn(handle)):
+        off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        shape = (ctypes.c_int64 * 4)()
+        name = ctypes.c_char_p()
+        check(info_fn(handle, i, ctypes.byref(off), ctypes.byref(numel), ctypes.byref(nd), shape,
+                      ctypes.byref(name)))
+        tensors.append((name.value.decode(), int(off.value),
+                        tuple(int(shape[k]) for k in range(nd.value))))
+    return tensors
+
+
+def _debug_buffer(fn, handle, name: str, device) -> np.ndarray:
+    """A host copy of the learner workspace buffer `name` (float32 words)."""
+    p, n = ctypes.c_void_p(), ctypes.c_int64()
+    check(fn(handle, name.encode(), ctypes.byref(p), ctypes.byref(n)))
+    return _device_array(p.value, n.value, np.float32, device).cpu().numpy().view(
+        np.float32).copy()
+
+
 NET_NATURE = 0
 NET_MLP = 1
 OBS_U8 = 0
@@ -364,15 +386,7 @@ class NativeDQN:
         L = lib()
         self.flat_size = int(L.acme_dqn_flat_size(h))
         self.num_params = int(L.acme_dqn_num_params(h))
-        self.tensors: List[Tuple[str, int, Tuple[int, ...]]] = []
-        for i in range(L.acme_dqn_num_tensors(h)):
-            off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-            shape = (ctypes.c_int64 * 4)()
-            name = ctypes.c_char_p()
-            check(L.acme_dqn_tensor_info(h, i, ctypes.byref(off), ctypes.byref(numel),
-                                         ctypes.byref(nd), shape, ctypes.byref(name)))
-            self.tensors.append((name.value.decode(), int(off.value),
-                                 tuple(int(shape[k]) for k in range(nd.value))))
+        self.tensors = _read_tensor_table(L.acme_dqn_num_tensors, L.acme_dqn_tensor_info, h)
         d = self.device
         z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=d)  # noqa: E731
         self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
@@ -501,11 +515,7 @@ class NativeDQN:
         check(lib().acme_dqn_set_num_steps(self._h, int(n)))
 
     def debug_buffer(self, name: str) -> np.ndarray:
-        p, n = ctypes.c_void_p(), ctypes.c_int64()
-        check(lib().acme_dqn_debug_buffer(self._h, name.encode(), ctypes.byref(p),
-                                          ctypes.byref(n)))
-        return _device_array(p.value, n.value, np.float32, self.device).cpu().numpy().view(
-            np.float32).copy()
+        return _debug_buffer(lib().acme_dqn_debug_buffer, self._h, name, self.device)
 
     # --------------------------------------------------------------- step
     def _batch(self, o_tm1, a_tm1, r_t, d_t, o_t, probabilities, global_min_probability=None,
@@ -660,11 +670,12 @@ def nccl_comm_destroy(comm: int) -> None:
 
 
 class _NativeActorCritic:
-    """The deterministic-policy-gradient learner handle shared by NativeD4PG and NativeDDPG:
-    flat buffers (policy tensors first, then critic tensors), step, policy.  Subclasses name
-    the C ABI prefix and the config struct, and fill the fields only they have."""
+    """The actor-critic learner handle shared by NativeD4PG, NativeDDPG and NativeMPO: flat
+    buffers (policy tensors first, then critic tensors), batch validation, step, policy.
+    Subclasses name the C ABI prefix and the config struct, and fill the fields only they
+    have; NativeMPO has a step and a policy of its own."""
 
-    _prefix = ""     # "acme_d4pg" / "acme_ddpg"
+    _prefix = ""     # "acme_d4pg" / "acme_ddpg" / "acme_mpo"
     _tag = ""        # error-message tag
     _config = None   # ctypes config struct
 
@@ -713,15 +724,7 @@ class _NativeActorCritic:
         self._h = h
         self.flat_size = int(self._fn("flat_size")(h))
         self.policy_size = int(self._fn("policy_size")(h))
-        self.tensors: List[Tuple[str, int, Tuple[int, ...]]] = []
-        for i in range(self._fn("num_tensors")(h)):
-            off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-            shape = (ctypes.c_int64 * 4)()
-            name = ctypes.c_char_p()
-            check(self._fn("tensor_info")(h, i, ctypes.byref(off), ctypes.byref(numel),
-                                          ctypes.byref(nd), shape, ctypes.byref(name)))
-            self.tensors.append((name.value.decode(), int(off.value),
-                                 tuple(int(shape[k]) for k in range(nd.value))))
+        self.tensors = _read_tensor_table(self._fn("num_tensors"), self._fn("tensor_info"), h)
         d = self.device
         z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=d)  # noqa: E731
         self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
@@ -755,13 +758,10 @@ class _NativeActorCritic:
         check(self._fn("set_num_steps")(self._h, int(n)))
 
     def debug_buffer(self, name: str) -> np.ndarray:
-        p, n = ctypes.c_void_p(), ctypes.c_int64()
-        check(self._fn("debug_buffer")(self._h, name.encode(), ctypes.byref(p),
-                                           ctypes.byref(n)))
-        return _device_array(p.value, n.value, np.float32, self.device).cpu().numpy().view(
-            np.float32).copy()
+        return _debug_buffer(self._fn("debug_buffer"), self._h, name, self.device)
 
-    def step(self, o_tm1, a_tm1, r_t, d_t, o_t, stream=None):
+    def _check_batch(self, o_tm1, a_tm1, r_t, d_t, o_t) -> int:
+        """Validates the transition tensors every step takes; returns the batch size."""
         B = int(r_t.shape[0])
         for name, t, cols in (("o_tm1", o_tm1, self.obs_dim), ("a_tm1", a_tm1, self.act_dim),
                               ("r_t", r_t, None), ("d_t", d_t, None), ("o_t", o_t, self.obs_dim)):
@@ -770,6 +770,10 @@ class _NativeActorCritic:
                 raise ValueError(f"{name} must be a contiguous float32 device tensor")
             if t.shape[0] != B or (cols is not None and t.numel() != B * cols):
                 raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {cols}]")
+        return B
+
+    def step(self, o_tm1, a_tm1, r_t, d_t, o_t, stream=None):
+        B = self._check_batch(o_tm1, a_tm1, r_t, d_t, o_t)
         b = _lib.D4PGBatch()
         b.o_tm1, b.a_tm1, b.r_t, b.d_t, b.o_t = (ptr(o_tm1), ptr(a_tm1), ptr(r_t), ptr(d_t),
                                                  ptr(o_t))
@@ -910,15 +914,7 @@ class NativeMPO(_NativeActorCritic):
     def step(self, o_tm1, a_tm1, r_t, d_t, o_t, noise=None, stream=None):
         """One learner step.  `noise`: eps [num_samples, B, act_dim] to sample the target
         policy's actions with (tests); None: generated on the device from (seed, step)."""
-        B = int(r_t.shape[0])
-        checks = [("o_tm1", o_tm1, self.obs_dim), ("a_tm1", a_tm1, self.act_dim),
-                  ("r_t", r_t, None), ("d_t", d_t, None), ("o_t", o_t, self.obs_dim)]
-        for name, t, cols in checks:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
-                    and t.dtype == torch.float32):
-                raise ValueError(f"{name} must be a contiguous float32 device tensor")
-            if t.shape[0] != B or (cols is not None and t.numel() != B * cols):
-                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {cols}]")
+        B = self._check_batch(o_tm1, a_tm1, r_t, d_t, o_t)
         b = _lib.MPOBatch()
         b.o_tm1, b.a_tm1, b.r_t, b.d_t, b.o_t = (ptr(o_tm1), ptr(a_tm1), ptr(r_t), ptr(d_t),
                                                  ptr(o_t))
@@ -995,15 +991,7 @@ class NativeIMPALA:
             check(L.acme_impala_create(ctypes.byref(cfg), ctypes.byref(h)), "impala create")
         self._h = h
         self.flat_size = int(L.acme_impala_flat_size(h))
-        self.tensors: List[Tuple[str, int, Tuple[int, ...]]] = []
-        for i in range(L.acme_impala_num_tensors(h)):
-            off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-            shape = (ctypes.c_int64 * 4)()
-            name = ctypes.c_char_p()
-            check(L.acme_impala_tensor_info(h, i, ctypes.byref(off), ctypes.byref(numel),
-                                            ctypes.byref(nd), shape, ctypes.byref(name)))
-            self.tensors.append((name.value.decode(), int(off.value),
-                                 tuple(int(shape[k]) for k in range(nd.value))))
+        self.tensors = _read_tensor_table(L.acme_impala_num_tensors, L.acme_impala_tensor_info, h)
         z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)  # noqa
         if shared_params is not None:
             if shared_params.numel() != self.flat_size or not shared_params.is_cuda:
@@ -1046,11 +1034,7 @@ class NativeIMPALA:
         check(lib().acme_impala_set_num_steps(self._h, int(n)))
 
     def debug_buffer(self, name: str) -> np.ndarray:
-        p, n = ctypes.c_void_p(), ctypes.c_int64()
-        check(lib().acme_impala_debug_buffer(self._h, name.encode(), ctypes.byref(p),
-                                             ctypes.byref(n)))
-        return _device_array(p.value, n.value, np.float32, self.device).cpu().numpy().view(
-            np.float32).copy()
+        return _debug_buffer(lib().acme_impala_debug_buffer, self._h, name, self.device)
 
     def plane_overflow(self, reset: bool = False) -> bool:
         """As NativeDQN.plane_overflow, for the Atari torso's plane path."""
@@ -1192,15 +1176,7 @@ class NativeR2D2:
             check(L.acme_r2d2_create(ctypes.byref(cfg), ctypes.byref(h)), "r2d2 create")
         self._h = h
         self.flat_size = int(L.acme_r2d2_flat_size(h))
-        self.tensors: List[Tuple[str, int, Tuple[int, ...]]] = []
-        for i in range(L.acme_r2d2_num_tensors(h)):
-            off, numel, nd = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
-            shape = (ctypes.c_int64 * 4)()
-            name = ctypes.c_char_p()
-            check(L.acme_r2d2_tensor_info(h, i, ctypes.byref(off), ctypes.byref(numel),
-                                          ctypes.byref(nd), shape, ctypes.byref(name)))
-            self.tensors.append((name.value.decode(), int(off.value),
-                                 tuple(int(shape[k]) for k in range(nd.value))))
+        self.tensors = _read_tensor_table(L.acme_r2d2_num_tensors, L.acme_r2d2_tensor_info, h)
         z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)  # noqa
         self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
         check(L.acme_r2d2_bind(h, ptr(self.params), ptr(self.target), ptr(self.grads),
@@ -1289,11 +1265,7 @@ class NativeR2D2:
         check(lib().acme_r2d2_set_lstm_unroll(self._h, 1 if per_step else 0), "r2d2 lstm unroll")
 
     def debug_buffer(self, name: str) -> np.ndarray:
-        p, n = ctypes.c_void_p(), ctypes.c_int64()
-        check(lib().acme_r2d2_debug_buffer(self._h, name.encode(), ctypes.byref(p),
-                                           ctypes.byref(n)))
-        return _device_array(p.value, n.value, np.float32, self.device).cpu().numpy().view(
-            np.float32).copy()
+        return _debug_buffer(lib().acme_r2d2_debug_buffer, self._h, name, self.device)
 
     def step(self, observation, prev_action, prev_reward, action, reward, discount,
              probabilities, h0=None, c0=None, stream=None):

@@ -637,8 +637,9 @@ int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** o
  * loss (acme/tf/losses/mpo.py:145-430): policy = LayerNormMLP(policy_sizes, activate_final) ->
  * MultivariateNormalDiagHead(act_dim) (acme/tf/networks/distributional.py:70-129; tanh_mean,
  * fixed_scale and use_tfd_independent off), critic = DDPG's scalar LayerNormMLP(critic_sizes +
- * (1,)), identity observation network.  The same native learner object as D4PG and DDPG with a
- * third head kind; the size limits are ACME_D4PG_MAX_LAYERS / ACME_D4PG_MAX_ACT.
+ * (1,)), identity observation network.  One learner core serves D4PG, DDPG and MPO (a step
+ * export returns ACME_ERR_INVALID for a handle of another kind); the size limits are
+ * ACME_D4PG_MAX_LAYERS / ACME_D4PG_MAX_ACT.
  *
  * Flat buffers: policy tensors (the head's mean layer "policy/multivariate_normal_diag_head/
  * linear/{w,b}", then its scale layer ".../linear_1/{w,b}"), critic tensors, then the dual
