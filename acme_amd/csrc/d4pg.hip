@@ -54,6 +54,7 @@
 #include "gemm.h"
 #include "gemm_direct.h"
 #include "kernels.h"
+#include "launch.h"
 #include "learner_common.h"
 #include "profiler.h"
 
@@ -769,15 +770,6 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdArgs a) {
 // load burst per wave; round 5: 0.196 -> 0.164 ms per step against the staged f32 engine of
 // gemm.h, profiles/r05/ab/d4pg_direct_*.log).
 #define D4_LAUNCH(prob, nz) gemm::launch_direct(prob, nz, (prob).K, st)
-#define D4_GEMM(name, prob)                                                                   \
-  do {                                                                                        \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, 157.3);       \
-    hipError_t _e = D4_LAUNCH(prob, 1);                                                       \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
 
 // Dense layer forward y = act(x @ W + b) over `rows` rows.
 int dense_fwd(const char* name, const float* x, int rows, int K, const float* w, const float* b,
@@ -787,13 +779,13 @@ int dense_fwd(const char* name, const float* x, int rows, int K, const float* w,
     p.M = rows; p.N = N; p.K = K; p.k_chunk = K;
     p.x = x; p.x2 = x; p.split_b = rows; p.ldx = K;
     p.w = w; p.bias = b; p.y = y; p.act = act; p.slab = nullptr;
-    D4_GEMM(name, p);
+    ACME_DIRECT_GEMM(name, p);
   } else {
     DenseFwd<false> p;
     p.M = rows; p.N = N; p.K = K; p.k_chunk = K;
     p.x = x; p.x2 = x; p.split_b = rows; p.ldx = K;
     p.w = w; p.bias = b; p.y = y; p.act = act; p.slab = nullptr;
-    D4_GEMM(name, p);
+    ACME_DIRECT_GEMM(name, p);
   }
   return ACME_OK;
 }

@@ -30,7 +30,9 @@
 #include "gemm_p3.h"
 #include "gemm_x6.h"
 #include "kernels.h"
+#include "launch.h"
 #include "learner_common.h"
+#include "plane_guard.h"
 #include "profiler.h"
 #include "rccl_dyn.h"
 #include "torso.h"
@@ -55,7 +57,7 @@ struct Layer {  // dense layer of the MLP network
 
 }  // namespace
 
-struct acme_dqn {
+struct acme_dqn : PlaneGuard {
   acme_dqn_config cfg;
   std::vector<Tensor> tensors;
   int64_t flat = 0, logical = 0;
@@ -87,10 +89,7 @@ struct acme_dqn {
   bool planes_stale = true;  // parameter planes need a refresh from the f32 buffers
   bool last_p3 = false;      // the last forward/backward ran the plane path
   uint16_t *wpl = nullptr, *tpl = nullptr;
-  // Scale records of the plane tensors (kScale* below) and the sticky overflow flag.
-  gemm::PScale* scales = nullptr;
-  int* overflow = nullptr;
-  bool scales_ok = false;    // the activation / gradient scales are calibrated
+  // (PlaneGuard: the scale records of the plane tensors, kSc* below.)
   bool calibrating = false;
   int64_t fwd_batch = 0;  // rows of the last stage-2 forward awaiting its stage 3
   uint16_t* frames = nullptr;  // f16 copies of [o_tm1; o_t] (2B frames)
@@ -159,9 +158,8 @@ struct acme_dqn {
   // Step guard (kernels.h StepGuard): the skip-on-overflow rule of the plane engine, Adam's
   // device step count (applied updates) on every path.  seq counts the steps issued (the
   // target forward's flag slot is seq & 1); host_skipped is a pinned mirror of the skipped
-  // count the end-of-step rescale writes (read by the host without a synchronisation).
-  StepGuard* guard = nullptr;
-  int64_t* host_skipped = nullptr;
+  // count the end-of-step rescale writes (read by the host without a synchronisation): both
+  // in PlaneGuard.
   int64_t seq = 0;
   // Step verdicts (re-issue of skipped steps, DQNLearner): every step's rescale publishes
   // (verdict_seq << 1) | skip into the pinned ring host_verdicts[verdict_seq & 63], read by
@@ -199,24 +197,11 @@ int add_tensor(acme_dqn* l, const std::string& name, std::initializer_list<int64
   return t;
 }
 
-int plane_alloc(acme_dqn* l, torso::Plane* x, int64_t count, int rec) {
-  const int64_t stride = align64(count);
-  uint16_t* p = nullptr;
-  int rc = dev_alloc(l, &p, gemm::kPlanes * stride);
-  if (rc != ACME_OK) return rc;
-  *x = torso::Plane{p, stride, l->scales + rec};
-  return ACME_OK;
-}
-
 // Plane view of parameter tensor t in a [2][flat] parameter-plane buffer (wpl or tpl, whose
 // scale records are kScParams / kScTarget).
 inline torso::Plane WP(const acme_dqn* l, uint16_t* base, int t) {
   return torso::Plane{base + l->tensors[t].offset, l->flat,
                       l->scales + (base == l->tpl ? kScTarget : kScParams)};
-}
-inline CPlanes CP(const torso::Plane& x) { return CPlanes{x.p, x.stride, x.sc}; }
-inline gemm::PlaneSrc SRC(const torso::Plane& x, int64_t elems) {
-  return gemm::PlaneSrc{x.p, x.stride, (int32_t)(2 * elems), x.sc};
 }
 // f16 frames of obs_a (rows [0, split)) and obs_b (the rest) into l->frames.
 int convert_frames(acme_dqn* l, const void* obs_a, const void* obs_b, int split, int rows,
@@ -225,7 +210,6 @@ int convert_frames(acme_dqn* l, const void* obs_a, const void* obs_b, int split,
   return launch_frames_f16(static_cast<const uint8_t*>(obs_a), static_cast<const uint8_t*>(obs_b),
                            split, rows, kObsBytes, l->frames, st);
 }
-inline Planes PP(const torso::Plane& x) { return Planes{x.p, x.stride, x.sc}; }
 bool use_p3(const acme_dqn* l) { return l->p3_capable && gemm::use_x6(); }
 // The gate of the step in flight (seq): its online records' flags, its target forward's, and
 // with data parallelism every rank's (the all-reduced padding word).
@@ -236,83 +220,9 @@ Gate step_gate(const acme_dqn* l) {
   if (l->dp_gate) q.dp = l->grads + l->dp_gate_index;
   return q;
 }
-// Clears the guard's flags (not its counts) after a calibration.
-int clear_guard_flags(acme_dqn* l, hipStream_t st) {
-  ACME_HIP_TRY(hipMemsetAsync(l->guard, 0, offsetof(StepGuard, applied), st));
-  return ACME_OK;
-}
 // The side stream is used unless the section profiler is on: profiled passes run every
 // kernel alone on one stream, so their per-kernel durations are uncontended.
 hipStream_t side_stream(const acme_dqn* l) { return prof::enabled() ? nullptr : l->side; }
-
-// Split-K helper: chunk size (multiple of BK) for `splits` splits of K.
-inline int chunk_for(int K, int splits) {
-  int c = (int)ceil_div(K, splits);
-  return (int)ceil_div(c, 32) * 32;
-}
-
-#define ACME_GEMM(BM, BN, WM, WN, prob, splits)                                      \
-  do {                                                                               \
-    hipError_t _e = gemm::launch_matmul<BM, BN, WM, WN>(prob, splits, st);          \
-    if (_e != hipSuccess) {                                                          \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                           \
-    }                                                                                \
-  } while (0)
-// Profiled launch: `flops` = algorithmic FLOPs of the launch (2 * useful MACs).
-#define ACME_GEMM_F(name, flops, BM, BN, WM, WN, prob, splits) \
-  do {                                                          \
-    ACME_PROF_PEAK(name, st, (double)(flops), 0.0,              \
-                   (gemm::matmul_peak_tflops<1, decltype(prob)>())); \
-    ACME_GEMM(BM, BN, WM, WN, prob, splits);                    \
-  } while (0)
-#define ACME_GEMM_N(name, BM, BN, WM, WN, prob, splits) \
-  ACME_GEMM_F(name, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, BM, BN, WM, WN, prob, splits)
-
-// Same with an explicit reduction stage depth BK (16 or 32).
-#define ACME_GEMM_NK(name, BM, BN, WM, WN, BKV, prob, splits)                                 \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   (gemm::matmul_peak_tflops<1, decltype(prob)>()));                             \
-    hipError_t _e = gemm::launch_matmul<BM, BN, WM, WN, BKV>(prob, splits, st);               \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-#define ACME_P3_GEMM(name, BM, BN, WM, WN, BKV, prob, splits)                                \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                    \
-    hipError_t _e = gemm::launch_gemm_p3<BM, BN, WM, WN, BKV>(prob, splits, st);              \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-// Warp-specialised plane GEMM (gemm_p3ws_kernel: producer and consumer waves).
-#define ACME_P3WS_GEMM(name, BM, BN, WM, WN, BKV, prob, splits, PIPE)                        \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                    \
-    hipError_t _e = gemm::launch_gemm_p3ws<BM, BN, WM, WN, BKV, PIPE>(prob, splits, st);      \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-#define ACME_P3G_GEMM(name, BM, BN, WM, WN, BKV, ST, prob, splits)                            \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                    \
-    hipError_t _e = gemm::launch_gemm_p3g<BM, BN, WM, WN, BKV, ST>(prob, splits, st);         \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
 
 // Split counts (K-splits) of the launches whose natural grid is too small to fill 256 CUs.
 constexpr int kFcFwdSplits = 8;  // [rows, 1024] x K 7744: 128x128 tiles: 8x8x8 = 512 blocks (online)
@@ -360,7 +270,7 @@ int head_forward(acme_dqn* l, const float* prm, int rows, const float* hid, floa
   p.M = rows; p.N = A + 1; p.K = 2 * kHidden; p.k_chunk = chunk_for(p.K, kHeadFwdSplits);
   p.H = kHidden; p.A = A; p.h = hid; p.wv = P(l, prm, l->t_vw); p.wa = P(l, prm, l->t_aw);
   p.slab = l->slab;
-  ACME_GEMM_N("head_fwd", 64, 32, 2, 1, p, kHeadFwdSplits);
+  ACME_GEMM("head_fwd", 64, 32, 2, 1, 16, 1, p, kHeadFwdSplits);
   ACME_PROF("head_fwd_finish", st, 0.0, 0.0);
   return launch_duel_head_finish(l->slab, kHeadFwdSplits, rows, A, P(l, prm, l->t_vb),
                                  P(l, prm, l->t_ab), q, st);
@@ -382,7 +292,7 @@ int nature_forward(acme_dqn* l, const float* prm, const void* obs_a, const void*
     p.x = x3; p.x2 = x3; p.split_b = rows; p.ldx = kFlat;
     p.w = P(l, prm, l->t_fcw); p.bias = P(l, prm, l->t_fcb); p.y = hid; p.act = ACT_RELU;
     p.slab = l->slab;
-    ACME_GEMM_NK("fc_fwd", 128, 128, 2, 2, 32, p, splits);
+    ACME_GEMM("fc_fwd", 128, 128, 2, 2, 32, 1, p, splits);
     const int64_t cnt = (int64_t)rows * 2 * kHidden;
     int rc = slab_reduce(l->slab, splits, cnt, hid, cnt, nullptr, P(l, prm, l->t_fcb),
                          2 * kHidden, 1, "fc_fwd_reduce", st);
@@ -431,11 +341,11 @@ int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso:
     // (The target launch is its own profiler section: bench.py reports both launches as
     // fc_fwd and each one apart.)
     if (ttall && l->single_role) ACME_P3_GEMM("fc_fwd_target", 256, 128, 2, 2, 32, p, splits);  // tests
-    else if (ttall) ACME_P3WS_GEMM("fc_fwd_target", 256, 128, 2, 2, 32, p, splits, true);
+    else if (ttall) ACME_P3WS_GEMM("fc_fwd_target", 256, 128, 2, 2, 32, p, splits);
     else if (tall && l->single_role) ACME_P3_GEMM("fc_fwd", 256, 128, 2, 2, 32, p, splits);  // tests
-    else if (tall) ACME_P3WS_GEMM("fc_fwd", 256, 128, 2, 2, 32, p, splits, true);
+    else if (tall) ACME_P3WS_GEMM("fc_fwd", 256, 128, 2, 2, 32, p, splits);
     else if (l->single_role) ACME_P3_GEMM("fc_fwd", 128, 128, 2, 2, 32, p, splits);  // tests
-    else ACME_P3WS_GEMM("fc_fwd", 128, 128, 2, 2, 32, p, splits, true);
+    else ACME_P3WS_GEMM("fc_fwd", 128, 128, 2, 2, 32, p, splits);
     // The online forward of a step: the head runs inside the loss launch (nature_backward).
     if (defer_head &&
         dqn_head_loss_dz_fusable(kHidden, l->cfg.num_actions, splits, P(l, prm, l->t_vw),
@@ -462,14 +372,14 @@ int mlp_layer(acme_dqn* l, const float* prm, const Layer& L, const void* a, cons
     p.x = static_cast<const typename In::T*>(a); p.x2 = static_cast<const typename In::T*>(b);
     p.split_b = split; p.ldx = L.in; p.w = P(l, prm, L.w); p.bias = P(l, prm, L.b); p.y = y;
     p.act = L.relu ? ACT_RELU : ACT_NONE;
-    ACME_GEMM_N("mlp_fwd", 64, 64, 2, 2, p, 1);
+    ACME_GEMM("mlp_fwd", 64, 64, 2, 2, 16, 1, p, 1);
   } else {
     DenseFwd<false, In> p;
     p.M = rows; p.N = L.out; p.K = L.in; p.k_chunk = L.in;
     p.x = static_cast<const typename In::T*>(a); p.x2 = static_cast<const typename In::T*>(b);
     p.split_b = split; p.ldx = L.in; p.w = P(l, prm, L.w); p.bias = P(l, prm, L.b); p.y = y;
     p.act = L.relu ? ACT_RELU : ACT_NONE;
-    ACME_GEMM_N("mlp_fwd", 64, 64, 2, 2, p, 1);
+    ACME_GEMM("mlp_fwd", 64, 64, 2, 2, 16, 1, p, 1);
   }
   return ACME_OK;
 }
@@ -598,7 +508,7 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
     DuelHeadWgrad p;
     p.M = 2 * kHidden; p.N = A + 1; p.K = B; p.k_chunk = chunk_for(B, kHeadBwdSplits);
     p.A = A; p.h = l->hid; p.g = l->g; p.act = l->a_cache; p.slab = hslab;
-    ACME_GEMM_N("head_wgrad", 64, 32, 2, 1, p, kHeadBwdSplits);
+    ACME_GEMM("head_wgrad", 64, 32, 2, 1, 16, 1, p, kHeadBwdSplits);
     ACME_PROF("head_wgrad_scatter", st, 0.0, 0.0);
     rc = launch_duel_head_grad_scatter(
         hslab, kHeadBwdSplits, kHidden, A, Pm(l, gr, l->t_vw), Pm(l, gr, l->t_vb),
@@ -631,7 +541,7 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
       // Producer / consumer waves (gemm_p3ws_kernel): 51.4 -> 47.3 us against the LDS-DMA
       // ring, the same bits.
       if (l->single_role) ACME_P3G_GEMM("fc_dgrad", 128, 128, 2, 2, 32, 3, p, 1);  // tests
-      else ACME_P3WS_GEMM("fc_dgrad", 128, 128, 2, 2, 32, p, 1, true);
+      else ACME_P3WS_GEMM("fc_dgrad", 128, 128, 2, 2, 32, p, 1);
     }
     if (fork && join_dense) ACME_HIP_TRY(hipStreamWaitEvent(st_main, l->ev[3], 0));
     l->dense_on_side = fork;
@@ -642,13 +552,13 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
     p.M = kFlat; p.N = 2 * kHidden; p.K = B; p.k_chunk = B;
     p.x = l->x3; p.ldx = kFlat; p.dz = l->dzh; p.out = Pm(l, gr, l->t_fcw);
     p.bias_out = Pm(l, gr, l->t_fcb);
-    ACME_GEMM_N("fc_wgrad", 128, 128, 2, 2, p, 1);
+    ACME_GEMM("fc_wgrad", 128, 128, 2, 2, 16, 1, p, 1);
   }
   {  // FC input grad -> dZ3 (masked by conv3's ReLU).
     DenseDgrad<true> p;
     p.M = B; p.N = kFlat; p.K = 2 * kHidden; p.k_chunk = p.K;
     p.dz = l->dzh; p.w = P(l, prm, l->t_fcw); p.xprev = l->x3; p.ldx = kFlat; p.dx = l->dz3;
-    ACME_GEMM_NK("fc_dgrad", 64, 128, 2, 2, 16, p, 1);
+    ACME_GEMM("fc_dgrad", 64, 128, 2, 2, 16, 1, p, 1);
   }
   return ACME_OK;  // the torso backward is stage 1 (acme_dqn_forward_backward_stage)
 }
@@ -661,13 +571,13 @@ int mlp_wgrad(acme_dqn* l, const Layer& L, const void* x, const float* dz, int B
     p.M = L.in; p.N = L.out; p.K = B; p.k_chunk = B;
     p.x = static_cast<const typename In::T*>(x); p.ldx = L.in; p.dz = dz; p.out = dw;
     p.bias_out = db;
-    ACME_GEMM_N("mlp_wgrad", 64, 64, 2, 2, p, 1);
+    ACME_GEMM("mlp_wgrad", 64, 64, 2, 2, 16, 1, p, 1);
   } else {
     DenseWgrad<false, In> p;
     p.M = L.in; p.N = L.out; p.K = B; p.k_chunk = B;
     p.x = static_cast<const typename In::T*>(x); p.ldx = L.in; p.dz = dz; p.out = dw;
     p.bias_out = db;
-    ACME_GEMM_N("mlp_wgrad", 64, 64, 2, 2, p, 1);
+    ACME_GEMM("mlp_wgrad", 64, 64, 2, 2, 16, 1, p, 1);
   }
   return ACME_OK;
 }
@@ -696,13 +606,13 @@ int mlp_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st) {
         p.M = B; p.N = L.in; p.K = L.out; p.k_chunk = L.out;
         p.dz = dz; p.w = P(l, prm, L.w); p.xprev = l->mlp_act[i - 1]; p.ldx = L.in;
         p.dx = l->mlp_dz[i - 1];
-        ACME_GEMM_N("mlp_dgrad", 64, 64, 2, 2, p, 1);
+        ACME_GEMM("mlp_dgrad", 64, 64, 2, 2, 16, 1, p, 1);
       } else {
         DenseDgrad<false> p;
         p.M = B; p.N = L.in; p.K = L.out; p.k_chunk = L.out;
         p.dz = dz; p.w = P(l, prm, L.w); p.xprev = l->mlp_act[i - 1]; p.ldx = L.in;
         p.dx = l->mlp_dz[i - 1];
-        ACME_GEMM_N("mlp_dgrad", 64, 64, 2, 2, p, 1);
+        ACME_GEMM("mlp_dgrad", 64, 64, 2, 2, 16, 1, p, 1);
       }
     }
   }
@@ -726,17 +636,11 @@ int sync_planes(acme_dqn* l, hipStream_t st) {
 // Initial scale records: w = r = wi = 1, amax slots 0; each record's flag is the guard word
 // of the tensors it covers (the online step's, the target forward's, the parameters').
 int reset_scales(acme_dqn* l) {
-  std::vector<gemm::PScale> init(kScCount);
-  std::memset(init.data(), 0, init.size() * sizeof(gemm::PScale));
-  for (auto& r : init) r.w = r.r = r.wi = r.rl = 1.f;
-  for (int i = 0; i < kScCount; ++i)
-    init[i].flag = i >= kScT1 && i <= kScT3 ? &l->guard->tt
-                   : i >= kScTransient     ? &l->guard->prm
-                                           : &l->guard->on;
-  ACME_HIP_TRY(hipMemcpy(l->scales, init.data(), init.size() * sizeof(gemm::PScale),
-                         hipMemcpyHostToDevice));
-  ACME_HIP_TRY(hipMemset(l->overflow, 0, sizeof(int)));
-  return ACME_OK;
+  return scales_init(l, kScCount, [l](int i) {
+    return i >= kScT1 && i <= kScT3 ? &l->guard->tt
+           : i >= kScTransient     ? &l->guard->prm
+                                   : &l->guard->on;
+  });
 }
 
 }  // namespace
@@ -767,14 +671,10 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
     acme_dqn_destroy(l);
     return code;
   };
-  if ((rc = dev_alloc(l, &l->guard, 1)) != ACME_OK) return fail(rc);
-  if (hipMemset(l->guard, 0, sizeof(StepGuard)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&l->host_skipped), sizeof(int64_t),
-                    hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&l->host_verdicts), kVerdictRing * sizeof(uint32_t),
+  if ((rc = guard_create(l)) != ACME_OK) return fail(rc);
+  if (hipHostMalloc(reinterpret_cast<void**>(&l->host_verdicts), kVerdictRing * sizeof(uint32_t),
                     hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
     return fail((set_error("step guard allocation failed"), ACME_ERR_HIP));
-  *l->host_skipped = 0;
   for (int i = 0; i < kVerdictRing; ++i) l->host_verdicts[i] = 0xFFFFFFFFu;  // none decided
   if (cfg->network == ACME_NET_NATURE_DQN) {
     l->t_c1w = add_tensor(l, "atari_torso/conv2_d/w", {8, 8, 4, 32});
@@ -811,8 +711,7 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
     if (cfg->obs_dtype == ACME_OBS_U8_SCALED && (int64_t)R2 * kObsBytes * 2 < (int64_t)INT32_MAX) {
       l->p3_capable = true;
       const int64_t fl = l->flat;
-      if ((rc = dev_alloc(l, &l->scales, kScCount)) || (rc = dev_alloc(l, &l->overflow, 1)) ||
-          (rc = reset_scales(l)) ||
+      if ((rc = reset_scales(l)) ||
           (rc = dev_alloc(l, &l->wpl, gemm::kPlanes * fl)) ||
           (rc = dev_alloc(l, &l->tpl, gemm::kPlanes * fl)) ||
           (rc = dev_alloc(l, &l->frames, (int64_t)R2 * kObsBytes)) ||
@@ -918,7 +817,7 @@ int acme_dqn_destroy(acme_dqn* l) {
   for (auto& e : l->dp_ev)
     if (e) (void)hipEventDestroy(e);
   if (l->dp_stream) (void)hipStreamDestroy(l->dp_stream);
-  if (l->host_skipped) (void)hipHostFree(l->host_skipped);
+  guard_destroy(l);
   if (l->host_verdicts) (void)hipHostFree(l->host_verdicts);
   delete l;
   return ACME_OK;
@@ -956,57 +855,26 @@ int acme_dqn_params_changed(acme_dqn* l) {
   return ACME_OK;
 }
 
-// Scale state = (w, r, wi, rl) of every record, host floats.
 int acme_dqn_scale_state(const acme_dqn* l, float* out, int32_t capacity, int32_t* count) {
-  ACME_CHECK_ARG(l && count, "null argument");
-  *count = l->scales ? 4 * kScCount : 0;
-  if (!l->scales || !out) return ACME_OK;
-  ACME_CHECK_ARG(capacity >= 4 * kScCount, "scale state needs %d floats", 4 * kScCount);
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < kScCount; ++i)
-    ACME_HIP_TRY(hipMemcpy(out + 4 * i, l->scales + i, 4 * sizeof(float), hipMemcpyDeviceToHost));
-  return ACME_OK;
+  return scale_state(l, out, capacity, count);
 }
 
 int acme_dqn_set_scale_state(acme_dqn* l, const float* in, int32_t count) {
-  ACME_CHECK_ARG(l && in, "null argument");
-  ACME_CHECK_ARG(l->scales && count == 4 * kScCount, "scale state of %d floats expected, got %d",
-                 l->scales ? 4 * kScCount : 0, count);
-  for (int i = 0; i < 4 * kScCount; ++i) {
-    int e;
-    const float m = std::frexp(in[i], &e);
-    ACME_CHECK_ARG(m == 0.5f, "scale state entries must be powers of two");
-  }
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < kScCount; ++i)
-    ACME_HIP_TRY(hipMemcpy(l->scales + i, in + 4 * i, 4 * sizeof(float), hipMemcpyHostToDevice));
-  l->scales_ok = true;
-  l->target_dirty = true;
-  return ACME_OK;
+  const int rc = set_scale_state(l, in, count);
+  if (rc == ACME_OK) l->target_dirty = true;
+  return rc;
 }
 
 int acme_dqn_plane_overflow(acme_dqn* l, int32_t* overflow, int32_t reset) {
-  ACME_CHECK_ARG(l && overflow, "null argument");
-  *overflow = 0;
-  if (!l->overflow) return ACME_OK;
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  int v = 0;
-  ACME_HIP_TRY(hipMemcpy(&v, l->overflow, sizeof(int), hipMemcpyDeviceToHost));
-  *overflow = v != 0;
-  if (reset) ACME_HIP_TRY(hipMemset(l->overflow, 0, sizeof(int)));
-  return ACME_OK;
+  return plane_overflow(l, overflow, reset);
 }
 
-int64_t acme_dqn_skipped_steps(const acme_dqn* l) {
-  if (!l || !l->host_skipped) return 0;
-  return *reinterpret_cast<volatile const int64_t*>(l->host_skipped);
-}
+int64_t acme_dqn_skipped_steps(const acme_dqn* l) { return skipped_steps(l); }
 
 int acme_dqn_guard_state(acme_dqn* l, int64_t* out4) {
   ACME_CHECK_ARG(l && out4 && l->guard, "null argument");
-  ACME_HIP_TRY(hipDeviceSynchronize());
   StepGuard g;
-  ACME_HIP_TRY(hipMemcpy(&g, l->guard, sizeof(g), hipMemcpyDeviceToHost));
+  if (int rc = read_guard(l, &g)) return rc;
   out4[0] = g.applied;
   out4[1] = g.skipped;
   out4[2] = g.last;
@@ -1018,9 +886,8 @@ int acme_dqn_verdict_timeouts(acme_dqn* l, int64_t* out) {
   ACME_CHECK_ARG(l && out, "null argument");
   *out = 0;
   if (!l->guard) return ACME_OK;
-  ACME_HIP_TRY(hipDeviceSynchronize());
   StepGuard g;
-  ACME_HIP_TRY(hipMemcpy(&g, l->guard, sizeof(g), hipMemcpyDeviceToHost));
+  if (int rc = read_guard(l, &g)) return rc;
   *out = g.vtimeout;
   return ACME_OK;
 }
@@ -1047,9 +914,7 @@ int acme_dqn_step_verdict(const acme_dqn* l, int64_t seq, int32_t* state) {
 
 int acme_dqn_set_applied_steps(acme_dqn* l, int64_t n) {
   ACME_CHECK_ARG(l && l->guard && n >= 0, "bad argument");
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  ACME_HIP_TRY(hipMemcpy(&l->guard->applied, &n, sizeof(n), hipMemcpyHostToDevice));
-  return ACME_OK;
+  return set_applied(l, n);
 }
 
 int acme_dqn_skip_word(const acme_dqn* l, const uint32_t** out) {
@@ -1198,10 +1063,7 @@ static int calibrate_scales(acme_dqn* l, const acme_transition_batch* batch, hip
   l->calibrating = false;
   if (rc != ACME_OK) return rc;
   // Overflows at the initial scales are expected and corrected by the passes.
-  ACME_HIP_TRY(hipMemsetAsync(l->overflow, 0, sizeof(int), st));
-  if ((rc = clear_guard_flags(l, st)) != ACME_OK) return rc;
-  l->scales_ok = true;
-  return ACME_OK;
+  return calibration_done(l, st);
 }
 
 static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batch,

@@ -29,10 +29,12 @@
 #include "gemm_p3.h"
 #include "gemm_x6.h"
 #include "kernels.h"
+#include "launch.h"
 #include "learner_common.h"
 #include "profiler.h"
 #include "torso.h"
 #include "lstm.h"
+#include "recurrent_common.h"
 
 using namespace acme;
 using namespace acme::conv;
@@ -41,66 +43,31 @@ using acme::gemm::launch_gemm;
 namespace {
 
 constexpr int kNormBlocks = 256;
-constexpr int kOarSplits = 8;    // split-K of the Atari OAR projection (K = 7744 + A + 1)
 constexpr int kOarSplitsP3 = 8;  // split-K of the plane-engine OAR projection (K = 7744)
 constexpr int kP3MinRows = 64;   // learner steps of at least this many frames use the planes
 
 }  // namespace
 
-struct acme_impala {
+struct acme_impala : RecurrentNet {
   acme_impala_config cfg;
-  std::vector<Tensor> tensors;
-  int64_t flat = 0;
-  int F = 0, D = 0, H = 0, H2 = 0, A = 0;  // features, embedding, lstm, head, actions
-  int t_c[6] = {-1, -1, -1, -1, -1, -1};   // torso w1 b1 w2 b2 w3 b3
-  int t_wi = -1, t_wh = -1, t_b = -1, t_w1 = -1, t_b1 = -1, t_wpv = -1, t_bpv = -1;
-  float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr;
-  int64_t num_steps = 0;
-  std::vector<void*> allocs;
+  int t_w1 = -1, t_b1 = -1, t_wpv = -1, t_bpv = -1;
   // workspace (rows = max_batch * max_sequence_length)
-  float *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *dz1 = nullptr, *dz2 = nullptr,
-        *dz3 = nullptr;
-  float* slab = nullptr;
-  float *gx = nullptr, *gates = nullptr, *h = nullptr, *c = nullptr, *hh = nullptr, *pv = nullptr;
-  float *dpv = nullptr, *dhh = nullptr, *dh = nullptr, *dgates = nullptr, *dc = nullptr;
+  float *hh = nullptr, *pv = nullptr, *dpv = nullptr, *dhh = nullptr;
   float *vs = nullptr, *pg_adv = nullptr, *lrho = nullptr, *lpa = nullptr, *ent = nullptr;
   double* norm_part = nullptr;
   int64_t* dev_step = nullptr;
   float* metrics_tmp = nullptr;
   float* norms = nullptr;
-  // Persistent LSTM unroll (H = 256, B <= 64): the forward's h_t granules [2][B * H] and the
-  // backward's partial-product granules [2][16][B * H] (8 B: tag | value bits), zeroed before
-  // every launch; the spin-timeout word.  lstm_steps: per-step launches instead (tests).
-  unsigned long long* xg = nullptr;
-  unsigned long long* xb = nullptr;
-  unsigned* tmo = nullptr;
-  bool lstm_steps = false;
   // Policy steps of an actor-side network on the plane engine (acme_impala_set_policy_planes):
   // the torso and W_i on f16 planes, the records rescaled after every call.
   bool policy_planes = false;
-  unsigned lstm_epoch = 0;
-  // Plane path of the Atari learner step (the DQN kernels: scaled two-plane f16 MFMA):
-  // parameter planes of the torso + W_i prefix of the flat buffer, refreshed at the start
-  // of every plane step; f16 frames; activation / gradient planes; its own split-K slab.
+  // Plane path of the Atari learner step (RecurrentNet; the DQN kernels): the f16 frames.
   bool p3_capable = false;
-  int64_t p3_prefix = 0;  // floats of the flat buffer split into planes (torso + W_i)
-  uint16_t* wpl = nullptr;
   uint16_t* frames = nullptr;
-  torso::Plane x1p{}, x2p{}, x3p{}, dz1p{}, dz2p{}, dz3p{}, dgp{};
-  // Scale records (gemm_p3.h PScale): the transient torso activations / gradients first
-  // (rescaled at the end of every plane step), then the parameter and dgates planes (set
-  // from their exact maxima by every split); sticky overflow flag.
-  gemm::PScale* scales = nullptr;
-  int* overflow = nullptr;
-  bool scales_ok = false;
-  float* pslab = nullptr;
   bool last_p3 = false;  // the last learner step ran the plane path (debug buffers join planes)
-  int64_t last_rows = 0;
-  // Step guard (kernels.h): a step whose planes overflowed or whose LSTM unroll timed out
+  // Step guard (PlaneGuard): a step whose planes overflowed or whose LSTM unroll timed out
   // (tmo[0]; tmo[1] counts them, tmo[2] is the policy step's own timeout word) applies no
   // update.  grad_sumsq folds the flags; clip_adam reads guard->last.
-  StepGuard* guard = nullptr;
-  int64_t* host_skipped = nullptr;
 };
 
 namespace {
@@ -108,8 +75,7 @@ namespace {
 // Every record is transient (written and read within a step, rescaled at its end from the
 // step's maxima): the activations, their gradients, dgates and the parameter planes (split
 // from the f32 parameters at the start of each forward).
-enum { kScX1, kScX2, kScX3, kScDz3, kScDz2, kScDz1, kScDgates, kScParams, kScTransient,
-       kScCount = kScTransient };
+enum { kScTransient = kScRecurrent, kScCount = kScTransient };
 
 // dW_h = h_prev^T dgates: h_prev of row m = b*T + t is h[m - 1] (t > 0) or h0[b] (t = 0).
 struct HPrevWgrad {
@@ -163,18 +129,6 @@ bool rg_pairs(const acme_impala*, int B) { return ceil_div(B, 2) * kRgGroups <= 
 // forward 48.5 -> 36.5 us, BPTT 39.5 -> 31.2 us, the step 0.491 -> 0.473 ms against two
 // rows (three alternating pairs, round 4; scalar FMAs, the same per-row order and bits).
 bool rg_single(const acme_impala*, int B) { return B * kRgGroups <= 256; }
-
-// The granule tags of the next persistent launch: tag0 + t, tag0 = 128 x a per-learner launch
-// count, so no launch can match a granule an earlier one left (the buffers are never cleared
-// between launches); the buffers are cleared once the count wraps.
-unsigned next_lstm_tags(acme_impala* l, hipStream_t st) {
-  if (++l->lstm_epoch >= (1u << 24)) {
-    l->lstm_epoch = 1;
-    (void)hipMemsetAsync(l->xg, 0, (size_t)2 * l->cfg.max_batch * l->H * 8, st);
-    (void)hipMemsetAsync(l->xb, 0, (size_t)2 * kRgGroups * l->cfg.max_batch * l->H * 8, st);
-  }
-  return l->lstm_epoch << 7;
-}
 
 // ------------------------------------------------------------------ loss
 // Three launches over the B*T rows (row = b * T + t, t < T-1 carry the losses):
@@ -343,163 +297,40 @@ __global__ void __launch_bounds__(256) impala_loss_grad_kernel(const LossArgs a)
 
 // ------------------------------------------------------------------ orchestration
 
-#define IM_GEMM(name, BM, BN, WM, WN, WK, prob, splits)                                         \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0,  \
-                   (gemm::matmul_peak_tflops<WK, decltype(prob)>()));                             \
-    hipError_t _e = gemm::launch_matmul<BM, BN, WM, WN, 16, WK>(prob, splits, st);              \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__);  \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-// The small f32 layers after the LSTM (a few hundred rows): the register-operand engine
-// (gemm_direct.h: each lane's k run in one burst, 8 waves per 32 x 32 tile; round 5: faster
-// than the staged f32 engine, profiles/r05/ab/impala_direct_small_layers.log).
-#define IM_DGEMM(name, prob)                                                                   \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0,  \
-                   157.3);                                                                     \
-    hipError_t _e = gemm::launch_direct(prob, 1, (prob).K, st);                                \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__);  \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-#define IM_CHECK()                                                                             \
-  do {                                                                                         \
-    hipError_t _e = hipGetLastError();                                                         \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-inline int chunk_for(int K, int splits) {
-  int c = (int)ceil_div(K, splits);
-  return (int)ceil_div(c, 32) * 32;
-}
-
-bool atari(const acme_impala* l) { return l->cfg.torso == ACME_IMPALA_TORSO_ATARI; }
-
-// ---- plane path helpers
-#define IM_P3_GEMM(name, BM, BN, WM, WN, BKV, prob, splits)                                    \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                    \
-    hipError_t _e = gemm::launch_gemm_p3<BM, BN, WM, WN, BKV>(prob, splits, st);              \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-#define IM_P3WS_GEMM(name, BM, BN, WM, WN, BKV, prob, splits)                                  \
-  do {                                                                                         \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                    \
-    hipError_t _e = gemm::launch_gemm_p3ws<BM, BN, WM, WN, BKV, true>(prob, splits, st);      \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-// Plane view of parameter tensor t in the [2][flat] parameter planes.
-torso::Plane WP(const acme_impala* l, int t) {
-  return torso::Plane{l->wpl + l->tensors[t].offset, l->flat, l->scales + kScParams};
-}
-gemm::PlaneSrc SRC(const torso::Plane& x, int64_t elems) {
-  return gemm::PlaneSrc{x.p, x.stride, (int32_t)(2 * elems), x.sc};
-}
-torso::PWeights torso_pw(const acme_impala* l) {
-  return torso::PWeights{WP(l, l->t_c[0]), WP(l, l->t_c[2]), WP(l, l->t_c[4]),
-                         P(l, l->params, l->t_c[1]), P(l, l->params, l->t_c[3]),
-                         P(l, l->params, l->t_c[5])};
-}
 // The plane path runs the learner steps of the Atari torso with enough frames to fill the
 // GEMMs (ACME_V_IMP3=1 at creation: the f32 engine throughout, for tests).
 bool use_p3(const acme_impala* l, int rows) { return l->p3_capable && rows >= kP3MinRows; }
-
-torso::Weights torso_w(const acme_impala* l) {
-  return torso::Weights{P(l, l->params, l->t_c[0]), P(l, l->params, l->t_c[1]),
-                        P(l, l->params, l->t_c[2]), P(l, l->params, l->t_c[3]),
-                        P(l, l->params, l->t_c[4]), P(l, l->params, l->t_c[5])};
-}
 
 // Network forward over rows = B*T frames: features, OAR projection, T LSTM steps, head.
 int network_forward(acme_impala* l, const void* obs, const int32_t* prev_a, const float* prev_r,
                     const float* h0, const float* c0, int64_t state_stride, int B, int T,
                     hipStream_t st, bool p3, unsigned* tmo) {
   const int rows = B * T, H = l->H, A = l->A;
-  const float* feat;
+  int rc;
   if (p3) {
     // Parameter planes of the torso + W_i (the only plane operands), the f16 frames,
     // the plane torso, then feat @ W_i[0:F] on the plane engine and the embedding tail.
-    int rc;
-    {
-      ACME_PROF("impala_planes", st, 0.0, 8.0 * (double)l->p3_prefix);
-      rc = launch_split_planes_lagged(l->params, l->p3_prefix, l->wpl, l->flat,
-                                      l->scales + kScParams, st);
-      if (rc != ACME_OK) return rc;
-    }
+    if ((rc = split_param_planes(l, l->params, l->wpl, kScParams, "impala_planes", st)) != ACME_OK)
+      return rc;
     {
       ACME_PROF("impala_frames_f16", st, 0.0, 3.0 * (double)rows * torso::kObsBytes);
       rc = launch_frames_f16(static_cast<const uint8_t*>(obs), static_cast<const uint8_t*>(obs),
                               rows, rows, torso::kObsBytes, l->frames, st);
       if (rc != ACME_OK) return rc;
     }
-    rc = torso::forward_p3(torso_pw(l), torso::Frames{l->frames}, rows,
-                           torso::PActs{l->x1p, l->x2p, l->x3p}, st);
-    if (rc != ACME_OK) return rc;
-    const int F = l->F, N = 4 * H;
-    P3DenseFwd p;
-    p.M = rows; p.N = N; p.K = F; p.k_chunk = chunk_for(F, kOarSplitsP3);
-    p.a_src = SRC(l->x3p, (int64_t)rows * F); p.ldx = F;
-    p.b_src = SRC(WP(l, l->t_wi), (int64_t)F * N); p.slab = l->pslab;
-    IM_P3WS_GEMM("impala_oar_fwd", 128, 128, 2, 2, 32, p, kOarSplitsP3);
-    {
-      ACME_PROF("impala_oar_reduce", st, 0.0, 4.0 * (kOarSplitsP3 + 1) * (double)rows * N);
-      const int64_t n4 = (int64_t)rows * N / 4;
-      oar_finish_kernel<<<(unsigned)ceil_div(n4, 256), 256, 0, st>>>(
-          l->pslab, kOarSplitsP3, rows, N, P(l, l->params, l->t_wi) + (size_t)F * N,
-          P(l, l->params, l->t_b), prev_a, prev_r, A, l->gx);
-      IM_CHECK();
-    }
-  } else if (atari(l)) {
-    int rc = torso::forward(torso_w(l), true, obs, obs, rows, rows,
-                            torso::Acts{l->x1, l->x2, l->x3}, st);
-    if (rc != ACME_OK) return rc;
-    feat = l->x3;
+    rc = oar_forward_p3<128, 128>(l, l->params, l->wpl, kScParams, torso::Frames{l->frames}, rows,
+                                  kOarSplitsP3, -1, prev_a, prev_r, "impala_oar_fwd",
+                                  "impala_oar_reduce", st);
   } else {
-    feat = static_cast<const float*>(obs);
+    rc = oar_forward_f32(l, l->params, obs, rows, prev_a, prev_r, "impala_oar_fwd",
+                         "impala_oar_reduce", st);
   }
-  if (!p3) {
-    OarFwd p;
-    p.M = rows; p.N = 4 * H; p.K = l->D;
-    p.x = Oar{feat, l->F, A, prev_a, prev_r};
-    p.w = P(l, l->params, l->t_wi); p.bias = P(l, l->params, l->t_b); p.y = l->gx;
-    if (atari(l)) {
-      p.k_chunk = chunk_for(p.K, kOarSplits);
-      p.slab = l->slab;
-      IM_GEMM("impala_oar_fwd", 64, 64, 2, 2, 1, p, kOarSplits);
-      ACME_PROF("impala_oar_reduce", st, 0.0, 4.0 * (kOarSplits + 1) * (double)rows * 4 * H);
-      int rc = launch_slab_reduce(l->slab, kOarSplits, (int64_t)rows * 4 * H, l->gx,
-                                  (int64_t)rows * 4 * H, nullptr, P(l, l->params, l->t_b), 4 * H,
-                                  0, st);
-      if (rc != ACME_OK) return rc;
-    } else {
-      p.k_chunk = p.K;
-      p.slab = nullptr;
-      IM_GEMM("impala_oar_fwd", 32, 32, 1, 1, 8, p, 1);
-    }
-  }
+  if (rc != ACME_OK) return rc;
   {
     ACME_PROF("impala_lstm_fwd", st, 2.0 * rows * (double)H * 4 * H, 0.0);
     const size_t smem = lstm_fwd_smem(B, H);
     if (lstm_persistent(l, B)) {  // one launch for the whole unroll (lstm_fwd_rg_kernel)
-      const unsigned tag0 = next_lstm_tags(l, st);
+      const unsigned tag0 = next_lstm_tags(l, st, 7);
       if (rg_single(l, B))
         lstm_fwd_rg_kernel<kRgH, 1><<<(unsigned)(B * kRgGroups), 256, 0, st>>>(
             l->gx, P(l, l->params, l->t_wh), h0, state_stride, c0, state_stride, B, T, T, 1,
@@ -512,7 +343,7 @@ int network_forward(acme_impala* l, const void* obs, const int32_t* prev_a, cons
         lstm_fwd_rg_kernel<kRgH, 4><<<(unsigned)(ceil_div(B, 4) * kRgGroups), 256, 0, st>>>(
             l->gx, P(l, l->params, l->t_wh), h0, state_stride, c0, state_stride, B, T, T, 1,
             l->gates, l->h, l->c, l->xg, tag0, tmo);
-      IM_CHECK();
+      ACME_LAUNCH_CHECK();
     } else
     for (int t = 0; t < T; ++t) {
       const float* hp = t == 0 ? h0 : l->h + (size_t)(t - 1) * H;
@@ -521,7 +352,7 @@ int network_forward(acme_impala* l, const void* obs, const int32_t* prev_a, cons
       lstm_fwd_step_kernel<<<H / kFwdUnits, 256, smem, st>>>(l->gx, P(l, l->params, l->t_wh), hp, hs,
                                                           cp, hs, B, T, 1, t, H, l->gates, l->h,
                                                           l->c, B);
-      IM_CHECK();
+      ACME_LAUNCH_CHECK();
     }
   }
   {
@@ -530,7 +361,7 @@ int network_forward(acme_impala* l, const void* obs, const int32_t* prev_a, cons
     p.x = l->h; p.x2 = l->h; p.split_b = rows; p.ldx = H;
     p.w = P(l, l->params, l->t_w1); p.bias = P(l, l->params, l->t_b1); p.y = l->hh;
     p.act = ACT_RELU; p.slab = nullptr;
-    IM_DGEMM("impala_head_fwd", p);
+    ACME_DIRECT_GEMM("impala_head_fwd", p);
   }
   {
     DenseFwd<false> p;
@@ -538,7 +369,7 @@ int network_forward(acme_impala* l, const void* obs, const int32_t* prev_a, cons
     p.x = l->hh; p.x2 = l->hh; p.split_b = rows; p.ldx = l->H2;
     p.w = P(l, l->params, l->t_wpv); p.bias = P(l, l->params, l->t_bpv); p.y = l->pv;
     p.act = ACT_NONE; p.slab = nullptr;
-    IM_DGEMM("impala_pv_fwd", p);
+    ACME_DIRECT_GEMM("impala_pv_fwd", p);
   }
   return ACME_OK;
 }
@@ -567,13 +398,13 @@ int impala_step_impl(acme_impala* l, const acme_sequence_batch* bt, float* metri
     a.lstm_timeout = l->tmo;
     const unsigned rb = (unsigned)ceil_div(rows, 4);
     impala_rowstats_kernel<<<rb, 256, 0, st>>>(a);
-    IM_CHECK();
+    ACME_LAUNCH_CHECK();
     const int vrows = B * T;
     impala_vtrace_kernel<<<1, 256, vrows <= kVtraceLdsRows ? 6 * sizeof(float) * vrows : 0,
                            st>>>(a);
-    IM_CHECK();
+    ACME_LAUNCH_CHECK();
     impala_loss_grad_kernel<<<rb, 256, 0, st>>>(a);
-    IM_CHECK();
+    ACME_LAUNCH_CHECK();
   }
   float* gr = l->grads;
   {  // policy/value head
@@ -581,27 +412,27 @@ int impala_step_impl(acme_impala* l, const acme_sequence_batch* bt, float* metri
     w.M = l->H2; w.N = A + 1; w.K = rows; w.k_chunk = rows;
     w.x = l->hh; w.ldx = l->H2; w.dz = l->dpv; w.out = Pm(l, gr, l->t_wpv);
     w.bias_out = Pm(l, gr, l->t_bpv);
-    IM_DGEMM("impala_pv_wgrad", w);
+    ACME_DIRECT_GEMM("impala_pv_wgrad", w);
     DenseDgrad<false> d;
     d.M = rows; d.N = l->H2; d.K = A + 1; d.k_chunk = A + 1;
     d.dz = l->dpv; d.w = P(l, l->params, l->t_wpv); d.xprev = l->hh; d.ldx = l->H2; d.dx = l->dhh;
     d.act = ACT_RELU;
-    IM_DGEMM("impala_pv_dgrad", d);
+    ACME_DIRECT_GEMM("impala_pv_dgrad", d);
   }
   {  // Linear(256) after the LSTM
     DenseWgrad<true> w;
     w.M = H; w.N = l->H2; w.K = rows; w.k_chunk = rows;
     w.x = l->h; w.ldx = H; w.dz = l->dhh; w.out = Pm(l, gr, l->t_w1); w.bias_out = Pm(l, gr, l->t_b1);
-    IM_DGEMM("impala_head_wgrad", w);
+    ACME_DIRECT_GEMM("impala_head_wgrad", w);
     DenseDgrad<true> d;
     d.M = rows; d.N = H; d.K = l->H2; d.k_chunk = l->H2;
     d.dz = l->dhh; d.w = P(l, l->params, l->t_w1); d.xprev = nullptr; d.ldx = H; d.dx = l->dh;
-    IM_DGEMM("impala_head_dgrad", d);
+    ACME_DIRECT_GEMM("impala_head_dgrad", d);
   }
   {  // BPTT
     ACME_PROF("impala_lstm_bwd", st, 2.0 * rows * (double)H * 4 * H, 0.0);
     if (lstm_persistent(l, B)) {  // one launch for the whole BPTT (lstm_bwd_rg_kernel)
-      const unsigned tag0 = next_lstm_tags(l, st);
+      const unsigned tag0 = next_lstm_tags(l, st, 7);
       if (rg_single(l, B))
         lstm_bwd_rg_kernel<kRgH, 1><<<(unsigned)(B * kRgGroups), 256, 0, st>>>(
             l->dh, P(l, l->params, l->t_wh), l->gates, l->c, bt->c0, bt->state_stride, B, T, 0,
@@ -614,14 +445,14 @@ int impala_step_impl(acme_impala* l, const acme_sequence_batch* bt, float* metri
         lstm_bwd_rg_kernel<kRgH, 4><<<(unsigned)(ceil_div(B, 4) * kRgGroups), 256, 0, st>>>(
             l->dh, P(l, l->params, l->t_wh), l->gates, l->c, bt->c0, bt->state_stride, B, T, 0,
             T, 1, l->dgates, l->xb, tag0, l->tmo);
-      IM_CHECK();
+      ACME_LAUNCH_CHECK();
     } else {
     ACME_HIP_TRY(hipMemsetAsync(l->dc, 0, (size_t)B * H * sizeof(float), st));
     for (int t = T - 1; t >= 0; --t) {
       lstm_bwd_step_kernel<<<H / kUnits, 256, 0, st>>>(l->dh, P(l, l->params, l->t_wh), l->gates,
                                                        l->c, bt->c0, bt->state_stride, l->dc,
                                                        l->dgates, B, T, t, H, T, 1);
-      IM_CHECK();
+      ACME_LAUNCH_CHECK();
     }
     }
   }
@@ -630,48 +461,17 @@ int impala_step_impl(acme_impala* l, const acme_sequence_batch* bt, float* metri
     w.M = H; w.N = 4 * H; w.K = rows; w.k_chunk = rows;
     w.h = l->h; w.h0 = bt->h0; w.h0_stride = bt->state_stride; w.T = T; w.dz = l->dgates;
     w.out = Pm(l, gr, l->t_wh);
-    IM_GEMM("impala_wh_wgrad", 32, 32, 1, 1, 8, w, 1);
+    ACME_GEMM("impala_wh_wgrad", 32, 32, 1, 1, 16, 8, w, 1);
   }
   if (p3) {  // W_i, b and the embedding gradient on the plane engine, then the plane torso
-    const int F = l->F, N = 4 * H;
+    if ((rc = dgates_to_planes(l, rows, "impala_dgates_planes", st)) != ACME_OK) return rc;
     {
-      ACME_PROF("impala_dgates_planes", st, 0.0, 8.0 * (double)rows * N);
-      rc = launch_split_planes_lagged(l->dgates, (int64_t)rows * N, l->dgp.p, l->dgp.stride,
-                                      l->dgp.sc, st);
-      if (rc != ACME_OK) return rc;
-    }
-    {
-      P3DenseWgrad p;
-      p.M = F; p.N = N; p.K = rows; p.k_chunk = rows;
-      p.a_src = SRC(l->x3p, (int64_t)rows * F); p.ldx = F;
-      p.b_src = SRC(l->dgp, (int64_t)rows * N); p.out = Pm(l, gr, l->t_wi);
-      p.bias_out = Pm(l, gr, l->t_b);
+      P3DenseWgrad p = wi_wgrad_p3(l, rows, 0);
       // (256x128 warp-specialised tiles: 24.7 -> 26.6 us, round 4.)
-      IM_P3_GEMM("impala_wi_wgrad", 128, 128, 2, 2, 16, p, 1);
+      ACME_P3_GEMM("impala_wi_wgrad", 128, 128, 2, 2, 16, p, 1);
     }
-    {
-      ACME_PROF("impala_wi_wgrad_tail", st, 0.0, 4.0 * (double)rows * N);
-      const int tw = tail_waves(A);
-      oar_wgrad_tail_kernel<<<(unsigned)ceil_div(N, 64), 64 * tw,
-                              (size_t)tw * (A + 1) * 64 * sizeof(float), st>>>(
-          l->dgates, rows, N, bt->prev_action, bt->prev_reward, A,
-          Pm(l, gr, l->t_wi) + (size_t)F * N);
-      IM_CHECK();
-    }
-    {
-      P3DenseDgrad p;
-      p.M = rows; p.N = F; p.K = N; p.k_chunk = N;
-      p.a_src = SRC(l->dgp, (int64_t)rows * N);
-      p.b_src = SRC(WP(l, l->t_wi), (int64_t)F * N);
-      p.xprev = CPlanes{l->x3p.p, l->x3p.stride, l->x3p.sc}; p.ldx = F;
-      p.dx = Planes{l->dz3p.p, l->dz3p.stride, l->dz3p.sc};
-      IM_P3WS_GEMM("impala_feat_dgrad", 128, 128, 2, 2, 32, p, 1);
-    }
-    torso::Grads g{Pm(l, gr, l->t_c[0]), Pm(l, gr, l->t_c[1]), Pm(l, gr, l->t_c[2]),
-                   Pm(l, gr, l->t_c[3]), Pm(l, gr, l->t_c[4]), Pm(l, gr, l->t_c[5])};
-    rc = torso::backward_p3(torso_pw(l), g, torso::Frames{l->frames}, rows,
-                            torso::PActs{l->x1p, l->x2p, l->x3p}, l->dz3p, l->dz2p, l->dz1p,
-                            l->pslab, st);
+    rc = wi_backward_p3<128, 128>(l, torso::Frames{l->frames}, rows, 0, bt->prev_action,
+                                  bt->prev_reward, "impala_wi_wgrad_tail", "impala_feat_dgrad", st);
     if (rc != ACME_OK) return rc;
     // The next plane step's activation / gradient scales from this step's maxima.
     RescaleGuard rg;  // an overflowed or underflowed record skips the step (grad_sumsq)
@@ -680,25 +480,9 @@ int impala_step_impl(acme_impala* l, const acme_sequence_batch* bt, float* metri
     rc = launch_plane_rescale(l->scales, kScTransient, kScTransient, -1, -1, l->overflow, st, -1,
                               -1, rg);
     if (rc != ACME_OK) return rc;
-  } else {
-    const float* feat = atari(l) ? l->x3 : static_cast<const float*>(bt->observation);
-    OarWgrad o;
-    o.M = l->D; o.N = 4 * H; o.K = rows; o.k_chunk = rows;
-    o.x = Oar{feat, l->F, A, bt->prev_action, bt->prev_reward};
-    o.dz = l->dgates; o.out = Pm(l, gr, l->t_wi); o.bias_out = Pm(l, gr, l->t_b);
-    if (atari(l)) IM_GEMM("impala_wi_wgrad", 128, 128, 2, 2, 1, o, 1);
-    else IM_GEMM("impala_wi_wgrad", 32, 32, 1, 1, 8, o, 1);
-  }
-  if (!p3 && atari(l)) {  // embedding features -> conv3 dZ -> torso backward
-    DenseDgrad<true> d;
-    d.M = rows; d.N = l->F; d.K = 4 * H; d.k_chunk = 4 * H;
-    d.dz = l->dgates; d.w = P(l, l->params, l->t_wi); d.xprev = l->x3; d.ldx = l->F;
-    d.dx = l->dz3; d.act = ACT_RELU;
-    IM_GEMM("impala_feat_dgrad", 64, 128, 2, 2, 1, d, 1);
-    torso::Grads g{Pm(l, gr, l->t_c[0]), Pm(l, gr, l->t_c[1]), Pm(l, gr, l->t_c[2]),
-                   Pm(l, gr, l->t_c[3]), Pm(l, gr, l->t_c[4]), Pm(l, gr, l->t_c[5])};
-    rc = torso::backward(torso_w(l), g, true, bt->observation, rows,
-                         torso::Acts{l->x1, l->x2, l->x3}, l->dz3, l->dz2, l->dz1, l->slab, st);
+  } else {  // the same on the f32 engine
+    rc = wi_backward_f32(l, bt->observation, rows, 0, bt->prev_action, bt->prev_reward,
+                         "impala_wi_wgrad", "impala_feat_dgrad", st);
     if (rc != ACME_OK) return rc;
   }
   if (!apply) return ACME_OK;
@@ -734,25 +518,20 @@ int acme_impala_destroy(acme_impala* l) {
   // right after its last step): drain it before the buffers go.
   (void)hipDeviceSynchronize();
   for (void* p : l->allocs) (void)hipFree(p);
-  if (l->host_skipped) (void)hipHostFree(l->host_skipped);
+  guard_destroy(l);
   delete l;
   return ACME_OK;
 }
 
 int acme_impala_create(const acme_impala_config* cfg, acme_impala** out) {
   ACME_CHECK_ARG(cfg && out, "null argument");
-  ACME_CHECK_ARG(cfg->torso == ACME_IMPALA_TORSO_ATARI || cfg->torso == ACME_IMPALA_TORSO_FLAT,
-                 "unknown torso %d", cfg->torso);
-  ACME_CHECK_ARG(cfg->torso == ACME_IMPALA_TORSO_ATARI || cfg->obs_dim >= 1,
-                 "obs_dim must be >= 1 for the flat torso");
+  if (int rc = check_recurrent_config(cfg->torso, cfg->obs_dim, cfg->max_batch, cfg->lstm_size))
+    return rc;
   ACME_CHECK_ARG(cfg->num_actions >= 1 && cfg->num_actions <= 63, "num_actions must be in [1, 63]");
   ACME_CHECK_ARG(cfg->semantics == ACME_SEMANTICS_TF || cfg->semantics == ACME_SEMANTICS_JAX,
                  "unknown learner semantics %d", cfg->semantics);
-  ACME_CHECK_ARG(cfg->max_batch >= 1 && cfg->max_batch <= 1024, "max_batch must be in [1, 1024]");
   ACME_CHECK_ARG(cfg->max_sequence_length >= 2 && cfg->max_sequence_length <= 64,
                  "max_sequence_length must be in [2, 64]");
-  ACME_CHECK_ARG(cfg->lstm_size >= 8 && cfg->lstm_size % 8 == 0,
-                 "lstm_size must be a positive multiple of 8");
   // The per-step forward stages h_prev of every row in LDS; the one-launch unroll (lstm_size
   // 256, at most 64 sequences) does not.
   ACME_CHECK_ARG(lstm_fwd_smem(cfg->max_batch, cfg->lstm_size) <= 65536 ||
@@ -766,24 +545,10 @@ int acme_impala_create(const acme_impala_config* cfg, acme_impala** out) {
     acme_impala_destroy(l);
     return code;
   };
-  l->A = cfg->num_actions;
-  l->H = cfg->lstm_size;
-  l->H2 = cfg->head_size;
-  l->F = cfg->torso == ACME_IMPALA_TORSO_ATARI ? torso::kFlat : cfg->obs_dim;
-  l->D = l->F + l->A + 1;
   const std::string pre = "impala_atari_network/";
-  if (cfg->torso == ACME_IMPALA_TORSO_ATARI) {
-    l->t_c[0] = add_tensor(l, pre + "atari_torso/conv2_d/w", {8, 8, 4, 32});
-    l->t_c[1] = add_tensor(l, pre + "atari_torso/conv2_d/b", {32});
-    l->t_c[2] = add_tensor(l, pre + "atari_torso/conv2_d_1/w", {4, 4, 32, 64});
-    l->t_c[3] = add_tensor(l, pre + "atari_torso/conv2_d_1/b", {64});
-    l->t_c[4] = add_tensor(l, pre + "atari_torso/conv2_d_2/w", {3, 3, 64, 64});
-    l->t_c[5] = add_tensor(l, pre + "atari_torso/conv2_d_2/b", {64});
-  }
+  add_recurrent_tensors(l, pre, cfg->torso, cfg->obs_dim, cfg->num_actions, cfg->lstm_size,
+                        cfg->head_size, cfg->max_batch);
   const int H = l->H, A = l->A, H2 = l->H2;
-  l->t_wi = add_tensor(l, pre + "lstm/w_i", {l->D, 4 * H});
-  l->t_wh = add_tensor(l, pre + "lstm/w_h", {H, 4 * H});
-  l->t_b = add_tensor(l, pre + "lstm/b", {4 * H});
   l->t_w1 = add_tensor(l, pre + "linear/w", {H, H2});
   l->t_b1 = add_tensor(l, pre + "linear/b", {H2});
   l->t_wpv = add_tensor(l, pre + "policy_value/w", {H2, A + 1});
@@ -791,78 +556,26 @@ int acme_impala_create(const acme_impala_config* cfg, acme_impala** out) {
   const int64_t R = (int64_t)cfg->max_batch * cfg->max_sequence_length;
   const int B = cfg->max_batch;
   int rc;
-  int64_t slab = 1;
-  if (cfg->torso == ACME_IMPALA_TORSO_ATARI) {
-    slab = std::max<int64_t>(torso::wgrad_slab_floats(), (int64_t)kOarSplits * R * 4 * H);
-    if ((rc = dev_alloc(l, &l->x1, R * torso::kX1)) || (rc = dev_alloc(l, &l->x2, R * torso::kFlat)) ||
-        (rc = dev_alloc(l, &l->x3, R * torso::kFlat)) || (rc = dev_alloc(l, &l->dz1, R * torso::kX1)) ||
-        (rc = dev_alloc(l, &l->dz2, R * torso::kFlat)) || (rc = dev_alloc(l, &l->dz3, R * torso::kFlat)))
-      return fail(rc);
-  }
-  if ((rc = dev_alloc(l, &l->slab, slab)) || (rc = dev_alloc(l, &l->gx, R * 4 * H)) ||
-      (rc = dev_alloc(l, &l->gates, R * 4 * H)) || (rc = dev_alloc(l, &l->h, R * H)) ||
-      (rc = dev_alloc(l, &l->c, R * H)) || (rc = dev_alloc(l, &l->hh, R * H2)) ||
+  if ((rc = alloc_recurrent(l, R, R, 1)) || (rc = dev_alloc(l, &l->hh, R * H2)) ||
       (rc = dev_alloc(l, &l->pv, R * (A + 1))) || (rc = dev_alloc(l, &l->dpv, R * (A + 1))) ||
-      (rc = dev_alloc(l, &l->dhh, R * H2)) || (rc = dev_alloc(l, &l->dh, R * H)) ||
-      (rc = dev_alloc(l, &l->dgates, R * 4 * H)) || (rc = dev_alloc(l, &l->dc, (int64_t)B * H)) ||
-      (rc = dev_alloc(l, &l->vs, R)) || (rc = dev_alloc(l, &l->pg_adv, R)) ||
-      (rc = dev_alloc(l, &l->lrho, R)) || (rc = dev_alloc(l, &l->lpa, R)) ||
-      (rc = dev_alloc(l, &l->ent, R)) ||
+      (rc = dev_alloc(l, &l->dhh, R * H2)) || (rc = dev_alloc(l, &l->vs, R)) ||
+      (rc = dev_alloc(l, &l->pg_adv, R)) || (rc = dev_alloc(l, &l->lrho, R)) ||
+      (rc = dev_alloc(l, &l->lpa, R)) || (rc = dev_alloc(l, &l->ent, R)) ||
       (rc = dev_alloc(l, &l->norm_part, 2 * kNormBlocks)) || (rc = dev_alloc(l, &l->dev_step, 1)) ||
       (rc = dev_alloc(l, &l->metrics_tmp, 4)) || (rc = dev_alloc(l, &l->norms, 2)) ||
-      (rc = dev_alloc(l, &l->xg, (int64_t)2 * B * H)) || (rc = dev_alloc(l, &l->tmo, 4)) ||
-      (rc = dev_alloc(l, &l->guard, 1)))
-    return fail(rc);
-  if (hipMemset(l->guard, 0, sizeof(StepGuard)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&l->host_skipped), sizeof(int64_t),
-                    hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-    return fail((set_error("step guard allocation failed"), ACME_ERR_HIP));
-  *l->host_skipped = 0;
-  if (H == kRgH && B <= kRgMaxB &&
-      (rc = dev_alloc(l, &l->xb, (int64_t)2 * kRgGroups * B * H)))
+      (rc = alloc_lstm_granules(l, H == kRgH && B <= kRgMaxB ? kRgGroups : 0)) ||
+      (rc = guard_create(l)))
     return fail(rc);
   // Plane path (Atari torso): each operand plane is addressed through a 31-bit byte range,
   // so the f16 frames of one step bound it (R < 38,000 frames); larger unrolls stay f32.
-  if (cfg->torso == ACME_IMPALA_TORSO_ATARI && R * torso::kObsBytes * 2 < (int64_t)INT32_MAX &&
-      R >= kP3MinRows && tune_variant("IMP3") != 1) {
+  if (atari(l) && R * torso::kObsBytes * 2 < (int64_t)INT32_MAX && R >= kP3MinRows &&
+      tune_variant("IMP3") != 1) {
     l->p3_capable = true;
-    l->p3_prefix = align64(l->tensors[l->t_wi].offset + l->tensors[l->t_wi].numel);
-    if ((rc = dev_alloc(l, &l->scales, kScCount)) || (rc = dev_alloc(l, &l->overflow, 1)))
-      return fail(rc);
-    std::vector<gemm::PScale> init(kScCount);
-    std::memset(init.data(), 0, init.size() * sizeof(gemm::PScale));
-    for (auto& r : init) {
-      r.w = r.r = r.wi = r.rl = 1.f;
-      r.flag = &l->guard->on;
-    }
-    if (hipMemcpy(l->scales, init.data(), init.size() * sizeof(gemm::PScale),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(l->overflow, 0, sizeof(int)) != hipSuccess)
-      return fail((set_error("scale record init failed"), ACME_ERR_HIP));
-    auto plane = [&](torso::Plane* x, int64_t count, int rec) {
-      const int64_t stride = align64(count);
-      uint16_t* q = nullptr;
-      int r = dev_alloc(l, &q, gemm::kPlanes * stride);
-      *x = torso::Plane{q, stride, l->scales + rec};
-      return r;
-    };
-    if ((rc = dev_alloc(l, &l->wpl, gemm::kPlanes * l->flat)) ||
-        (rc = dev_alloc(l, &l->frames, R * torso::kObsBytes)) ||
-        (rc = plane(&l->x1p, R * torso::kX1, kScX1)) ||
-        (rc = plane(&l->x2p, R * torso::kFlat, kScX2)) ||
-        (rc = plane(&l->x3p, R * torso::kFlat, kScX3)) ||
-        (rc = plane(&l->dz1p, R * torso::kX1, kScDz1)) ||
-        (rc = plane(&l->dz2p, R * torso::kFlat, kScDz2)) ||
-        (rc = plane(&l->dz3p, R * torso::kFlat, kScDz3)) ||
-        (rc = plane(&l->dgp, R * 4 * H, kScDgates)) ||
-        (rc = dev_alloc(l, &l->pslab, std::max<int64_t>(torso::wgrad_slab_floats_p3(),
-                                                        (int64_t)kOarSplitsP3 * R * 4 * H))))
+    if ((rc = alloc_recurrent_planes(l, R, R, kScCount, kOarSplitsP3)) ||
+        (rc = dev_alloc(l, &l->frames, R * torso::kObsBytes)))
       return fail(rc);
   }
-  if (hipMemset(l->dev_step, 0, sizeof(int64_t)) != hipSuccess ||
-      hipMemset(l->tmo, 0, 4 * sizeof(unsigned)) != hipSuccess ||
-      (l->xg && hipMemset(l->xg, 0, (size_t)2 * B * H * 8) != hipSuccess) ||
-      (l->xb && hipMemset(l->xb, 0, (size_t)2 * kRgGroups * B * H * 8) != hipSuccess))
+  if (hipMemset(l->dev_step, 0, sizeof(int64_t)) != hipSuccess)
     return fail((set_error("hipMemset failed"), ACME_ERR_HIP));
   *out = l;
   return ACME_OK;
@@ -916,38 +629,14 @@ int acme_impala_step(acme_impala* l, const acme_sequence_batch* b, float* metric
                      ((uintptr_t)b->h0 & 15) == 0,
                  "core state rows must be 16-byte aligned with state_stride >= lstm_size");
   hipStream_t st = as_stream(stream);
-  int rc = ACME_OK;
-  if (atari(l) && use_p3(l, (int)(b->batch * b->sequence_length)) && !l->scales_ok) {
-    // Plane scales for newly bound parameters: forward + backward passes without the
-    // update (the first at the current scales, whose maxima are measured before the split;
-    // each ends with the rescale), then the step.  Overflows at the initial scales are
-    // expected and cleared.
-    // Four passes: the input-gradient chain dgates -> dz3 -> dz2 -> dz1 is four tensors
-    // deep, and a tensor computed from planes that underflowed at their initial scale
-    // measures 0 until its input is calibrated (as the DQN learner's calibrate_scales).
-    for (int pass = 0; pass < 4 && rc == ACME_OK; ++pass) rc = impala_step_impl(l, b, nullptr, st, false);
-    if (rc != ACME_OK) return rc;
-    ACME_HIP_TRY(hipMemsetAsync(l->overflow, 0, sizeof(int), st));
-    ACME_HIP_TRY(hipMemsetAsync(l->guard, 0, offsetof(StepGuard, applied), st));
-    ACME_HIP_TRY(hipMemsetAsync(l->tmo, 0, sizeof(unsigned), st));
-    l->scales_ok = true;
-  }
-  rc = impala_step_impl(l, b, metrics, st);
-  if (rc != ACME_OK) return rc;
-  l->num_steps += 1;
-  return ACME_OK;
+  const bool p3 = atari(l) && use_p3(l, (int)(b->batch * b->sequence_length));
+  return calibrate_then_step(l, p3, st, [&](bool apply) {
+    return impala_step_impl(l, b, apply ? metrics : nullptr, st, apply);
+  });
 }
 
 int acme_impala_plane_overflow(acme_impala* l, int32_t* overflow, int32_t reset) {
-  ACME_CHECK_ARG(l && overflow, "null argument");
-  *overflow = 0;
-  if (!l->overflow) return ACME_OK;
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  int v = 0;
-  ACME_HIP_TRY(hipMemcpy(&v, l->overflow, sizeof(int), hipMemcpyDeviceToHost));
-  *overflow = v != 0;
-  if (reset) ACME_HIP_TRY(hipMemset(l->overflow, 0, sizeof(int)));
-  return ACME_OK;
+  return plane_overflow(l, overflow, reset);
 }
 
 int acme_impala_policy_step(acme_impala* l, const void* obs, const int32_t* prev_action,
@@ -1009,49 +698,24 @@ int acme_impala_set_applied_steps(acme_impala* l, int64_t n) {
   ACME_CHECK_ARG(l && n >= 0, "bad argument");
   ACME_HIP_TRY(hipDeviceSynchronize());
   ACME_HIP_TRY(hipMemcpy(l->dev_step, &n, sizeof(n), hipMemcpyHostToDevice));
-  ACME_HIP_TRY(hipMemcpy(&l->guard->applied, &n, sizeof(n), hipMemcpyHostToDevice));
-  return ACME_OK;
+  return set_applied(l, n);
 }
 
-// Scale state = (w, r, wi, rl) of every record (as acme_dqn_scale_state).
 int acme_impala_scale_state(const acme_impala* l, float* out, int32_t capacity, int32_t* count) {
-  ACME_CHECK_ARG(l && count, "null argument");
-  *count = l->scales ? 4 * kScCount : 0;
-  if (!l->scales || !out) return ACME_OK;
-  ACME_CHECK_ARG(capacity >= 4 * kScCount, "scale state needs %d floats", 4 * kScCount);
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < kScCount; ++i)
-    ACME_HIP_TRY(hipMemcpy(out + 4 * i, l->scales + i, 4 * sizeof(float), hipMemcpyDeviceToHost));
-  return ACME_OK;
+  return scale_state(l, out, capacity, count);
 }
 
 int acme_impala_set_scale_state(acme_impala* l, const float* in, int32_t count) {
-  ACME_CHECK_ARG(l && in, "null argument");
-  ACME_CHECK_ARG(l->scales && count == 4 * kScCount, "scale state of %d floats expected, got %d",
-                 l->scales ? 4 * kScCount : 0, count);
-  for (int i = 0; i < 4 * kScCount; ++i) {
-    int e;
-    const float m = std::frexp(in[i], &e);
-    ACME_CHECK_ARG(m == 0.5f, "scale state entries must be powers of two");
-  }
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < kScCount; ++i)
-    ACME_HIP_TRY(hipMemcpy(l->scales + i, in + 4 * i, 4 * sizeof(float), hipMemcpyHostToDevice));
-  l->scales_ok = true;
-  return ACME_OK;
+  return set_scale_state(l, in, count);
 }
 
-int64_t acme_impala_skipped_steps(const acme_impala* l) {
-  if (!l || !l->host_skipped) return 0;
-  return *reinterpret_cast<volatile const int64_t*>(l->host_skipped);
-}
+int64_t acme_impala_skipped_steps(const acme_impala* l) { return skipped_steps(l); }
 
 int acme_impala_guard_state(acme_impala* l, int64_t* out4) {
   ACME_CHECK_ARG(l && out4 && l->guard, "null argument");
-  ACME_HIP_TRY(hipDeviceSynchronize());
   StepGuard g;
   unsigned t[4];
-  ACME_HIP_TRY(hipMemcpy(&g, l->guard, sizeof(g), hipMemcpyDeviceToHost));
+  if (int rc = read_guard(l, &g)) return rc;
   ACME_HIP_TRY(hipMemcpy(t, l->tmo, sizeof(t), hipMemcpyDeviceToHost));
   out4[0] = g.applied;
   out4[1] = g.skipped;
@@ -1072,11 +736,7 @@ int acme_impala_debug_buffer(const acme_impala* l, const char* name, const float
                              int64_t* count) {
   ACME_CHECK_ARG(l && name && out && count, "null argument");
   const int64_t R = (int64_t)l->cfg.max_batch * l->cfg.max_sequence_length;
-  struct Item {
-    const char* n;
-    const float* p;
-    int64_t c;
-  } items[] = {
+  const DebugItem items[] = {
       {"pv", l->pv, R * (l->A + 1)}, {"vs", l->vs, R},        {"pg_adv", l->pg_adv, R},
       {"h", l->h, R * l->H},         {"c", l->c, R * l->H},   {"dpv", l->dpv, R * (l->A + 1)},
       {"dgates", l->dgates, R * 4 * l->H}, {"grad_norm", l->norms, 1},
@@ -1086,30 +746,14 @@ int acme_impala_debug_buffer(const acme_impala* l, const char* name, const float
       {"hh", l->hh, R * l->H2},      {"x1", l->x1, l->x1 ? R * torso::kX1 : 0},
       {"x2", l->x2, l->x2 ? R * torso::kFlat : 0}, {"x3", l->x3, l->x3 ? R * torso::kFlat : 0},
   };
-  for (const Item& it : items)
-    if (it.p && strcmp(it.n, name) == 0) {
-      if (l->last_p3) {  // the plane path keeps the torso activations as planes: join them
-        const struct {
-          const char* n;
-          torso::Plane pl;
-          int64_t per_row;
-        } ptab[] = {{"x1", l->x1p, torso::kX1}, {"x2", l->x2p, torso::kFlat},
-                    {"x3", l->x3p, torso::kFlat}};
-        for (const auto& q : ptab)
-          if (strcmp(q.n, name) == 0) {
-            ACME_HIP_TRY(hipDeviceSynchronize());
-            int rc = launch_join_planes(q.pl.p, q.pl.stride, l->last_rows * q.per_row,
-                                        const_cast<float*>(it.p), q.pl.sc, 0);
-            if (rc != ACME_OK) return rc;
-            ACME_HIP_TRY(hipDeviceSynchronize());
-          }
-      }
-      *out = it.p;
-      *count = it.c;
-      return ACME_OK;
-    }
-  set_error("unknown debug buffer '%s'", name);
-  return ACME_ERR_INVALID;
+  int rc = find_debug_buffer(items, name, out, count);
+  if (rc == ACME_OK && !*out) {  // a buffer this network does not have (x1 on the flat torso)
+    set_error("unknown debug buffer '%s'", name);
+    return ACME_ERR_INVALID;
+  }
+  // The plane path keeps the torso activations as planes: join them.
+  if (rc == ACME_OK && l->last_p3) rc = join_torso_planes(l, name);
+  return rc;
 }
 
 }  // extern "C"

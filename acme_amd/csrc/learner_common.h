@@ -2,7 +2,10 @@
 // way: the tensor table of its flat parameter buffer, its device workspace allocations, and
 // the lookups behind *_tensor_info and *_debug_buffer.  The helpers are templates over the
 // learner type L, which has `std::vector<Tensor> tensors`, `int64_t flat` and
-// `std::vector<void*> allocs`.
+// `std::vector<void*> allocs`.  Beside it: launch.h (the profiled GEMM launch macros and
+// chunk_for), plane_guard.h (the step guard and plane-scale state of the learners on the f16
+// plane engine: dqn.hip, impala.hip, r2d2_learner.hip) and recurrent_common.h (the OAR
+// embedding -> LSTM part impala.hip and r2d2_learner.hip share).
 #pragma once
 
 #include <algorithm>

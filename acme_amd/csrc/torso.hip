@@ -15,6 +15,8 @@
 #include "gemm_p3c12.h"
 #include "gemm_x6.h"
 #include "kernels.h"
+#include "launch.h"
+#include "plane_guard.h"
 #include "profiler.h"
 
 namespace acme {
@@ -27,24 +29,6 @@ namespace {
 
 constexpr int kConv1WgradSplits = 256, kConv2WgradSplits = 64, kConv3WgradSplits = 64;
 
-inline int chunk_for(int K, int splits) {
-  int c = (int)ceil_div(K, splits);
-  return (int)ceil_div(c, 32) * 32;
-}
-
-#define TORSO_GEMM(name, BM, BN, WM, WN, prob, splits)                                        \
-  TORSO_GEMM_F(name, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, BM, BN, WM, \
-               WN, prob, splits)
-#define TORSO_GEMM_F(name, flops, BM, BN, WM, WN, prob, splits)                               \
-  do {                                                                                        \
-    ACME_PROF_PEAK(name, st, flops, 0.0, (gemm::matmul_peak_tflops<1, decltype(prob)>()));      \
-    hipError_t _e = gemm::launch_matmul<BM, BN, WM, WN, 16>(prob, splits, st);                 \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-
 // Conv weight + bias gradient: split-K over the batch pixels into [splits][K+1][CO] slabs
 // (row K = bias partial from the GEMM's colsum hook), then one deterministic reduction
 // writes dW and db.
@@ -54,7 +38,7 @@ int conv_wgrad(const typename In::T* x, const float* dz, int rows, int splits, f
   ConvWgrad<G, In> p;
   p.M = G::K; p.N = G::CO; p.K = rows * G::OPIX; p.k_chunk = chunk_for(p.K, splits);
   p.x = x; p.dz = dz; p.slab = slab;
-  TORSO_GEMM(name, BM, BN, WM, WN, p, splits);
+  ACME_GEMM(name, BM, BN, WM, WN, 16, 1, p, splits);
   const int64_t count = (int64_t)(p.M + 1) * p.N;
   ACME_PROF(rname, st, 0.0, 4.0 * (double)(splits + 1) * (double)count);
   return launch_slab_reduce(slab, splits, count, dw, (int64_t)p.M * p.N, db, nullptr, 0, 0, st);
@@ -75,25 +59,25 @@ int forward(const Weights& w, bool u8, const void* obs_a, const void* obs_b, int
     p.M = rows * G1::OPIX; p.N = G1::CO; p.K = G1::K; p.k_chunk = G1::K;
     p.x = static_cast<const uint8_t*>(obs_a); p.x2 = static_cast<const uint8_t*>(obs_b);
     p.split_b = split; p.w = w.w1; p.bias = w.b1; p.y = a.x1;
-    TORSO_GEMM("conv1_fwd", 128, 32, 4, 1, p, 1);
+    ACME_GEMM("conv1_fwd", 128, 32, 4, 1, 16, 1, p, 1);
   } else {
     ConvFwd<G1, InF32> p;
     p.M = rows * G1::OPIX; p.N = G1::CO; p.K = G1::K; p.k_chunk = G1::K;
     p.x = static_cast<const float*>(obs_a); p.x2 = static_cast<const float*>(obs_b);
     p.split_b = split; p.w = w.w1; p.bias = w.b1; p.y = a.x1;
-    TORSO_GEMM("conv1_fwd", 128, 32, 4, 1, p, 1);
+    ACME_GEMM("conv1_fwd", 128, 32, 4, 1, 16, 1, p, 1);
   }
   {
     ConvFwd<G2, InF32> p;
     p.M = rows * G2::OPIX; p.N = G2::CO; p.K = G2::K; p.k_chunk = G2::K;
     p.x = a.x1; p.x2 = a.x1; p.split_b = rows; p.w = w.w2; p.bias = w.b2; p.y = a.x2;
-    TORSO_GEMM("conv2_fwd", 128, 64, 2, 2, p, 1);
+    ACME_GEMM("conv2_fwd", 128, 64, 2, 2, 16, 1, p, 1);
   }
   {
     ConvFwd<G3, InF32> p;
     p.M = rows * G3::OPIX; p.N = G3::CO; p.K = G3::K; p.k_chunk = G3::K;
     p.x = a.x2; p.x2 = a.x2; p.split_b = rows; p.w = w.w3; p.bias = w.b3; p.y = a.x3;
-    TORSO_GEMM("conv3_fwd", 128, 64, 2, 2, p, 1);
+    ACME_GEMM("conv3_fwd", 128, 64, 2, 2, 16, 1, p, 1);
   }
   return ACME_OK;
 }
@@ -109,7 +93,7 @@ int backward(const Weights& w, const Grads& g, bool u8, const void* obs, int row
     ConvDgrad<G3> p;
     p.M = rows * G3::IPIX; p.N = G3::CI; p.K = G3::KH * G3::KW * G3::CO; p.k_chunk = p.K;
     p.dz = dz3; p.w = w.w3; p.xprev = a.x2; p.dx = dz2;
-    TORSO_GEMM("conv3_dgrad", 128, 64, 2, 2, p, 1);
+    ACME_GEMM("conv3_dgrad", 128, 64, 2, 2, 16, 1, p, 1);
   }
   // conv2
   if ((rc = conv_wgrad<G2, InF32, 64, 64, 2, 2>(a.x1, dz2, rows, kConv2WgradSplits, slab, g.w2,
@@ -121,8 +105,8 @@ int backward(const Weights& w, const Grads& g, bool u8, const void* obs, int row
     p.k_chunk = p.K; p.batch = rows;
     p.dz = dz2; p.w = w.w2; p.xprev = a.x1; p.dx = dz1;
     // Useful FLOPs: every input pixel once, K = KR per class.
-    TORSO_GEMM_F("conv2_dgrad", 2.0 * rows * G2::IPIX * G2::CI * (double)p.K, 256, 32, 4, 1, p,
-                 G2::S * G2::S);
+    ACME_GEMM_F("conv2_dgrad", 2.0 * rows * G2::IPIX * G2::CI * (double)p.K, 256, 32, 4, 1, 16,
+                1, p, G2::S * G2::S);
   }
   // conv1 (no input gradient needed)
   if (u8)
@@ -141,29 +125,6 @@ namespace {
 constexpr int kP3Conv1WgradSplits = 512, kP3Conv2WgradSplits = 128, kP3Conv3WgradSplits = 128;
 constexpr int kP3MaxWgradSplits = 512;
 
-#define P3_GEMM_F(name, flops, BM, BN, WM, WN, BK, prob, splits)                             \
-  do {                                                                                        \
-    ACME_PROF_PEAK(name, st, flops, 0.0, gemm::p3_peak_tflops<decltype(prob)>());             \
-    hipError_t _e = gemm::launch_gemm_p3<BM, BN, WM, WN, BK>(prob, splits, st);               \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-// Warp-specialised form (gemm_p3ws_kernel, fragment reads one k16 step ahead; BK = 32).
-#define P3WS_GEMM(name, BM, BN, WM, WN, prob, splits)                                        \
-  do {                                                                                        \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                   \
-    hipError_t _e = gemm::launch_gemm_p3ws<BM, BN, WM, WN, 32, true>(prob, splits, st);      \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-#define P3_GEMM(name, BM, BN, WM, WN, BK, prob, splits)                                      \
-  P3_GEMM_F(name, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, BM, BN, WM, \
-            WN, BK, prob, splits)
 // Image-resident convolution (gemm_p3i.h): FPB frames per block, WM x WN waves of 32*MT
 // rows; `frames` images.
 using I1F = gemm::ImgGeomPairs<G1>;
@@ -171,22 +132,9 @@ using I2F = gemm::ImgGeom<G2, false>;
 using I3F = gemm::ImgGeom<G3, false>;
 using I3D = gemm::ImgGeom<G3, true>;
 #define P3I_GEMM(name, GI, FPB, BN, WM, WN, MT, prob, frames)                                 \
-  do {                                                                                        \
-    ACME_PROF_PEAK(name, st, 2.0 * (double)(prob).M * (double)(prob).N * (double)(prob).K, 0.0, \
-                   gemm::p3_peak_tflops<decltype(prob)>());                                   \
-    hipError_t _e = gemm::launch_gemm_p3i<GI, FPB, BN, WM, WN, MT>(prob, frames, st);         \
-    if (_e != hipSuccess) {                                                                   \
-      set_error("gemm launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return ACME_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
+  ACME_LAUNCH_GEMM(name, ACME_MNK_FLOPS(prob), gemm::p3_peak_tflops<decltype(prob)>(),        \
+                   (gemm::launch_gemm_p3i<GI, FPB, BN, WM, WN, MT>(prob, frames, st)))
 
-inline CPlanes cp(const Plane& x) { return CPlanes{x.p, x.stride, x.sc}; }
-inline Planes pl(const Plane& x) { return Planes{x.p, x.stride, x.sc}; }
-// Operand source over the first `elems` elements of each plane.
-inline PlaneSrc src(const Plane& x, int64_t elems) {
-  return PlaneSrc{x.p, x.stride, (int32_t)(2 * elems), x.sc};
-}
 inline PlaneSrc frames_src(const Frames& f, int rows) {
   return PlaneSrc{static_cast<const uint16_t*>(f.p), 0,
                   (int32_t)((f.u8 ? 1 : 2) * (int64_t)rows * G1::IPIX * G1::CI)};
@@ -200,7 +148,7 @@ int conv1_fwd_p3(const PWeights& w, const Frames& frames, int rows, const Planes
   p.stamps = stamps;
   p.M = rows * G1::OPIX; p.N = G1::CO; p.K = G1::K; p.k_chunk = G1::K;
   const int n1 = U8 ? std::min(rows, frames.split) : rows;
-  p.a_src = frames_src(frames, n1); p.b_src = src(w.w1, G1::K * G1::CO);
+  p.a_src = frames_src(frames, n1); p.b_src = SRC(w.w1, G1::K * G1::CO);
   if (U8 && n1 < rows) {
     p.a_src2 = frames_src(frames.rows_from(n1), rows - n1);
     p.a_split = n1;
@@ -223,12 +171,12 @@ int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, c
             ACME_ERR_INVALID);
   P3ConvFwd<G1, 1, U8> p1;
   p1.M = nf * G1::OPIX; p1.N = G1::CO; p1.K = G1::K; p1.k_chunk = G1::K;
-  p1.a_src = frames_src(fr, nf); p1.b_src = src(w.w1, G1::K * G1::CO);
+  p1.a_src = frames_src(fr, nf); p1.b_src = SRC(w.w1, G1::K * G1::CO);
   p1.bias = w.b1;
   p1.y = Planes{a.x1.p + (int64_t)nsep * kX1, a.x1.stride, a.x1.sc};
   P3ConvFwd<G2, gemm::kPlanes> p2;
   p2.M = nf * G2::OPIX; p2.N = G2::CO; p2.K = G2::K; p2.k_chunk = G2::K;
-  p2.a_src = src(a.x1, (int64_t)rows * kX1); p2.b_src = src(w.w2, G2::K * G2::CO);
+  p2.a_src = SRC(a.x1, (int64_t)rows * kX1); p2.b_src = SRC(w.w2, G2::K * G2::CO);
   p2.bias = w.b2;
   p2.y = Planes{a.x2.p + (int64_t)nsep * kFlat, a.x2.stride, a.x2.sc};
   const double fl = 2.0 * p1.M * p1.N * (double)p1.K + 2.0 * p2.M * p2.N * (double)p2.K;
@@ -248,11 +196,11 @@ int conv1_wgrad_p3(const Frames& frames, int rows, const Plane& dz1, float* slab
   P3ConvWgrad<G1, 1, U8> q;
   q.M = G1::K; q.N = G1::CO; q.K = rows * G1::OPIX;
   q.k_chunk = chunk_for(q.K, splits);
-  q.a_src = frames_src(frames, rows); q.b_src = src(dz1, (int64_t)rows * kX1);
+  q.a_src = frames_src(frames, rows); q.b_src = SRC(dz1, (int64_t)rows * kX1);
   q.slab = slab;
   // Producer / consumer waves (gemm_p3ws_kernel): 28.5 -> 25.0 us, the same bits.
-  if (single_role) P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
-  else P3WS_GEMM("conv1_wgrad", 256, 32, 4, 1, q, splits);
+  if (single_role) ACME_P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
+  else ACME_P3WS_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
   p = q;
   return ACME_OK;
 }
@@ -289,14 +237,14 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
       (rc = frames.u8 ? conv12_fwd_p3<true>(w, frames, rows, nsep, a, st)
                       : conv12_fwd_p3<false>(w, frames, rows, nsep, a, st)) != ACME_OK)
     return rc;
-  if (nsep > 0 && (rc = frames.u8 ? conv1_fwd_p3<true>(w, frames, nsep, pl(a.x1), st, g_stamps_conv[0])
-                                  : conv1_fwd_p3<false>(w, frames, nsep, pl(a.x1), st, g_stamps_conv[0])) != ACME_OK)
+  if (nsep > 0 && (rc = frames.u8 ? conv1_fwd_p3<true>(w, frames, nsep, PP(a.x1), st, g_stamps_conv[0])
+                                  : conv1_fwd_p3<false>(w, frames, nsep, PP(a.x1), st, g_stamps_conv[0])) != ACME_OK)
     return rc;
   if (nsep > 0) {
     P3ConvFwd<G2, gemm::kPlanes> p;
     p.M = nsep * G2::OPIX; p.N = G2::CO; p.K = G2::K; p.k_chunk = G2::K;
-    p.a_src = src(a.x1, (int64_t)nsep * kX1); p.b_src = src(w.w2, G2::K * G2::CO);
-    p.bias = w.b2; p.y = pl(a.x2);
+    p.a_src = SRC(a.x1, (int64_t)nsep * kX1); p.b_src = SRC(w.w2, G2::K * G2::CO);
+    p.bias = w.b2; p.y = PP(a.x2);
     p.stamps = g_stamps_conv[1];
     // Image-resident x1 (gemm_p3i.h; two frames, 8 x 2 waves per block): with two f16
     // planes a frame's x1 image is 56 KB, so two frames and the weight ring fit one CU.
@@ -307,8 +255,8 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
   {
     P3ConvFwd<G3, gemm::kPlanes> p;
     p.M = rows * G3::OPIX; p.N = G3::CO; p.K = G3::K; p.k_chunk = G3::K;
-    p.a_src = src(a.x2, (int64_t)rows * kFlat); p.b_src = src(w.w3, G3::K * G3::CO);
-    p.bias = w.b3; p.y = pl(a.x3);
+    p.a_src = SRC(a.x2, (int64_t)rows * kFlat); p.b_src = SRC(w.w3, G3::K * G3::CO);
+    p.bias = w.b3; p.y = PP(a.x3);
     if (keep_x1 != 0) p.stamps = g_stamps_conv[2];  // the online forward's
     // Image-resident, 4 x 2 waves (measured 50.1 -> 43.5 us vs the 128x64 im2col engine;
     // two frames per block measured slower on the step, 0.550 -> 0.568-0.618 ms).
@@ -340,9 +288,9 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     p.M = G3::K; p.N = G3::CO; p.K = rows * G3::OPIX;
     const int splits = kP3Conv3WgradSplits;
     p.k_chunk = chunk_for(p.K, splits);
-    p.a_src = src(a.x2, (int64_t)rows * kFlat); p.b_src = src(dz3, (int64_t)rows * kFlat);
+    p.a_src = SRC(a.x2, (int64_t)rows * kFlat); p.b_src = SRC(dz3, (int64_t)rows * kFlat);
     p.slab = wslab;
-    P3_GEMM("conv3_wgrad", 128, 64, 2, 2, 32, p, splits);
+    ACME_P3_GEMM("conv3_wgrad", 128, 64, 2, 2, 32, p, splits);
     if (defer) sd.defer[2] = WgradSlab{wslab, splits, (int64_t)p.M * p.N, p.N};
     else if ((rc = p3_wgrad_reduce(p, splits, wslab, g.w3, g.b3, "conv3_wgrad_reduce", st)))
       return rc;
@@ -351,8 +299,8 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
   {
     P3ConvDgrad<G3> p;
     p.M = rows * G3::IPIX; p.N = G3::CI; p.K = G3::KH * G3::KW * G3::CO; p.k_chunk = p.K;
-    p.a_src = src(dz3, (int64_t)rows * kFlat); p.b_src = src(w.w3, G3::K * G3::CO);
-    p.xprev = cp(a.x2); p.dx = pl(dz2);
+    p.a_src = SRC(dz3, (int64_t)rows * kFlat); p.b_src = SRC(w.w3, G3::K * G3::CO);
+    p.xprev = CP(a.x2); p.dx = PP(dz2);
     // Image-resident dZ, two frames x 8 x 2 waves: 37.4 us (128x64 im2col) -> 31.2 us.
     P3I_GEMM("conv3_dgrad", I3D, 2, 64, 8, 2, 1, p, rows);
   }
@@ -366,10 +314,10 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     p.M = G2::K; p.N = G2::CO; p.K = rows * G2::OPIX;
     const int splits = kP3Conv2WgradSplits;
     p.k_chunk = chunk_for(p.K, splits);
-    p.a_src = src(a.x1, (int64_t)rows * kX1); p.b_src = src(dz2, (int64_t)rows * kFlat);
+    p.a_src = SRC(a.x1, (int64_t)rows * kX1); p.b_src = SRC(dz2, (int64_t)rows * kFlat);
     float* slab2 = defer ? sd.slab2 : wslab;
     p.slab = slab2;
-    P3_GEMM("conv2_wgrad", 128, 64, 2, 2, 32, p, splits);
+    ACME_P3_GEMM("conv2_wgrad", 128, 64, 2, 2, 32, p, splits);
     if (defer) sd.defer[1] = WgradSlab{slab2, splits, (int64_t)p.M * p.N, p.N};
     else if ((rc = p3_wgrad_reduce(p, splits, slab2, g.w2, g.b2, "conv2_wgrad_reduce", st)))
       return rc;
@@ -380,8 +328,8 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     P3ConvDgradSubZ<G2> p;
     p.M = P3ConvDgradSubZ<G2>::max_rows(rows); p.N = G2::CI; p.K = P3ConvDgradSubZ<G2>::KR;
     p.k_chunk = p.K; p.batch = rows;
-    p.a_src = src(dz2, (int64_t)rows * kFlat); p.b_src = src(w.w2, G2::K * G2::CO);
-    p.xprev = cp(a.x1); p.dx = pl(dz1);
+    p.a_src = SRC(dz2, (int64_t)rows * kFlat); p.b_src = SRC(w.w2, G2::K * G2::CO);
+    p.xprev = CP(a.x1); p.dx = PP(dz1);
     // Image-resident dZ, two frames x four classes per block (16 waves, gemm_p3s.h):
     // 57.7 us (128x32 im2col) -> 38.0 (one frame per block) -> 34.7 us.
     const double fl = 2.0 * rows * G2::IPIX * G2::CI * (double)p.K;

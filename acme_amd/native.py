@@ -338,8 +338,177 @@ OBS_U8 = 0
 OBS_F32 = 1
 
 
-class NativeDQN:
+class _NativeLearner:
+    """A native learner handle and its flat buffers, shared by every Native* learner class:
+    creation and lifetime, the tensor table, the flat params / (target) / grads / Adam m / v
+    buffers and their bind, the step count and debug buffers.  Subclasses name the C ABI
+    prefix (_prefix, e.g. "acme_dqn") and the error-message tag (_tag)."""
+
+    _prefix = ""
+    _tag = ""
+    _has_target = True  # a target network's buffer is bound after params
+
+    def _fn(self, name: str):
+        return getattr(lib(), f"{self._prefix}_{name}")
+
+    def _create(self, cfg, device, shared_params: Optional[torch.Tensor] = None) -> None:
+        """Creates the handle from cfg, allocates the flat buffers (params = shared_params
+        when given) and binds them."""
+        self.cfg = cfg
+        self.device = torch.device(device or "cuda")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)), f"{self._tag} create")
+        self._h = h
+        self.flat_size = int(self._fn("flat_size")(h))
+        self.tensors = _read_tensor_table(self._fn("num_tensors"), self._fn("tensor_info"), h)
+        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)  # noqa
+        if shared_params is not None:
+            if shared_params.numel() != self.flat_size or not shared_params.is_cuda:
+                raise ValueError("shared_params must be a device buffer of the same layout")
+            self.params = shared_params
+        else:
+            self.params = z()
+        bound = [self.params]
+        if self._has_target:
+            self.target = z()
+            bound.append(self.target)
+        self.grads, self.m, self.v = z(), z(), z()
+        bound += [self.grads, self.m, self.v]
+        check(self._fn("bind")(h, *[ptr(b) for b in bound]), f"{self._tag} bind")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._fn("destroy")(h)
+            except Exception:
+                pass
+            self._h = None
+
+    # --------------------------------------------------------------- parameters
+    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        out = {}
+        for name, off, shape in self.tensors:
+            n = int(np.prod(shape))
+            out[name] = flat[off:off + n].view(shape)
+        return out
+
+    def _copy_in(self, flat: torch.Tensor, src: Dict[str, np.ndarray]) -> None:
+        for name, t in self.views(flat).items():
+            t.copy_(torch.as_tensor(np.asarray(src[name], np.float32)).view(t.shape))
+
+    def set_params(self, params: Dict[str, np.ndarray], target: Optional[Dict] = None) -> None:
+        self._copy_in(self.params, params)
+        if self._has_target:
+            self._copy_in(self.target, target if target is not None else params)
+        self.params_changed()
+
+    def get_params(self, which: str = "params") -> Dict[str, np.ndarray]:
+        flat = getattr(self, which)
+        return {k: v.detach().cpu().numpy().copy() for k, v in self.views(flat).items()}
+
+    @property
+    def num_steps(self) -> int:
+        return int(self._fn("num_steps")(self._h))
+
+    @num_steps.setter
+    def num_steps(self, n: int) -> None:
+        check(self._fn("set_num_steps")(self._h, int(n)))
+
+    def debug_buffer(self, name: str) -> np.ndarray:
+        return _debug_buffer(self._fn("debug_buffer"), self._h, name, self.device)
+
+    def params_changed(self) -> None:
+        """The params / target buffers were written from outside (nothing to do for a learner
+        whose step reads the f32 buffers directly)."""
+
+    def _sequence_batch(self, observation, prev_action, prev_reward, action, reward, discount,
+                        h0, c0, behaviour_logits=None, core_state=True):
+        """Validates a recurrent learner's batch-major [B, T, ...] device tensors and the core
+        state at t = 0 (h0 / c0 [B, H] views with unit inner stride, unless not core_state);
+        returns the filled _lib.SequenceBatch."""
+        B, T = int(action.shape[0]), int(action.shape[1])
+        want = torch.uint8 if self.torso == "atari" else torch.float32
+        checks = [("observation", observation, want), ("prev_action", prev_action, torch.int32),
+                  ("prev_reward", prev_reward, torch.float32), ("action", action, torch.int32),
+                  ("reward", reward, torch.float32), ("discount", discount, torch.float32)]
+        if behaviour_logits is not None:
+            checks.append(("behaviour_logits", behaviour_logits, torch.float32))
+        for name, t, dt in checks:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
+                    and t.dtype == dt):
+                raise ValueError(f"{name} must be a contiguous {dt} device tensor")
+            if tuple(t.shape[:2]) != (B, T):
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {T}, ...]")
+        b = _lib.SequenceBatch()
+        b.observation, b.prev_action, b.prev_reward = ptr(observation), ptr(prev_action), ptr(prev_reward)
+        b.action, b.reward, b.discount = ptr(action), ptr(reward), ptr(discount)
+        b.behaviour_logits = ptr(behaviour_logits) if behaviour_logits is not None else None
+        if core_state:
+            for name, t in (("h0", h0), ("c0", c0)):
+                if (t is None or t.dtype != torch.float32 or t.shape != (B, self.lstm_size)
+                        or t.stride(1) != 1):
+                    raise ValueError(f"{name} must be float32 [{B}, {self.lstm_size}] with unit "
+                                     "inner stride")
+            if h0.stride(0) != c0.stride(0):
+                raise ValueError("h0 and c0 must share a row stride")
+            b.h0, b.c0, b.state_stride = ptr(h0), ptr(c0), int(h0.stride(0))
+        else:
+            b.h0 = b.c0 = None
+            b.state_stride = self.lstm_size
+        b.batch, b.sequence_length = B, T
+        return b
+
+
+class _PlaneState:
+    """Plane-scale and step-guard state of the learners on the f16 plane engine (NativeDQN,
+    NativeIMPALA, NativeR2D2), beside _NativeLearner."""
+
+    def params_changed(self) -> None:
+        """Tells the learner its params / target buffers were written from outside (its
+        derived f16 parameter planes are rebuilt and the plane scales recalibrate before the
+        next use)."""
+        check(self._fn("params_changed")(self._h), f"{self._tag} params_changed")
+
+    def scale_state(self) -> np.ndarray:
+        """The plane scales (learner state for checkpoints; empty without the plane path)."""
+        n = ctypes.c_int32(0)
+        fn, what = self._fn("scale_state"), f"{self._tag} scale_state"
+        check(fn(self._h, None, 0, ctypes.byref(n)), what)
+        out = np.zeros(n.value, np.float32)
+        if n.value:
+            check(fn(self._h, out.ctypes.data, n.value, ctypes.byref(n)), what)
+        return out
+
+    def set_scale_state(self, state) -> None:
+        """Restores scale_state() (after params_changed): resumed steps are bit-identical."""
+        a = np.ascontiguousarray(np.asarray(state, np.float32))
+        if a.size:
+            check(self._fn("set_scale_state")(self._h, a.ctypes.data, a.size),
+                  f"{self._tag} set_scale_state")
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps skipped (plane overflow or LSTM timeout) so far among those the device has
+        finished (no synchronisation)."""
+        return int(self._fn("skipped_steps")(self._h))
+
+
+def _plane_overflow(self, reset: bool = False) -> bool:
+    """True if a plane tensor exceeded f16's range at its scale since the last reset
+    (synchronises the device).  NativeDQN's and NativeIMPALA's plane_overflow."""
+    v = ctypes.c_int32(0)
+    check(self._fn("plane_overflow")(self._h, ctypes.byref(v), int(reset)),
+          f"{self._tag} plane_overflow")
+    return bool(v.value)
+
+
+class NativeDQN(_PlaneState, _NativeLearner):
     """acme_dqn learner + its flat buffers."""
+
+    _prefix, _tag = "acme_dqn", "dqn"
+    plane_overflow = _plane_overflow
 
     def __init__(self, *, network: str, num_actions: int, max_batch: int, obs_dtype: str,
                  obs_dim: int = 0, hidden: Sequence[int] = (), discount: float = 0.99,
@@ -373,88 +542,18 @@ class NativeDQN:
         cfg.target_update_period = int(target_update_period)
         cfg.max_abs_reward = max_abs_reward
         cfg.semantics = _lib.SEMANTICS_JAX if semantics == "jax" else _lib.SEMANTICS_TF
-        self.cfg = cfg
         self.semantics = semantics
         self.network = network
         self.num_actions = int(num_actions)
         self.max_batch = int(max_batch)
-        self.device = torch.device(device or "cuda")
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().acme_dqn_create(ctypes.byref(cfg), ctypes.byref(h)), "dqn create")
-        self._h = h
-        L = lib()
-        self.flat_size = int(L.acme_dqn_flat_size(h))
-        self.num_params = int(L.acme_dqn_num_params(h))
-        self.tensors = _read_tensor_table(L.acme_dqn_num_tensors, L.acme_dqn_tensor_info, h)
+        self._create(cfg, device)
+        self.num_params = int(lib().acme_dqn_num_params(self._h))
         d = self.device
-        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=d)  # noqa: E731
-        self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
-        check(L.acme_dqn_bind(h, ptr(self.params), ptr(self.target), ptr(self.grads),
-                              ptr(self.m), ptr(self.v)), "dqn bind")
         self.loss = torch.zeros(1, dtype=torch.float32, device=d)
         self.td_error = torch.zeros(max_batch, dtype=torch.float32, device=d)
         self.priorities = torch.zeros(max_batch, dtype=torch.float64, device=d)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().acme_dqn_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    # --------------------------------------------------------------- parameters
-    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        out = {}
-        for name, off, shape in self.tensors:
-            n = int(np.prod(shape))
-            out[name] = flat[off:off + n].view(shape)
-        return out
-
-    def set_params(self, params: Dict[str, np.ndarray], target: Optional[Dict] = None) -> None:
-        for flat, src in ((self.params, params), (self.target, target if target is not None else params)):
-            v = self.views(flat)
-            for name, t in v.items():
-                t.copy_(torch.as_tensor(np.asarray(src[name], np.float32)).view(t.shape))
-        self.params_changed()
-
-    def params_changed(self) -> None:
-        """Tells the learner its params / target buffers were written from outside (its
-        derived f16 parameter planes are rebuilt before the next use)."""
-        check(lib().acme_dqn_params_changed(self._h), "dqn params_changed")
-
-    def scale_state(self) -> np.ndarray:
-        """The plane scales (learner state for checkpoints; empty without the plane path)."""
-        n = ctypes.c_int32(0)
-        check(lib().acme_dqn_scale_state(self._h, None, 0, ctypes.byref(n)), "dqn scale_state")
-        out = np.zeros(n.value, np.float32)
-        if n.value:
-            check(lib().acme_dqn_scale_state(self._h, out.ctypes.data, n.value, ctypes.byref(n)),
-                  "dqn scale_state")
-        return out
-
-    def set_scale_state(self, state) -> None:
-        """Restores scale_state() (after params_changed): resumed steps are bit-identical."""
-        a = np.ascontiguousarray(np.asarray(state, np.float32))
-        if a.size:
-            check(lib().acme_dqn_set_scale_state(self._h, a.ctypes.data, a.size),
-                  "dqn set_scale_state")
-
-    def plane_overflow(self, reset: bool = False) -> bool:
-        """True if a plane tensor of the uint8 Nature path exceeded f16's range at its scale
-        since the last reset (synchronises the device; acme_dqn_plane_overflow)."""
-        v = ctypes.c_int32(0)
-        check(lib().acme_dqn_plane_overflow(self._h, ctypes.byref(v), int(reset)), "dqn plane_overflow")
-        return bool(v.value)
-
     # ---- step guard (acme_dqn_guard_state: the skip-on-overflow rule of the plane path)
-    @property
-    def skipped_steps(self) -> int:
-        """Steps skipped so far among those the device has finished (no synchronisation)."""
-        return int(lib().acme_dqn_skipped_steps(self._h))
-
     def guard_state(self) -> Dict[str, int]:
         """{applied, skipped, last_skipped, q_values_overflowed, verdict_timeouts} (synchronises
         the device)."""
@@ -501,21 +600,6 @@ class NativeDQN:
 
     def set_data_parallel_gate(self, enable: bool) -> None:
         check(lib().acme_dqn_set_data_parallel_gate(self._h, 1 if enable else 0), "dqn dp gate")
-
-    def get_params(self, which: str = "params") -> Dict[str, np.ndarray]:
-        flat = getattr(self, which)
-        return {k: v.detach().cpu().numpy().copy() for k, v in self.views(flat).items()}
-
-    @property
-    def num_steps(self) -> int:
-        return int(lib().acme_dqn_num_steps(self._h))
-
-    @num_steps.setter
-    def num_steps(self, n: int) -> None:
-        check(lib().acme_dqn_set_num_steps(self._h, int(n)))
-
-    def debug_buffer(self, name: str) -> np.ndarray:
-        return _debug_buffer(lib().acme_dqn_debug_buffer, self._h, name, self.device)
 
     # --------------------------------------------------------------- step
     def _batch(self, o_tm1, a_tm1, r_t, d_t, o_t, probabilities, global_min_probability=None,
@@ -669,18 +753,13 @@ def nccl_comm_destroy(comm: int) -> None:
     check(lib().acme_nccl_comm_destroy(ctypes.c_void_p(comm)), "nccl comm destroy")
 
 
-class _NativeActorCritic:
+class _NativeActorCritic(_NativeLearner):
     """The actor-critic learner handle shared by NativeD4PG, NativeDDPG and NativeMPO: flat
     buffers (policy tensors first, then critic tensors), batch validation, step, policy.
-    Subclasses name the C ABI prefix and the config struct, and fill the fields only they
-    have; NativeMPO has a step and a policy of its own."""
+    Subclasses name the C ABI prefix ("acme_d4pg" / "acme_ddpg" / "acme_mpo") and the config
+    struct, and fill the fields only they have; NativeMPO has a step and a policy of its own."""
 
-    _prefix = ""     # "acme_d4pg" / "acme_ddpg" / "acme_mpo"
-    _tag = ""        # error-message tag
     _config = None   # ctypes config struct
-
-    def _fn(self, name: str):
-        return getattr(lib(), f"{self._prefix}_{name}")
 
     def _setup(self, *, obs_dim, act_dim, max_batch, policy_sizes, critic_sizes, action_min,
                action_max, discount, target_update_period, policy_learning_rate,
@@ -715,50 +794,12 @@ class _NativeActorCritic:
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
         cfg.clipping = 1 if clipping else 0
         cfg.layer_norm_epsilon = layer_norm_epsilon
-        self.cfg = cfg
         self.obs_dim, self.act_dim, self.max_batch = int(obs_dim), int(act_dim), int(max_batch)
-        self.device = torch.device(device or "cuda")
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)), f"{self._tag} create")
-        self._h = h
-        self.flat_size = int(self._fn("flat_size")(h))
-        self.policy_size = int(self._fn("policy_size")(h))
-        self.tensors = _read_tensor_table(self._fn("num_tensors"), self._fn("tensor_info"), h)
+        self._create(cfg, device)
+        self.policy_size = int(self._fn("policy_size")(self._h))
         d = self.device
-        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=d)  # noqa: E731
-        self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
-        check(self._fn("bind")(h, ptr(self.params), ptr(self.target), ptr(self.grads),
-                               ptr(self.m), ptr(self.v)), f"{self._tag} bind")
         self.critic_loss = torch.zeros(1, dtype=torch.float32, device=d)
         self.policy_loss = torch.zeros(1, dtype=torch.float32, device=d)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                self._fn("destroy")(h)
-            except Exception:
-                pass
-            self._h = None
-
-    views = NativeDQN.views
-    set_params = NativeDQN.set_params
-    get_params = NativeDQN.get_params
-
-    def params_changed(self) -> None:  # the step reads the f32 buffers directly
-        pass
-
-    @property
-    def num_steps(self) -> int:
-        return int(self._fn("num_steps")(self._h))
-
-    @num_steps.setter
-    def num_steps(self, n: int) -> None:
-        check(self._fn("set_num_steps")(self._h, int(n)))
-
-    def debug_buffer(self, name: str) -> np.ndarray:
-        return _debug_buffer(self._fn("debug_buffer"), self._h, name, self.device)
 
     def _check_batch(self, o_tm1, a_tm1, r_t, d_t, o_t) -> int:
         """Validates the transition tensors every step takes; returns the batch size."""
@@ -950,8 +991,11 @@ class NativeMPO(_NativeActorCritic):
         return self.policy_distribution(obs, use_target, stream)[0]
 
 
-class NativeIMPALA:
+class NativeIMPALA(_PlaneState, _NativeLearner):
     """acme_impala learner + its flat buffers (no target network)."""
+
+    _prefix, _tag, _has_target = "acme_impala", "impala", False
+    plane_overflow = _plane_overflow
 
     def __init__(self, *, num_actions: int, max_batch: int, max_sequence_length: int,
                  torso: str = "atari", obs_dim: int = 0, lstm_size: int = 256,
@@ -980,73 +1024,14 @@ class NativeIMPALA:
         cfg.semantics = _lib.SEMANTICS_JAX if semantics == "jax" else _lib.SEMANTICS_TF
         cfg.learning_rate = learning_rate
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
-        self.cfg = cfg
         self.torso, self.obs_dim = torso, int(obs_dim)
         self.num_actions, self.lstm_size = int(num_actions), int(lstm_size)
         self.max_batch, self.max_sequence_length = int(max_batch), int(max_sequence_length)
-        self.device = torch.device(device or "cuda")
-        h = ctypes.c_void_p()
-        L = lib()
-        with torch.cuda.device(self.device):
-            check(L.acme_impala_create(ctypes.byref(cfg), ctypes.byref(h)), "impala create")
-        self._h = h
-        self.flat_size = int(L.acme_impala_flat_size(h))
-        self.tensors = _read_tensor_table(L.acme_impala_num_tensors, L.acme_impala_tensor_info, h)
-        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)  # noqa
-        if shared_params is not None:
-            if shared_params.numel() != self.flat_size or not shared_params.is_cuda:
-                raise ValueError("shared_params must be a device buffer of the same layout")
-            self.params = shared_params
-        else:
-            self.params = z()
-        self.grads, self.m, self.v = z(), z(), z()
-        check(L.acme_impala_bind(h, ptr(self.params), ptr(self.grads), ptr(self.m),
-                                 ptr(self.v)), "impala bind")
+        self._create(cfg, device, shared_params)
         self.metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().acme_impala_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    views = NativeDQN.views
-    get_params = NativeDQN.get_params
-
     def set_params(self, params: Dict[str, np.ndarray]) -> None:
-        for name, t in self.views(self.params).items():
-            t.copy_(torch.as_tensor(np.asarray(params[name], np.float32)).view(t.shape))
-        self.params_changed()
-
-    def params_changed(self) -> None:
-        """The bound parameters were written directly: plane scales recalibrate."""
-        check(lib().acme_impala_params_changed(self._h), "impala params_changed")
-
-    @property
-    def num_steps(self) -> int:
-        return int(lib().acme_impala_num_steps(self._h))
-
-    @num_steps.setter
-    def num_steps(self, n: int) -> None:
-        check(lib().acme_impala_set_num_steps(self._h, int(n)))
-
-    def debug_buffer(self, name: str) -> np.ndarray:
-        return _debug_buffer(lib().acme_impala_debug_buffer, self._h, name, self.device)
-
-    def plane_overflow(self, reset: bool = False) -> bool:
-        """As NativeDQN.plane_overflow, for the Atari torso's plane path."""
-        v = ctypes.c_int32(0)
-        check(lib().acme_impala_plane_overflow(self._h, ctypes.byref(v), int(reset)),
-              "impala plane_overflow")
-        return bool(v.value)
-
-    @property
-    def skipped_steps(self) -> int:
-        """Steps skipped (plane overflow or LSTM timeout) among those the device finished."""
-        return int(lib().acme_impala_skipped_steps(self._h))
+        super().set_params(params)
 
     def guard_state(self) -> Dict[str, int]:
         """{applied, skipped, last_skipped, lstm_timeouts} (synchronises the device)."""
@@ -1063,22 +1048,6 @@ class NativeIMPALA:
     def applied_steps(self, n: int) -> None:
         check(lib().acme_impala_set_applied_steps(self._h, int(n)), "impala set_applied_steps")
 
-    def scale_state(self) -> np.ndarray:
-        """The plane scales (learner state for checkpoints; empty without the plane path)."""
-        n = ctypes.c_int32(0)
-        check(lib().acme_impala_scale_state(self._h, None, 0, ctypes.byref(n)), "impala scales")
-        out = np.zeros(n.value, np.float32)
-        if n.value:
-            check(lib().acme_impala_scale_state(self._h, out.ctypes.data, n.value,
-                                                ctypes.byref(n)), "impala scales")
-        return out
-
-    def set_scale_state(self, state) -> None:
-        a = np.ascontiguousarray(np.asarray(state, np.float32))
-        if a.size:
-            check(lib().acme_impala_set_scale_state(self._h, a.ctypes.data, a.size),
-                  "impala set_scale_state")
-
     def set_policy_planes(self, on: bool = True) -> None:
         """Policy steps (>= 64 rows, Atari torso) on the plane engine: for actor-side networks
         that only run policy steps (acme_impala_set_policy_planes)."""
@@ -1092,29 +1061,8 @@ class NativeIMPALA:
              behaviour_logits, h0, c0, stream=None):
         """Batch-major [B, T, ...] device tensors; h0 / c0 are [B, H] views (any row stride
         that is a multiple of 4 floats, e.g. core_state[:, 0] of a [B, T, H] tensor)."""
-        B, T = int(action.shape[0]), int(action.shape[1])
-        want = torch.uint8 if self.torso == "atari" else torch.float32
-        checks = (("observation", observation, want), ("prev_action", prev_action, torch.int32),
-                  ("prev_reward", prev_reward, torch.float32), ("action", action, torch.int32),
-                  ("reward", reward, torch.float32), ("discount", discount, torch.float32),
-                  ("behaviour_logits", behaviour_logits, torch.float32))
-        for name, t, dt in checks:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
-                    and t.dtype == dt):
-                raise ValueError(f"{name} must be a contiguous {dt} device tensor")
-            if tuple(t.shape[:2]) != (B, T):
-                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {T}, ...]")
-        for name, t in (("h0", h0), ("c0", c0)):
-            if t.dtype != torch.float32 or t.shape != (B, self.lstm_size) or t.stride(1) != 1:
-                raise ValueError(f"{name} must be float32 [{B}, {self.lstm_size}] with unit "
-                                 "inner stride")
-        if h0.stride(0) != c0.stride(0):
-            raise ValueError("h0 and c0 must share a row stride")
-        b = _lib.SequenceBatch()
-        b.observation, b.prev_action, b.prev_reward = ptr(observation), ptr(prev_action), ptr(prev_reward)
-        b.action, b.reward, b.discount = ptr(action), ptr(reward), ptr(discount)
-        b.behaviour_logits, b.h0, b.c0 = ptr(behaviour_logits), ptr(h0), ptr(c0)
-        b.state_stride, b.batch, b.sequence_length = int(h0.stride(0)), B, T
+        b = self._sequence_batch(observation, prev_action, prev_reward, action, reward, discount,
+                                 h0, c0, behaviour_logits=behaviour_logits)
         check(lib().acme_impala_step(self._h, ctypes.byref(b), ptr(self.metrics),
                                      stream_ptr(stream)), "impala step")
 
@@ -1135,9 +1083,11 @@ class NativeIMPALA:
         return tuple(out)
 
 
-class NativeR2D2:
+class NativeR2D2(_PlaneState, _NativeLearner):
     """acme_r2d2 learner + its flat buffers (params, target, grads, Adam m / v):
     R2D2Learner._step (acme/agents/tf/r2d2/learning.py:112-200) on R2D2AtariNetwork."""
+
+    _prefix, _tag = "acme_r2d2", "r2d2"
 
     def __init__(self, *, num_actions: int, max_batch: int, max_sequence_length: int,
                  burn_in_length: int, torso: str = "atari", obs_dim: int = 0,
@@ -1163,24 +1113,12 @@ class NativeR2D2:
         cfg.max_priority_weight = max_priority_weight
         cfg.learning_rate = learning_rate
         cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
-        self.cfg = cfg
         self.torso, self.obs_dim = torso, int(obs_dim)
         self.num_actions, self.lstm_size = int(num_actions), int(lstm_size)
         self.max_batch, self.max_sequence_length = int(max_batch), int(max_sequence_length)
         self.burn_in_length = int(burn_in_length)
         self.store_lstm_state = bool(store_lstm_state)
-        self.device = torch.device(device or "cuda")
-        h = ctypes.c_void_p()
-        L = lib()
-        with torch.cuda.device(self.device):
-            check(L.acme_r2d2_create(ctypes.byref(cfg), ctypes.byref(h)), "r2d2 create")
-        self._h = h
-        self.flat_size = int(L.acme_r2d2_flat_size(h))
-        self.tensors = _read_tensor_table(L.acme_r2d2_num_tensors, L.acme_r2d2_tensor_info, h)
-        z = lambda: torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)  # noqa
-        self.params, self.target, self.grads, self.m, self.v = z(), z(), z(), z(), z()
-        check(L.acme_r2d2_bind(h, ptr(self.params), ptr(self.target), ptr(self.grads),
-                               ptr(self.m), ptr(self.v)), "r2d2 bind")
+        self._create(cfg, device)
         T, B = self.max_sequence_length, self.max_batch
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._errors = torch.zeros(max(T - self.burn_in_length - 1, 1) * B, dtype=torch.float32,
@@ -1194,49 +1132,8 @@ class NativeR2D2:
         tm, b = self._last
         return self._errors[:tm * b].view(tm, b)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().acme_r2d2_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    views = NativeDQN.views
-    get_params = NativeDQN.get_params
-
     def set_params(self, params: Dict[str, np.ndarray], target: Dict[str, np.ndarray]) -> None:
-        for buf, src in ((self.params, params), (self.target, target)):
-            for name, t in self.views(buf).items():
-                t.copy_(torch.as_tensor(np.asarray(src[name], np.float32)).view(t.shape))
-        self.params_changed()
-
-    def params_changed(self) -> None:
-        """The bound buffers were written directly: the plane scales recalibrate."""
-        check(lib().acme_r2d2_params_changed(self._h), "r2d2 params_changed")
-
-    @property
-    def skipped_steps(self) -> int:
-        """Steps skipped on plane overflow among those the device finished."""
-        return int(lib().acme_r2d2_skipped_steps(self._h))
-
-    def scale_state(self) -> np.ndarray:
-        """The plane scales (learner state for checkpoints; empty without the plane path)."""
-        n = ctypes.c_int32(0)
-        check(lib().acme_r2d2_scale_state(self._h, None, 0, ctypes.byref(n)), "r2d2 scales")
-        out = np.zeros(n.value, np.float32)
-        if n.value:
-            check(lib().acme_r2d2_scale_state(self._h, out.ctypes.data, n.value,
-                                              ctypes.byref(n)), "r2d2 scales")
-        return out
-
-    def set_scale_state(self, state) -> None:
-        """Restores scale_state() (after params_changed): resumed steps are bit-identical."""
-        a = np.ascontiguousarray(np.asarray(state, np.float32))
-        if a.size:
-            check(lib().acme_r2d2_set_scale_state(self._h, a.ctypes.data, a.size),
-                  "r2d2 set_scale_state")
+        super().set_params(params, target)
 
     def guard_state(self) -> Dict[str, int]:
         """{applied, skipped, last_skipped} (synchronises the device)."""
@@ -1252,20 +1149,9 @@ class NativeR2D2:
         """Device address of the step's skip word (gates the priority write-back), or None."""
         return lib().acme_r2d2_skip_word(self._h) or None
 
-    @property
-    def num_steps(self) -> int:
-        return int(lib().acme_r2d2_num_steps(self._h))
-
-    @num_steps.setter
-    def num_steps(self, n: int) -> None:
-        check(lib().acme_r2d2_set_num_steps(self._h, int(n)))
-
     def set_lstm_unroll(self, per_step: bool) -> None:
         """per_step=True: one LSTM launch per time step instead of the one-launch unroll."""
         check(lib().acme_r2d2_set_lstm_unroll(self._h, 1 if per_step else 0), "r2d2 lstm unroll")
-
-    def debug_buffer(self, name: str) -> np.ndarray:
-        return _debug_buffer(lib().acme_r2d2_debug_buffer, self._h, name, self.device)
 
     def step(self, observation, prev_action, prev_reward, action, reward, discount,
              probabilities, h0=None, c0=None, stream=None):
@@ -1274,37 +1160,12 @@ class NativeR2D2:
         sample's probabilities [B] (f64) and the core state at t = 0 (h0 / c0 [B, H] views
         with unit inner stride; ignored with store_lstm_state=False).  Loss, errors
         [T - burn_in - 1, B] and priorities [B] land in .loss / .errors / .priorities."""
-        B, T = int(action.shape[0]), int(action.shape[1])
-        want = torch.uint8 if self.torso == "atari" else torch.float32
-        checks = (("observation", observation, want), ("prev_action", prev_action, torch.int32),
-                  ("prev_reward", prev_reward, torch.float32), ("action", action, torch.int32),
-                  ("reward", reward, torch.float32), ("discount", discount, torch.float32))
-        for name, t, dt in checks:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
-                    and t.dtype == dt):
-                raise ValueError(f"{name} must be a contiguous {dt} device tensor")
-            if tuple(t.shape[:2]) != (B, T):
-                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {T}, ...]")
+        b = self._sequence_batch(observation, prev_action, prev_reward, action, reward, discount,
+                                 h0, c0, core_state=self.store_lstm_state)
+        B, T = int(b.batch), int(b.sequence_length)
         if not (probabilities.is_cuda and probabilities.dtype == torch.float64
                 and probabilities.is_contiguous() and probabilities.numel() == B):
             raise ValueError(f"probabilities must be a contiguous float64 [{B}] device tensor")
-        b = _lib.SequenceBatch()
-        b.observation, b.prev_action, b.prev_reward = ptr(observation), ptr(prev_action), ptr(prev_reward)
-        b.action, b.reward, b.discount = ptr(action), ptr(reward), ptr(discount)
-        b.behaviour_logits = None
-        if self.store_lstm_state:
-            for name, t in (("h0", h0), ("c0", c0)):
-                if (t is None or t.dtype != torch.float32 or t.shape != (B, self.lstm_size)
-                        or t.stride(1) != 1):
-                    raise ValueError(f"{name} must be float32 [{B}, {self.lstm_size}] with unit "
-                                     "inner stride")
-            if h0.stride(0) != c0.stride(0):
-                raise ValueError("h0 and c0 must share a row stride")
-            b.h0, b.c0, b.state_stride = ptr(h0), ptr(c0), int(h0.stride(0))
-        else:
-            b.h0 = b.c0 = None
-            b.state_stride = self.lstm_size
-        b.batch, b.sequence_length = B, T
         o = _lib.R2D2Outputs()
         o.loss, o.errors, o.priorities = ptr(self.loss), ptr(self._errors), ptr(self.priorities)
         self._last = (T - self.burn_in_length - 1, B)
