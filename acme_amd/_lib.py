@@ -124,6 +124,11 @@ class MPOConfig(ctypes.Structure):  # DDPGConfig without target_update_period, p
                 ("init_scale", c_f32), ("min_scale", c_f32), ("seed", ctypes.c_uint64)]
 
 
+class DMPOConfig(ctypes.Structure):  # acme_dmpo_config; the MPO fields are reachable directly
+    _anonymous_ = ("mpo",)
+    _fields_ = [("mpo", MPOConfig), ("num_atoms", c_i32), ("vmin", c_f32), ("vmax", c_f32)]
+
+
 class MPOBatch(ctypes.Structure):
     _fields_ = [("o_tm1", c_vp), ("a_tm1", c_vp), ("r_t", c_vp), ("d_t", c_vp), ("o_t", c_vp),
                 ("batch", c_i64), ("noise", c_vp)]
@@ -371,6 +376,23 @@ _SIGS = {
     "acme_mpo_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_mpo_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
                                       ctypes.POINTER(c_i64)]),
+    "acme_dmpo_create": (c_i32, [ctypes.POINTER(DMPOConfig), ctypes.POINTER(c_vp)]),
+    "acme_dmpo_destroy": (c_i32, [c_vp]),
+    "acme_dmpo_flat_size": (c_i64, [c_vp]),
+    "acme_dmpo_policy_size": (c_i64, [c_vp]),
+    "acme_dmpo_dual_offset": (c_i64, [c_vp]),
+    "acme_dmpo_num_tensors": (c_i32, [c_vp]),
+    "acme_dmpo_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(ctypes.c_char_p)]),
+    "acme_dmpo_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_dmpo_init_duals": (c_i32, [c_vp]),
+    "acme_dmpo_step": (c_i32, [c_vp, ctypes.POINTER(MPOBatch), ctypes.POINTER(MPOOutputs), c_vp]),
+    "acme_dmpo_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "acme_dmpo_num_steps": (c_i64, [c_vp]),
+    "acme_dmpo_set_num_steps": (c_i32, [c_vp, c_i64]),
+    "acme_dmpo_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
+                                       ctypes.POINTER(c_i64)]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),

@@ -26,6 +26,7 @@ import torch
 
 from acme_amd.agents.d4pg.learning import D4PGLearner, _learning_rate
 from acme_amd.native import NativeMPO
+from acme_amd.networks import LayerNormMLPCritic
 from acme_amd.utils import counting, loggers
 
 
@@ -52,6 +53,15 @@ class MPOLearner(D4PGLearner):
     the online distribution's mean."""
 
     _algorithm = "MPO"
+    checkpoint_subdirectory = "mpo_learner"  # the reference Checkpointer's (learning.py:113)
+    # What DistributionalMPOLearner replaces: the native handle, the critic descriptor it takes
+    # and the configuration that critic adds.
+    _native_type = NativeMPO
+    _critic_type = LayerNormMLPCritic
+
+    @staticmethod
+    def _critic_config(critic_network) -> Dict:
+        return {}
 
     def __init__(self, policy_network, critic_network, target_policy_network,
                  target_critic_network, discount: float, num_samples: int,
@@ -64,11 +74,17 @@ class MPOLearner(D4PGLearner):
                  batch_size: Optional[int] = None, seed: int = 0, device=None):
         B = self._check_networks(policy_network, critic_network, observation_network,
                                  target_observation_network, dataset, batch_size)
+        for net in (critic_network, target_critic_network):
+            if not isinstance(net, self._critic_type):
+                raise ValueError(f"acme_amd's {self._algorithm} learner takes a "
+                                 f"{self._critic_type.__name__} critic, not a "
+                                 f"{type(net).__name__}")
         loss = policy_loss_module or MPOLoss()
         if not isinstance(loss, MPOLoss):
             raise ValueError("policy_loss_module must be an acme_amd.agents.mpo.MPOLoss")
         self._policy_loss_module = loss
-        self._native = NativeMPO(
+        self._native = self._native_type(
+            **self._critic_config(critic_network),
             obs_dim=policy_network.obs_dim, act_dim=policy_network.act_dim, max_batch=B,
             policy_sizes=policy_network.layer_sizes, critic_sizes=critic_network.layer_sizes,
             num_samples=num_samples, discount=discount,

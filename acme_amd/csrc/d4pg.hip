@@ -18,7 +18,7 @@
 // activate_final); policy head NearZeroInitializedLinear + TanhToSpec
 // (rescaling.py:55-74); critic head DiscreteValuedHead (distributional.py:36-67).
 //
-// One learner core, three handle types.  acme_d4pg, acme_ddpg and acme_mpo derive from
+// One learner core, four handle types.  acme_d4pg, acme_ddpg, acme_mpo and acme_dmpo derive from
 // acme_actor_critic, whose Head says which step it takes; the flat-buffer layout, bind, the
 // step entry (checks, graph or eager, step count), the LayerNormMLP passes, the backward
 // launches, clip_and_adam and the debug-buffer lookup are written once over that core, and
@@ -35,6 +35,12 @@
 // the device, the scalar critic over those N B rows, the decoupled MPO loss and its dual
 // variables as a third parameter group.  Its kernels are in mpo_kernels.h, its step is
 // mpo_step_impl below.
+//
+// DMPO (acme_dmpo_*, acme/agents/tf/dmpo/learning.py:147-276) is Head::kMpoCategorical: MPO's
+// policy side and duals with D4PG's DiscreteValuedHead critic, the head run over the N B
+// sampled rows and the bootstrap distribution of each state the mixture of its N sampled
+// distributions (dmpo_mix_loss_kernel, mpo_kernels.h).  Its step is dmpo_step_impl, built from
+// the blocks of mpo_step_impl and the categorical head's backward of d4pg_step_impl.
 //
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
@@ -94,11 +100,19 @@ enum class Head {
   kCategorical,  // D4PG: DiscreteValuedHead, categorical projection loss
   kScalar,       // DDPG: one scalar, TD loss
   kMpo,          // MPO: scalar critic, Gaussian policy head, the dual variables
+  kMpoCategorical,  // DMPO: MPO's policy side, D4PG's DiscreteValuedHead critic
 };
+
+// The kinds with a Gaussian policy head, sampled actions and dual variables (MPO's policy side).
+constexpr bool has_duals(Head h) { return h == Head::kMpo || h == Head::kMpoCategorical; }
+// The kinds whose critic ends in a DiscreteValuedHead over the support `values`.
+constexpr bool is_categorical(Head h) {
+  return h == Head::kCategorical || h == Head::kMpoCategorical;
+}
 
 }  // namespace
 
-// The learner behind the three handle types of this file (below): the LayerNormMLP policy and
+// The learner behind the four handle types of this file (below): the LayerNormMLP policy and
 // critic in one flat buffer, their workspaces and the captured step graphs.
 struct acme_actor_critic {
   virtual ~acme_actor_critic() = default;
@@ -141,11 +155,15 @@ struct acme_actor_critic {
     float *noise, *act;                   // [N B][A] eps used, sampled actions
     float *cost, *tiled;                  // [N B] out-of-bound cost, [N B][obs] o_t tiled N times
     float *w, *pw;                        // [N B] normalized weights, penalty weights
-    float *qt;                            // [B] mean_n of the sampled target values (ctg.out)
+    float *sq;                            // [N B] sampled target values (MPO: ctg.out itself)
+    float *qt;                            // [B] mean_n of the sampled target values
     float *dmean, *dpre;                  // [B][A] dloss / d(online mean, pre-softplus scale)
     float *part;                          // [ceil(B / 4)][kMpoCols] per-block sums of the loss kernel
     float *stats, *klm_rel, *kls_rel, *ploss;  // outputs when the caller passes none
   } mb = {};
+  // DMPO (acme_dmpo_create): the categorical head over the N B sampled rows (ctg.out holds
+  // their logits, mb.sq their means) and the bootstrap mixture of each state.
+  float* mixture = nullptr;               // [B][atoms] normalised mixture probabilities
   // Captured step graphs, keyed by the batch / output pointers, B and the target copies.
   struct Graph {
     const void* key[kGraphKeys];
@@ -162,6 +180,7 @@ struct acme_actor_critic {
 struct acme_d4pg : acme_actor_critic {};
 struct acme_ddpg : acme_actor_critic {};
 struct acme_mpo : acme_actor_critic {};
+struct acme_dmpo : acme_actor_critic {};
 
 namespace {
 
@@ -461,32 +480,34 @@ __global__ void __launch_bounds__(256) policy_head_kernel(const PolicyHeadPair p
 //               written exactly as l2_project (:44-83); dlogits = (softmax - target) / B,
 //               ce[row] = cross-entropy (summed into the loss by adam_clip_kernel).
 //   rows >= B : dpg rows; q = sum softmax * values, dq/dlogits = (values - q) * softmax.
-// The loss math of one row from its logits in registers (ql: the online critic's, tl: the
-// target critic's, lane = atom, -inf past K).
-__device__ __forceinline__ void loss_row(float ql, float tl, int row, int lane,
-                                         const float* __restrict__ r, const float* __restrict__ d,
-                                         const float* __restrict__ values, int B, int K,
-                                         float discount, float* __restrict__ dlogits,
-                                         float* __restrict__ ce_out) {
+// The softmax of one row of logits in registers (lane = atom, -inf past K): its maximum, the
+// sum of the exponentials and the lane's probability.
+struct RowSoftmax {
+  float m, s, p;
+};
+__device__ __forceinline__ RowSoftmax row_softmax(float x, bool on) {
+  RowSoftmax o;
+  o.m = wave_max(x);
+  const float e = on ? expf(x - o.m) : 0.f;
+  o.s = wave_sum(e);
+  o.p = e / o.s;
+  return o;
+}
+
+// The categorical loss of row `row` < B from the online critic's logits ql with their softmax
+// q and the target probabilities pj (lane = atom; D4PG: the target critic's softmax, DMPO: the
+// mixture over the sampled actions): l2_project, the cross entropy and dlogits.
+__device__ __forceinline__ void categorical_loss_row(
+    float ql, const RowSoftmax& q, float pj, float vi, int row, int lane,
+    const float* __restrict__ r, const float* __restrict__ d, const float* __restrict__ values,
+    int B, int K, float discount, float* __restrict__ dlogits, float* __restrict__ ce_out) {
   const bool on = lane < K;
-  const float vi = on ? values[lane] : 0.f;
-  const float m2 = wave_max(ql);
-  const float e2 = on ? expf(ql - m2) : 0.f;
-  const float s2 = wave_sum(e2);
-  const float sm = e2 / s2;
-  if (row >= B) {
-    const float q = wave_sum(on ? sm * vi : 0.f);
-    if (on) dlogits[(size_t)row * K + lane] = (vi - q) * sm;
-    return;
-  }
+  const float m2 = q.m, s2 = q.s, sm = q.p;
   const float vmin = values[0], vmax = values[K - 1];
   // Support spacings of l2_project: d_pos = Zq[i+1] - Zq[i] (wrapping to vmin), d_neg =
   // Zq[i] - Zq[i-1] (wrapping to vmax).
   const float dpos = on ? ((lane + 1 < K ? values[lane + 1] : vmin) - vi) : 1.f;
   const float dneg = on ? (vi - (lane > 0 ? values[lane - 1] : vmax)) : 1.f;
-  const float mx = wave_max(tl);
-  const float e = on ? expf(tl - mx) : 0.f;
-  const float pj = e / wave_sum(e);
   const float gd = discount * d[row];
   const float zc = fminf(fmaxf(r[row] + gd * vi, vmin), vmax);
   // delta_hat = (sg dq) / d_pos - ((1 - sg) dq) / d_neg with sg = (dq >= 0): one of the two
@@ -504,6 +525,25 @@ __device__ __forceinline__ void loss_row(float ql, float tl, int row, int lane,
   const float ce = wave_sum(on ? -tgt * logp : 0.f);
   if (on) dlogits[(size_t)row * K + lane] = (1.f / (float)B) * (sm - tgt);
   if (lane == 0) ce_out[row] = ce;
+}
+
+// The loss math of one D4PG row from its logits in registers (ql: the online critic's, tl: the
+// target critic's, lane = atom, -inf past K).
+__device__ __forceinline__ void loss_row(float ql, float tl, int row, int lane,
+                                         const float* __restrict__ r, const float* __restrict__ d,
+                                         const float* __restrict__ values, int B, int K,
+                                         float discount, float* __restrict__ dlogits,
+                                         float* __restrict__ ce_out) {
+  const bool on = lane < K;
+  const float vi = on ? values[lane] : 0.f;
+  const RowSoftmax q = row_softmax(ql, on);
+  if (row >= B) {
+    const float qv = wave_sum(on ? q.p * vi : 0.f);
+    if (on) dlogits[(size_t)row * K + lane] = (vi - qv) * q.p;
+    return;
+  }
+  const RowSoftmax t = row_softmax(tl, on);
+  categorical_loss_row(ql, q, t.p, vi, row, lane, r, d, values, B, K, discount, dlogits, ce_out);
 }
 
 __global__ void __launch_bounds__(256) d4pg_loss_kernel(
@@ -1283,17 +1323,13 @@ void set_gauss_head(const acme_actor_critic* l, GaussHeadPair& p, int i, const f
 // The policy head's input gradient is formed by the loss kernel (its two linears' weight
 // gradients ride the first policy backward launch), and the policy's backward runs before
 // the critic's so that no launch carries more than kZ weight gradients.
-int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
-                  int copy, hipStream_t st) {
-  const acme_mpo_config& mc = l->mcfg;
-  const int B = (int)bt->batch, N = mc.num_samples, NB = N * B;
-  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
-  const int D = mc.per_dim_constraining ? ad : 1;
-  const NetDesc& pd = l->pol;
-  const NetDesc& cd = l->cri;
-  const int pL = pd.nl - 1, cL = cd.nl - 1;
-  auto& mb = l->mb;
-  int rc;
+//
+// The blocks MPO's step shares with DMPO's (dmpo_step_impl) are functions of their own: the
+// target copies, the policy side up to the sampled actions, the MPO loss with the duals, and
+// the policy backward.
+
+// The two start-of-step target copies: bit 0 of `copy` the policy, bit 1 the critic.
+int mpo_target_copies(acme_actor_critic* l, int copy, hipStream_t st) {
   if (copy & 1) {
     ACME_PROF("mpo_target_copy", st, 0.0, 2.0 * 4.0 * (double)l->policy_flat);
     ACME_HIP_TRY(hipMemcpyAsync(l->target, l->params, (size_t)l->policy_flat * sizeof(float),
@@ -1305,7 +1341,19 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
                                 (size_t)(l->critic_end - l->policy_flat) * sizeof(float),
                                 hipMemcpyDeviceToDevice, st));
   }
-  const float scale_mul = mpo_scale_mul(l);
+  return ACME_OK;
+}
+
+// The online and the target policy on o_t with their Gaussian heads, then N actions per state
+// from the target policy, their out-of-bound cost and o_t tiled N times.
+int mpo_policy_and_sample(acme_actor_critic* l, const acme_mpo_batch* bt, hipStream_t st) {
+  const acme_mpo_config& mc = l->mcfg;
+  const int B = (int)bt->batch, N = mc.num_samples, NB = N * B;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const NetDesc& pd = l->pol;
+  const int pL = pd.nl - 1;
+  auto& mb = l->mb;
+  int rc;
   {
     const NetIn pin[2] = {{l->params, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->pon},
                           {l->target, bt->o_t, nullptr, bt->o_t, nullptr, B, B, &l->ptg}};
@@ -1327,23 +1375,21 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
     mpo_sample_kernel<<<(unsigned)ceil_div(NB, 256), 256, 0, st>>>(a);
     ACME_LAUNCH_CHECK();
   }
-  {
-    const NetIn cin[2] = {{l->params, bt->o_tm1, bt->a_tm1, bt->o_tm1, bt->a_tm1, B, B, &l->con},
-                          {l->target, mb.tiled, mb.act, mb.tiled, mb.act, NB, NB, &l->ctg}};
-    if ((rc = lnmlp_forward_pair(l, cd, cin, od, ad, "mpo_critic_ln", st))) return rc;
-  }
-  {
-    ACME_PROF("mpo_head_td", st, 2.0 * (NB + 2.0 * B) * (double)cd.sizes[cL], 0.0);
-    MpoHeadTdArgs a;
-    a.h = l->con.h[cL]; a.w = P(l, l->params, cd.ow); a.b = P(l, l->params, cd.ob);
-    a.th = l->ctg.h[cL]; a.tw = P(l, l->target, cd.ow); a.tb = P(l, l->target, cd.ob);
-    a.r = bt->r_t; a.d = bt->d_t;
-    a.B = B; a.N = N; a.H = cd.sizes[cL]; a.act = act_of_layer(cL); a.discount = l->cfg.discount;
-    a.q = l->con.out; a.sq = l->ctg.out; a.qt = mb.qt; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
-    a.dz = l->cdz[cL];
-    mpo_head_td_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
-    ACME_LAUNCH_CHECK();
-  }
+  return ACME_OK;
+}
+
+// The MPO loss over the sampled values mb.sq with its backward into the policy head (dz[pL],
+// dmean, dpre), then the dual gradients, the stats and the duals' Adam.
+int mpo_loss_and_duals(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
+                       hipStream_t st) {
+  const acme_mpo_config& mc = l->mcfg;
+  const int B = (int)bt->batch, N = mc.num_samples;
+  const int ad = l->cfg.act_dim;
+  const int D = mc.per_dim_constraining ? ad : 1;
+  const NetDesc& pd = l->pol;
+  const int pL = pd.nl - 1;
+  auto& mb = l->mb;
+  const float scale_mul = mpo_scale_mul(l);
   const int nblk = (int)ceil_div(B, 4);
   float* stats = out && out->stats ? out->stats : mb.stats;
   float* klm_rel = out && out->kl_mean_rel ? out->kl_mean_rel : mb.klm_rel;
@@ -1351,7 +1397,7 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
   {
     ACME_PROF("mpo_loss", st, 0.0, 0.0);
     MpoLossArgs a;
-    a.sq = l->ctg.out; a.cost = mb.cost; a.act = mb.act;
+    a.sq = mb.sq; a.cost = mb.cost; a.act = mb.act;
     a.mu_on = l->pon.out; a.sd_on = mb.sd_on; a.pre_on = l->pon.t;
     a.mu_t = l->ptg.out; a.sd_t = mb.sd_t;
     a.log_temp = P(l, l->params, l->t_temp); a.log_amean = P(l, l->params, l->t_amean);
@@ -1382,16 +1428,57 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
     mpo_finalize_kernel<<<1, 256, 0, st>>>(a);
     ACME_LAUNCH_CHECK();
   }
-  BwdGroup g;
-  std::vector<LnReduce> ln;
-  // Policy backward from dz[pL] (written by the loss kernel).
+  return ACME_OK;
+}
+
+// Policy backward from dz[pL] (written by the loss kernel); leaves the first layer's weight
+// gradient in `g` for the critic's first backward launch.
+int mpo_policy_backward(acme_actor_critic* l, const acme_mpo_batch* bt, BwdGroup& g,
+                        std::vector<LnReduce>& ln, hipStream_t st) {
+  const int B = (int)bt->batch, od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const NetDesc& pd = l->pol;
+  const int pL = pd.nl - 1;
+  auto& mb = l->mb;
+  int rc;
   add_wgrad(g, l->pon.h[pL], B, pd.sizes[pL], mb.dmean, ad, Pm(l, l->grads, pd.ow),
             Pm(l, l->grads, pd.ob));
   add_wgrad(g, l->pon.h[pL], B, pd.sizes[pL], mb.dpre, ad, Pm(l, l->grads, l->sw),
             Pm(l, l->grads, l->sb));
-  if ((rc = lnmlp_backward_mlp(l, pd, l->pon, l->pdz, B, B, g, "mpo_bwd_phead", st, true)) ||
-      (rc = ln_backward(l, pd, l->pon, l->pdz[0], B, B, false, bt->o_t, nullptr, od, 0,
-                        l->lnslab2, g, ln, st)))
+  if ((rc = lnmlp_backward_mlp(l, pd, l->pon, l->pdz, B, B, g, "mpo_bwd_phead", st, true)))
+    return rc;
+  return ln_backward(l, pd, l->pon, l->pdz[0], B, B, false, bt->o_t, nullptr, od, 0, l->lnslab2,
+                     g, ln, st);
+}
+
+int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
+                  int copy, hipStream_t st) {
+  const int B = (int)bt->batch, N = l->mcfg.num_samples, NB = N * B;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const NetDesc& cd = l->cri;
+  const int cL = cd.nl - 1;
+  auto& mb = l->mb;
+  int rc;
+  if ((rc = mpo_target_copies(l, copy, st)) || (rc = mpo_policy_and_sample(l, bt, st))) return rc;
+  {
+    const NetIn cin[2] = {{l->params, bt->o_tm1, bt->a_tm1, bt->o_tm1, bt->a_tm1, B, B, &l->con},
+                          {l->target, mb.tiled, mb.act, mb.tiled, mb.act, NB, NB, &l->ctg}};
+    if ((rc = lnmlp_forward_pair(l, cd, cin, od, ad, "mpo_critic_ln", st))) return rc;
+  }
+  {
+    ACME_PROF("mpo_head_td", st, 2.0 * (NB + 2.0 * B) * (double)cd.sizes[cL], 0.0);
+    MpoHeadTdArgs a;
+    a.h = l->con.h[cL]; a.w = P(l, l->params, cd.ow); a.b = P(l, l->params, cd.ob);
+    a.th = l->ctg.h[cL]; a.tw = P(l, l->target, cd.ow); a.tb = P(l, l->target, cd.ob);
+    a.r = bt->r_t; a.d = bt->d_t;
+    a.B = B; a.N = N; a.H = cd.sizes[cL]; a.act = act_of_layer(cL); a.discount = l->cfg.discount;
+    a.q = l->con.out; a.sq = mb.sq; a.qt = mb.qt; a.td = l->td; a.dq = l->dq; a.loss = l->ce;
+    a.dz = l->cdz[cL];
+    mpo_head_td_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+  }
+  BwdGroup g;
+  std::vector<LnReduce> ln;
+  if ((rc = mpo_loss_and_duals(l, bt, out, st)) || (rc = mpo_policy_backward(l, bt, g, ln, st)))
     return rc;
   // Critic backward over the B TD rows; the head's weight gradient (one live column) and the
   // policy's first-layer weight gradient ride its first launch.
@@ -1403,6 +1490,64 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
   // The duals' floats past critic_end are the finalize kernel's.
+  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, out ? out->policy_loss : nullptr,
+                       out ? out->critic_loss : nullptr, st);
+}
+
+// DistributionalMPOLearner._step (acme/agents/tf/dmpo/learning.py:147-276) on one stream: MPO's
+// step with D4PG's categorical critic.
+//   target copies, policy side, sampling: MPO's blocks                             (:161-204)
+//   online critic on [o_tm1, a_tm1] (B rows), target critic on the N B samples, the
+//     DiscreteValuedHead of both in one launch (B and N B rows)                    (:207-224)
+//   dmpo_mix_loss_kernel: sampled q, the bootstrap mixture of each state, the categorical
+//     loss and dlogits of the B online rows                                        (:212-233)
+//   MPO loss and duals, policy backward: MPO's blocks                              (:236-240)
+//   critic backward as D4PG's over the B rows (no dpg rows), clipping, two Adams   (:252-267)
+// Launches at B = 256, N = 20, policy 256x3, critic 512/512/256, no target copy: policy 3 + 1,
+// sample 1, critic 3 + 1 head, mixture loss 1, MPO loss 2, policy backward 2 + 1, critic
+// backward 1 + 2 + 1 + 1, clipping and Adam 2: 22, two more than MPO's 20 (the head GEMM pair
+// and the head's backward launch; the mixture kernel stands where mpo_head_td_kernel stood,
+// which also wrote the scalar head's input gradient).
+int dmpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
+                   int copy, hipStream_t st) {
+  const int B = (int)bt->batch, N = l->mcfg.num_samples, NB = N * B;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const NetDesc& cd = l->cri;
+  const int cL = cd.nl - 1, K = cd.nout;
+  auto& mb = l->mb;
+  int rc;
+  if ((rc = mpo_target_copies(l, copy, st)) || (rc = mpo_policy_and_sample(l, bt, st))) return rc;
+  {
+    const NetIn cin[2] = {{l->params, bt->o_tm1, bt->a_tm1, bt->o_tm1, bt->a_tm1, B, B, &l->con},
+                          {l->target, mb.tiled, mb.act, mb.tiled, mb.act, NB, NB, &l->ctg}};
+    if ((rc = critic_forward_pair(l, cin, st))) return rc;
+  }
+  {
+    ACME_PROF("dmpo_mix_loss", st, 0.0, 4.0 * (double)K * (NB + 3.0 * B));
+    DmpoMixArgs a;
+    a.c_logits = l->con.out; a.t_logits = l->ctg.out;
+    a.r = bt->r_t; a.d = bt->d_t; a.values = l->values;
+    a.B = B; a.N = N; a.K = K; a.discount = l->cfg.discount;
+    a.sq = mb.sq; a.mix = l->mixture; a.dlogits = l->dlogits; a.ce = l->ce;
+    dmpo_mix_loss_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+  }
+  BwdGroup g;
+  std::vector<LnReduce> ln;
+  // The policy's backward first, as in MPO: no launch carries more than kZ weight gradients.
+  if ((rc = mpo_loss_and_duals(l, bt, out, st)) || (rc = mpo_policy_backward(l, bt, g, ln, st)))
+    return rc;
+  // Critic backward over the B rows: the head's launch (its weight and input gradients) also
+  // carries the policy's first-layer weight gradient.
+  add_wgrad(g, l->con.h[cL], B, cd.sizes[cL], l->dlogits, K, Pm(l, l->grads, cd.ow),
+            Pm(l, l->grads, cd.ob));
+  add_dgrad(g, l->dlogits, B, K, P(l, l->params, cd.ow), cd.sizes[cL], l->con.h[cL],
+            act_of_layer(cL), l->cdz[cL]);
+  if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, B, B, g, "dmpo_bwd_chead", st, false)) ||
+      (rc = ln_backward(l, cd, l->con, l->cdz[0], B, B, false, bt->o_tm1, bt->a_tm1, od, ad,
+                        l->lnslab, g, ln, st)) ||
+      (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
+    return rc;
   return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, out ? out->policy_loss : nullptr,
                        out ? out->critic_loss : nullptr, st);
 }
@@ -1484,7 +1629,7 @@ int run_step(acme_actor_critic* l, const char* api, const Batch* batch,
 }
 
 // ------------------------------------------------------------------ the shared learner
-// The bodies behind the acme_d4pg_*, acme_ddpg_* and acme_mpo_* exports.
+// The bodies behind the acme_d4pg_*, acme_ddpg_*, acme_mpo_* and acme_dmpo_* exports.
 
 int ac_destroy(acme_actor_critic* l) {
   if (!l) return ACME_OK;
@@ -1501,7 +1646,7 @@ int check_config(const acme_d4pg_config* cfg, Head head) {
                  "obs_dim + act_dim must be in [2, %d]", kMaxIn);
   ACME_CHECK_ARG(cfg->act_dim <= ACME_D4PG_MAX_ACT, "act_dim must be <= %d", ACME_D4PG_MAX_ACT);
   ACME_CHECK_ARG(cfg->max_batch >= 1 && cfg->max_batch <= 65536, "max_batch must be in [1, 65536]");
-  if (head == Head::kCategorical) {
+  if (is_categorical(head)) {
     ACME_CHECK_ARG(cfg->num_atoms >= 2 && cfg->num_atoms <= ACME_D4PG_MAX_ATOMS,
                    "num_atoms must be in [2, %d]", ACME_D4PG_MAX_ATOMS);
     ACME_CHECK_ARG(cfg->vmax > cfg->vmin, "vmax must exceed vmin");
@@ -1522,7 +1667,8 @@ int check_config(const acme_d4pg_config* cfg, Head head) {
 }
 
 // Lays out the tensors and allocates the workspaces of a fresh learner.  Head::kScalar and
-// Head::kMpo come with cfg->num_atoms = 1 (the support unused); Head::kMpo with `mpo`.
+// Head::kMpo come with cfg->num_atoms = 1 (the support unused); Head::kMpo and
+// Head::kMpoCategorical with `mpo`.
 int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
                  const acme_mpo_config* mpo) {
   l->cfg = *cfg;
@@ -1538,7 +1684,7 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
   l->policy_flat = l->flat;
   add_net(l, l->cri, "critic", cfg->obs_dim + cfg->act_dim, cfg->num_critic_layers,
           cfg->critic_sizes, cfg->num_atoms,
-          head == Head::kCategorical ? "discrete_valued_head/linear" : nullptr);
+          is_categorical(head) ? "discrete_valued_head/linear" : nullptr);
   l->critic_end = l->flat;
   if (mpo) {
     l->mcfg = *mpo;
@@ -1574,6 +1720,13 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
       return rc;
     if (hipMemset(mb.pw, 0, (size_t)NB * sizeof(float)) != hipSuccess)
       return (set_error("hipMemset failed"), ACME_ERR_HIP);
+    // MPO's scalar head writes the sampled values where DMPO's head writes the N B x K logits
+    // (ctg.out, sized by alloc_acts); DMPO keeps the values, and the mixtures, beside them.
+    mb.sq = l->ctg.out;
+    if (head == Head::kMpoCategorical &&
+        ((rc = dev_alloc(l, &mb.sq, NB)) ||
+         (rc = dev_alloc(l, &l->mixture, (int64_t)B * cfg->num_atoms))))
+      return rc;
   }
   for (int i = 0; i < l->cri.nl; ++i)
     if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return rc;
@@ -1593,7 +1746,7 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
       (rc = dev_alloc(l, &l->norms, 2)) || (rc = dev_alloc(l, &l->loss_tmp, 2)) ||
       (rc = dev_alloc(l, &l->ce, B)) || (rc = dev_alloc(l, &l->dev_step, 1)))
     return rc;
-  if (head != Head::kCategorical &&
+  if (!is_categorical(head) &&
       ((rc = dev_alloc(l, &l->td, B)) || (rc = dev_alloc(l, &l->dq, 2 * B))))
     return rc;
   // Support: tf.linspace(vmin, vmax, K) (computed in f64, rounded once to f32).
@@ -1612,7 +1765,7 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
   return ACME_OK;
 }
 
-// A learner of handle type L (acme_d4pg, acme_ddpg, acme_mpo) with the given head kind.
+// A learner of handle type L (acme_d4pg, acme_ddpg, acme_mpo, acme_dmpo) with the given head kind.
 template <class L>
 int create_learner(const acme_d4pg_config* cfg, Head head, const acme_mpo_config* mpo, L** out) {
   int rc = check_config(cfg, head);
@@ -1685,6 +1838,7 @@ int d4pg_step(acme_actor_critic* l, const acme_d4pg_batch* batch, const acme_d4p
               void* stream) {
   ACME_CHECK_ARG(l && batch, "null argument");
   ACME_CHECK_ARG(l->head != Head::kMpo, "an MPO learner steps through acme_mpo_step");
+  ACME_CHECK_ARG(l->head != Head::kMpoCategorical, "a DMPO learner steps through acme_dmpo_step");
   const bool copy = l->num_steps % l->cfg.target_update_period == 0;
   const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
                                  batch->o_t, out ? out->critic_loss : nullptr,
@@ -1741,6 +1895,27 @@ int ac_debug_buffer(const acme_actor_critic* l, const char* name, const float** 
   }
   const int64_t NB = B * l->mcfg.num_samples;
   const auto& mb = l->mb;
+  if (l->head == Head::kMpoCategorical) {
+    for (const char* scalar_only : {"q_tm1", "q_t", "td", "dq"})
+      if (strcmp(name, scalar_only) == 0) {
+        set_error("debug buffer '%s' is the scalar critic's: a DMPO learner has logits_tm1, "
+                  "sampled_logits, mixture, dlogits and ce", name);
+        return ACME_ERR_INVALID;
+      }
+    const DebugItem items[] = {
+        {"mean_on", l->pon.out, B * A}, {"std_on", mb.sd_on, B * A}, {"pre_on", l->pon.t, B * A},
+        {"mean_t", l->ptg.out, B * A},  {"std_t", mb.sd_t, B * A},   {"noise", mb.noise, NB * A},
+        {"actions", mb.act, NB * A},    {"cost", mb.cost, NB},       {"sampled_q", mb.sq, NB},
+        {"weights", mb.w, NB},          {"penalty_weights", mb.pw, NB},
+        {"logits_tm1", l->con.out, B * K}, {"sampled_logits", l->ctg.out, NB * K},
+        {"mixture", l->mixture, B * K}, {"dlogits", l->dlogits, B * K}, {"ce", l->ce, B},
+        {"dmean", mb.dmean, B * A},     {"dpre", mb.dpre, B * A},
+        {"norms", l->norms, 2},         {"losses", l->loss_tmp, 2},
+        {"stats", mb.stats, ACME_MPO_NUM_STATS},
+        {"kl_mean_rel", mb.klm_rel, A}, {"kl_stddev_rel", mb.kls_rel, A},
+    };
+    return find_debug_buffer(items, name, out, count);
+  }
   const DebugItem items[] = {
       {"mean_on", l->pon.out, B * A}, {"std_on", mb.sd_on, B * A}, {"pre_on", l->pon.t, B * A},
       {"mean_t", l->ptg.out, B * A},  {"std_t", mb.sd_t, B * A},   {"noise", mb.noise, NB * A},
@@ -1753,6 +1928,101 @@ int ac_debug_buffer(const acme_actor_critic* l, const char* name, const float** 
       {"kl_mean_rel", mb.klm_rel, A}, {"kl_stddev_rel", mb.kls_rel, A},
   };
   return find_debug_buffer(items, name, out, count);
+}
+
+// The bodies behind the acme_mpo_* and acme_dmpo_* exports that only those two kinds have.
+
+// What acme_mpo_create checks of the fields that MPO adds to the shared configuration.
+int check_mpo_config(const acme_mpo_config* cfg) {
+  ACME_CHECK_ARG(cfg->num_samples >= 1 && cfg->num_samples <= ACME_MPO_MAX_SAMPLES,
+                 "num_samples must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
+  // The target critic runs max_batch * num_samples rows through the GEMM engine and the
+  // LayerNorm row kernels, which take what D4PG's 2 * 65536 rows ask of them.
+  ACME_CHECK_ARG(cfg->max_batch >= 1 &&
+                     (int64_t)cfg->max_batch * cfg->num_samples <= ACME_MPO_MAX_ROWS,
+                 "max_batch * num_samples must be in [1, %d]", ACME_MPO_MAX_ROWS);
+  ACME_CHECK_ARG(cfg->target_policy_update_period >= 1 && cfg->target_critic_update_period >= 1,
+                 "target update periods must be >= 1");
+  ACME_CHECK_ARG(cfg->epsilon > 0.f && cfg->epsilon_mean > 0.f && cfg->epsilon_stddev > 0.f &&
+                     cfg->epsilon_penalty > 0.f,
+                 "the KL bounds (epsilon*) must be positive");
+  ACME_CHECK_ARG(cfg->init_scale > 0.f && cfg->min_scale >= 0.f,
+                 "init_scale must be positive and min_scale non-negative");
+  return ACME_OK;
+}
+
+int mpo_init_duals(acme_actor_critic* l) {
+  ACME_CHECK_ARG(l && has_duals(l->head), "not an MPO or DMPO learner");
+  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
+  ACME_HIP_TRY(hipDeviceSynchronize());
+  const acme_mpo_config& mc = l->mcfg;
+  const std::pair<int, float> init[] = {{l->t_temp, mc.init_log_temperature},
+                                        {l->t_amean, mc.init_log_alpha_mean},
+                                        {l->t_astd, mc.init_log_alpha_stddev},
+                                        {l->t_ptemp, mc.init_log_temperature}};
+  for (const auto& it : init) {
+    if (it.first < 0) continue;
+    const Tensor& t = l->tensors[it.first];
+    const std::vector<float> v((size_t)t.numel, it.second);
+    ACME_HIP_TRY(hipMemcpy(l->params + t.offset, v.data(), v.size() * sizeof(float),
+                           hipMemcpyHostToDevice));
+  }
+  return ACME_OK;
+}
+
+// acme_mpo_step (head = Head::kMpo) and acme_dmpo_step (Head::kMpoCategorical): a handle of
+// the other kind is refused with the name of its own entry.
+int mpo_step(acme_actor_critic* l, Head head, const acme_mpo_batch* batch,
+             const acme_mpo_outputs* out, void* stream) {
+  ACME_CHECK_ARG(l && batch, "null argument");
+  if (l->head != head) {
+    set_error(l->head == Head::kMpo               ? "an MPO learner steps through acme_mpo_step"
+              : l->head == Head::kMpoCategorical ? "a DMPO learner steps through acme_dmpo_step"
+              : head == Head::kMpo                ? "not an MPO learner"
+                                                  : "not a DMPO learner");
+    return ACME_ERR_INVALID;
+  }
+  const int copy = (l->num_steps % l->mcfg.target_policy_update_period == 0 ? 1 : 0) |
+                   (l->num_steps % l->mcfg.target_critic_update_period == 0 ? 2 : 0);
+  const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                 batch->o_t, batch->noise,
+                                 out ? out->critic_loss : nullptr,
+                                 out ? out->policy_loss : nullptr,
+                                 out ? out->stats : nullptr,
+                                 out ? out->kl_mean_rel : nullptr,
+                                 out ? out->kl_stddev_rel : nullptr};
+  if (head == Head::kMpo)
+    return run_step(l, "acme_mpo", batch, key, copy, stream,
+                    [&](hipStream_t s) { return mpo_step_impl(l, batch, out, copy, s); });
+  return run_step(l, "acme_dmpo", batch, key, copy, stream,
+                  [&](hipStream_t s) { return dmpo_step_impl(l, batch, out, copy, s); });
+}
+
+int mpo_policy(acme_actor_critic* l, const float* obs, int64_t rows, int32_t use_target,
+               float* mean_out, float* stddev_out, void* stream) {
+  ACME_CHECK_ARG(l && obs && mean_out && stddev_out, "null argument");
+  ACME_CHECK_ARG(has_duals(l->head), "not an MPO or DMPO learner");
+  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
+  ACME_CHECK_ARG(rows >= 0, "negative row count");
+  hipStream_t st = as_stream(stream);
+  const int B = l->cfg.max_batch, A = l->cfg.act_dim;
+  const NetDesc& pd = l->pol;
+  const float* prm = use_target ? l->target : l->params;
+  for (int64_t r0 = 0; r0 < rows; r0 += B) {
+    const int n = (int)std::min<int64_t>(B, rows - r0);
+    const float* o = obs + r0 * l->cfg.obs_dim;
+    const NetIn in[2] = {{prm, o, nullptr, o, nullptr, n, n, &l->ptg},
+                         {l->params, o, nullptr, o, nullptr, n, 0, &l->ptg}};
+    int rc = lnmlp_forward_pair(l, pd, in, l->cfg.obs_dim, 0, "mpo_policy_ln", st);
+    if (rc != ACME_OK) return rc;
+    GaussHeadPair g;
+    set_gauss_head(l, g, 0, prm, l->ptg.h[pd.nl - 1], n, mean_out + r0 * A, nullptr,
+                   stddev_out + r0 * A);
+    g.a[1] = g.a[0];
+    gauss_head_kernel<<<dim3((unsigned)ceil_div(n, 4), 1), 256, 0, st>>>(g);
+    ACME_LAUNCH_CHECK();
+  }
+  return ACME_OK;
 }
 
 }  // namespace
@@ -1834,20 +2104,8 @@ int acme_ddpg_debug_buffer(const acme_ddpg* l, const char* name, const float** o
 
 int acme_mpo_create(const acme_mpo_config* cfg, acme_mpo** out) {
   ACME_CHECK_ARG(cfg && out, "null argument");
-  ACME_CHECK_ARG(cfg->num_samples >= 1 && cfg->num_samples <= ACME_MPO_MAX_SAMPLES,
-                 "num_samples must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
-  // The target critic runs max_batch * num_samples rows through the GEMM engine and the
-  // LayerNorm row kernels, which take what D4PG's 2 * 65536 rows ask of them.
-  ACME_CHECK_ARG(cfg->max_batch >= 1 &&
-                     (int64_t)cfg->max_batch * cfg->num_samples <= ACME_MPO_MAX_ROWS,
-                 "max_batch * num_samples must be in [1, %d]", ACME_MPO_MAX_ROWS);
-  ACME_CHECK_ARG(cfg->target_policy_update_period >= 1 && cfg->target_critic_update_period >= 1,
-                 "target update periods must be >= 1");
-  ACME_CHECK_ARG(cfg->epsilon > 0.f && cfg->epsilon_mean > 0.f && cfg->epsilon_stddev > 0.f &&
-                     cfg->epsilon_penalty > 0.f,
-                 "the KL bounds (epsilon*) must be positive");
-  ACME_CHECK_ARG(cfg->init_scale > 0.f && cfg->min_scale >= 0.f,
-                 "init_scale must be positive and min_scale non-negative");
+  const int rc = check_mpo_config(cfg);
+  if (rc != ACME_OK) return rc;
   // target_update_period is unused: MPO has its own two.
   const acme_d4pg_config c = scalar_head_config(cfg, 1);
   return create_learner(&c, Head::kMpo, cfg, out);
@@ -1866,73 +2124,60 @@ int acme_mpo_bind(acme_mpo* l, float* params, float* target, float* grads, float
   return ac_bind(l, params, target, grads, adam_m, adam_v);
 }
 
-int acme_mpo_init_duals(acme_mpo* l) {
-  ACME_CHECK_ARG(l && l->head == Head::kMpo, "not an MPO learner");
-  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
-  ACME_HIP_TRY(hipDeviceSynchronize());
-  const acme_mpo_config& mc = l->mcfg;
-  const std::pair<int, float> init[] = {{l->t_temp, mc.init_log_temperature},
-                                        {l->t_amean, mc.init_log_alpha_mean},
-                                        {l->t_astd, mc.init_log_alpha_stddev},
-                                        {l->t_ptemp, mc.init_log_temperature}};
-  for (const auto& it : init) {
-    if (it.first < 0) continue;
-    const Tensor& t = l->tensors[it.first];
-    const std::vector<float> v((size_t)t.numel, it.second);
-    ACME_HIP_TRY(hipMemcpy(l->params + t.offset, v.data(), v.size() * sizeof(float),
-                           hipMemcpyHostToDevice));
-  }
-  return ACME_OK;
-}
-
+int acme_mpo_init_duals(acme_mpo* l) { return mpo_init_duals(l); }
 int acme_mpo_step(acme_mpo* l, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
                   void* stream) {
-  ACME_CHECK_ARG(l && batch, "null argument");
-  ACME_CHECK_ARG(l->head == Head::kMpo, "not an MPO learner");
-  const int copy = (l->num_steps % l->mcfg.target_policy_update_period == 0 ? 1 : 0) |
-                   (l->num_steps % l->mcfg.target_critic_update_period == 0 ? 2 : 0);
-  const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
-                                 batch->o_t, batch->noise,
-                                 out ? out->critic_loss : nullptr,
-                                 out ? out->policy_loss : nullptr,
-                                 out ? out->stats : nullptr,
-                                 out ? out->kl_mean_rel : nullptr,
-                                 out ? out->kl_stddev_rel : nullptr};
-  return run_step(l, "acme_mpo", batch, key, copy, stream,
-                  [&](hipStream_t s) { return mpo_step_impl(l, batch, out, copy, s); });
+  return mpo_step(l, Head::kMpo, batch, out, stream);
 }
-
 int acme_mpo_policy(acme_mpo* l, const float* obs, int64_t rows, int32_t use_target,
                     float* mean_out, float* stddev_out, void* stream) {
-  ACME_CHECK_ARG(l && obs && mean_out && stddev_out, "null argument");
-  ACME_CHECK_ARG(l->head == Head::kMpo, "not an MPO learner");
-  ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
-  ACME_CHECK_ARG(rows >= 0, "negative row count");
-  hipStream_t st = as_stream(stream);
-  const int B = l->cfg.max_batch, A = l->cfg.act_dim;
-  const NetDesc& pd = l->pol;
-  const float* prm = use_target ? l->target : l->params;
-  for (int64_t r0 = 0; r0 < rows; r0 += B) {
-    const int n = (int)std::min<int64_t>(B, rows - r0);
-    const float* o = obs + r0 * l->cfg.obs_dim;
-    const NetIn in[2] = {{prm, o, nullptr, o, nullptr, n, n, &l->ptg},
-                         {l->params, o, nullptr, o, nullptr, n, 0, &l->ptg}};
-    int rc = lnmlp_forward_pair(l, pd, in, l->cfg.obs_dim, 0, "mpo_policy_ln", st);
-    if (rc != ACME_OK) return rc;
-    GaussHeadPair g;
-    set_gauss_head(l, g, 0, prm, l->ptg.h[pd.nl - 1], n, mean_out + r0 * A, nullptr,
-                   stddev_out + r0 * A);
-    g.a[1] = g.a[0];
-    gauss_head_kernel<<<dim3((unsigned)ceil_div(n, 4), 1), 256, 0, st>>>(g);
-    ACME_LAUNCH_CHECK();
-  }
-  return ACME_OK;
+  return mpo_policy(l, obs, rows, use_target, mean_out, stddev_out, stream);
 }
-
 int64_t acme_mpo_num_steps(const acme_mpo* l) { return ac_num_steps(l); }
 int acme_mpo_set_num_steps(acme_mpo* l, int64_t n) { return ac_set_num_steps(l, n); }
 int acme_mpo_debug_buffer(const acme_mpo* l, const char* name, const float** out,
                           int64_t* count) {
+  return ac_debug_buffer(l, name, out, count);
+}
+
+// ------------------------------------------------------------------ DMPO
+// The shared learner with MPO's policy side and D4PG's categorical critic
+// (DistributionalMPOLearner._step, acme/agents/tf/dmpo/learning.py:147-276).
+
+int acme_dmpo_create(const acme_dmpo_config* cfg, acme_dmpo** out) {
+  ACME_CHECK_ARG(cfg && out, "null argument");
+  const int rc = check_mpo_config(&cfg->mpo);
+  if (rc != ACME_OK) return rc;
+  acme_d4pg_config c = scalar_head_config(&cfg->mpo, 1);
+  c.num_atoms = cfg->num_atoms; c.vmin = cfg->vmin; c.vmax = cfg->vmax;
+  return create_learner(&c, Head::kMpoCategorical, &cfg->mpo, out);
+}
+int acme_dmpo_destroy(acme_dmpo* l) { return ac_destroy(l); }
+int64_t acme_dmpo_flat_size(const acme_dmpo* l) { return ac_flat_size(l); }
+int64_t acme_dmpo_policy_size(const acme_dmpo* l) { return ac_policy_size(l); }
+int64_t acme_dmpo_dual_offset(const acme_dmpo* l) { return l ? l->critic_end : 0; }
+int32_t acme_dmpo_num_tensors(const acme_dmpo* l) { return ac_num_tensors(l); }
+int acme_dmpo_tensor_info(const acme_dmpo* l, int32_t i, int64_t* offset, int64_t* numel,
+                          int32_t* ndim, int64_t* shape4, const char** name) {
+  return tensor_info<acme_actor_critic>(l, i, offset, numel, ndim, shape4, name);
+}
+int acme_dmpo_bind(acme_dmpo* l, float* params, float* target, float* grads, float* adam_m,
+                   float* adam_v) {
+  return ac_bind(l, params, target, grads, adam_m, adam_v);
+}
+int acme_dmpo_init_duals(acme_dmpo* l) { return mpo_init_duals(l); }
+int acme_dmpo_step(acme_dmpo* l, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
+                   void* stream) {
+  return mpo_step(l, Head::kMpoCategorical, batch, out, stream);
+}
+int acme_dmpo_policy(acme_dmpo* l, const float* obs, int64_t rows, int32_t use_target,
+                     float* mean_out, float* stddev_out, void* stream) {
+  return mpo_policy(l, obs, rows, use_target, mean_out, stddev_out, stream);
+}
+int64_t acme_dmpo_num_steps(const acme_dmpo* l) { return ac_num_steps(l); }
+int acme_dmpo_set_num_steps(acme_dmpo* l, int64_t n) { return ac_set_num_steps(l, n); }
+int acme_dmpo_debug_buffer(const acme_dmpo* l, const char* name, const float** out,
+                           int64_t* count) {
   return ac_debug_buffer(l, name, out, count);
 }
 

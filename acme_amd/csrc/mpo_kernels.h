@@ -2,6 +2,8 @@
 // The kernels only MPO's step has: the Gaussian policy head, the action sampling, the critic
 // head over N sampled actions per state with the TD loss, the decoupled MPO loss
 // (acme/tf/losses/mpo.py:145-430) with its backward, and the dual variables' finalize + Adam.
+// DMPO's step adds one: the mixture of the sampled categorical distributions with the
+// categorical loss (dmpo_mix_loss_kernel).
 //
 // A section of d4pg.hip kept in a file of its own: included there once, inside its anonymous
 // namespace, after the device helpers it uses (wave_sum, wave_max, head_dot_row, act_bwd,
@@ -355,6 +357,69 @@ __global__ void __launch_bounds__(256) mpo_loss_kernel(const MpoLossArgs a) {
       if (blockIdx.x * 4 + r < a.B) s += rows_s[r][threadIdx.x];
     a.part[(size_t)blockIdx.x * kMpoCols + threadIdx.x] = s;
   }
+}
+
+// DMPO's critic loss (acme/agents/tf/dmpo/learning.py:212-232): the target critic's categorical
+// head ran over the N sampled actions of each state; the bootstrap distribution of state b is
+// the mixture of its N softmaxes.  d4pg_loss_kernel's layout: one wave per state b, four states
+// per block, lane = atom, -inf past K.
+//   for n = 0 .. N-1 over row n B + b of the target logits: p_n = softmax (max-subtracted),
+//     sq[n B + b] = sum_j p_n[j] values[j] (the sampled q the MPO loss weighs), acc += p_n
+//   mixture = acc / sum_j acc
+//   categorical_loss_row against the online critic's row b: l2_project, ce[b], dlogits[b]
+// The mixture form: the reference takes logsumexp_n(log_softmax_n) as logits (:215-217, without
+// subtracting log N) and the loss softmaxes them again; exp(logsumexp_n log p_n) = sum_n p_n, so
+// this accumulates sum_n p_n per lane in n order (a fixed order: graph and eager agree bit for
+// bit) and normalises it once, with neither the log nor the second exp.
+// One wave per state gives only B waves and a chain of N load -> butterfly rounds each, so the
+// logits of the next kMixAhead samples are loaded before the current ones are reduced.
+constexpr int kMixAhead = 4;
+struct DmpoMixArgs {
+  const float* c_logits;  // online critic [B][K]
+  const float* t_logits;  // target critic over the samples [N B][K]
+  const float *r, *d, *values;
+  int B, N, K;
+  float discount;
+  float *sq, *mix;        // [N B], [B][K]
+  float *dlogits, *ce;    // [B][K], [B]
+};
+
+__global__ void __launch_bounds__(256) dmpo_mix_loss_kernel(const DmpoMixArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;  // uniform per wave
+  const bool on = lane < a.K;
+  const int col = min(lane, a.K - 1);
+  const float vi = on ? a.values[lane] : 0.f;
+  const float ql = on ? a.c_logits[(size_t)b * a.K + lane] : -INFINITY;
+  // Sample n's logit of this lane (clamped indices: a load past N repeats the last row).
+  auto load = [&](int n) {
+    return a.t_logits[((size_t)min(n, a.N - 1) * a.B + b) * a.K + col];
+  };
+  float cur[kMixAhead], nxt[kMixAhead];
+#pragma unroll
+  for (int u = 0; u < kMixAhead; ++u) cur[u] = load(u);
+  float acc = 0.f;
+  for (int n0 = 0; n0 < a.N; n0 += kMixAhead) {
+#pragma unroll
+    for (int u = 0; u < kMixAhead; ++u) nxt[u] = load(n0 + kMixAhead + u);
+#pragma unroll
+    for (int u = 0; u < kMixAhead; ++u) {
+      const int n = n0 + u;
+      if (n >= a.N) break;  // uniform
+      const RowSoftmax t = row_softmax(on ? cur[u] : -INFINITY, on);
+      const float q = wave_sum(on ? t.p * vi : 0.f);
+      if (lane == 0) a.sq[(size_t)n * a.B + b] = q;
+      acc += t.p;  // in n order
+    }
+#pragma unroll
+    for (int u = 0; u < kMixAhead; ++u) cur[u] = nxt[u];
+  }
+  const float pj = acc / wave_sum(acc);
+  if (on) a.mix[(size_t)b * a.K + lane] = pj;
+  const RowSoftmax q = row_softmax(ql, on);
+  categorical_loss_row(ql, q, pj, vi, b, lane, a.r, a.d, a.values, a.B, a.K, a.discount,
+                       a.dlogits, a.ce);
 }
 
 // Sums the loss kernel's block partials in a fixed order, then forms the batch means, the dual

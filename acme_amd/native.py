@@ -891,6 +891,7 @@ class NativeMPO(_NativeActorCritic):
 
     _prefix, _tag, _config = "acme_mpo", "mpo", _lib.MPOConfig
     stat_names = _lib.MPO_STATS
+    _more_config: Dict = {}  # config fields a derived learner adds (NativeDMPO)
 
     def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int,
                  policy_sizes: Sequence[int] = (256, 256, 256),
@@ -927,7 +928,7 @@ class NativeMPO(_NativeActorCritic):
                     per_dim_constraining=1 if per_dim_constraining else 0,
                     action_penalization=1 if action_penalization else 0,
                     init_scale=init_scale, min_scale=min_scale,
-                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF, **self._more_config)
         self.dual_offset = int(self._fn("dual_offset")(self._h))
         self.dual_dim = self.act_dim if per_dim_constraining else 1
         check(self._fn("init_duals")(self._h), "mpo init_duals")
@@ -972,7 +973,7 @@ class NativeMPO(_NativeActorCritic):
         out.stats, out.kl_mean_rel = ptr(self.stats), ptr(self.kl_mean_rel)
         out.kl_stddev_rel = ptr(self.kl_stddev_rel)
         check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(out), stream_ptr(stream)),
-              "mpo step")
+              f"{self._tag} step")
 
     def policy_distribution(self, obs: torch.Tensor, use_target: bool = False, stream=None):
         """(mean, stddev) [rows, act_dim] of the policy's diagonal Gaussian."""
@@ -989,6 +990,26 @@ class NativeMPO(_NativeActorCritic):
     def policy(self, obs: torch.Tensor, use_target: bool = False, stream=None) -> torch.Tensor:
         """The distribution's mean (the greedy action)."""
         return self.policy_distribution(obs, use_target, stream)[0]
+
+
+class NativeDMPO(NativeMPO):
+    """acme_dmpo learner: NativeMPO's policy side, duals, step and stats with D4PG's categorical
+    critic (DiscreteValuedHead over `num_atoms` atoms on [vmin, vmax]); the surface of
+    NativeMPO plus `values`, the support."""
+
+    _prefix, _tag, _config = "acme_dmpo", "dmpo", _lib.DMPOConfig
+
+    def __init__(self, *, num_atoms: int = 51, vmin: float = -150.0, vmax: float = 150.0,
+                 **mpo_args):
+        self.num_atoms, self.vmin, self.vmax = int(num_atoms), float(vmin), float(vmax)
+        self._more_config = dict(num_atoms=self.num_atoms, vmin=self.vmin, vmax=self.vmax)
+        super().__init__(**mpo_args)
+
+    @property
+    def values(self) -> np.ndarray:
+        """The support: tf.linspace(vmin, vmax, num_atoms), as the learner computes it."""
+        step = (np.float64(self.vmax) - np.float64(self.vmin)) / (self.num_atoms - 1)
+        return (np.float64(self.vmin) + np.arange(self.num_atoms) * step).astype(np.float32)
 
 
 class NativeIMPALA(_PlaneState, _NativeLearner):

@@ -375,6 +375,22 @@ def make_mpo_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 2
     }
 
 
+def make_dmpo_networks(obs_dim: int, action_spec, policy_layer_sizes=(256, 256, 256),
+                       critic_layer_sizes=(512, 512, 256), vmin: float = -150.0,
+                       vmax: float = 150.0, num_atoms: int = 51, init_scale: float = 0.3,
+                       min_scale: float = 1e-6) -> Dict[str, object]:
+    """DMPO's networks (make_networks of examples/control_suite/run_dmpo.py): MPO's Gaussian
+    LayerNormMLP policy and D4PG's distributional critic (observation network = identity)."""
+    act_dim = int(np.prod(action_spec.shape))
+    return {
+        "policy": LayerNormMLPGaussianPolicy(obs_dim, act_dim, policy_layer_sizes, init_scale,
+                                             min_scale),
+        "critic": DistributionalCritic(obs_dim, act_dim, critic_layer_sizes, vmin, vmax,
+                                       num_atoms),
+        "observation": "identity",
+    }
+
+
 # ------------------------------------------------------------------ IMPALA (Atari)
 
 

@@ -755,6 +755,64 @@ int acme_mpo_set_num_steps(acme_mpo* l, int64_t n);
 int acme_mpo_debug_buffer(const acme_mpo* l, const char* name, const float** out,
                           int64_t* count);
 
+/* ------------------------------------------------------------------ DMPO -- */
+/* Replaces DistributionalMPOLearner._step (acme/agents/tf/dmpo/learning.py:147-276): MPO's
+ * step with D4PG's categorical critic.  policy = MPO's (LayerNormMLP ->
+ * MultivariateNormalDiagHead), critic = D4PG's (concat(obs, action) -> LayerNormMLP(critic_sizes,
+ * activate_final) -> DiscreteValuedHead(vmin, vmax, num_atoms)), identity observation network.
+ * The policy side, the sampling noise, the MPO loss, the duals, the batch and the outputs are
+ * acme_mpo's; a step export returns ACME_ERR_INVALID for a handle of another kind and names
+ * the entry that handle steps through.
+ *
+ * Flat buffers: MPO's layout with D4PG's critic tensors: policy tensors, critic tensors ending
+ * in "critic/discrete_valued_head/linear/{w,b}" [H, num_atoms], [num_atoms], then the duals.
+ *
+ * Bootstrap distribution: the target critic's head runs over the N B rows [tiled o_t, sampled
+ * actions]; with p[n][b] = softmax(logits[n B + b]) the target of state b is the mixture
+ * softmax_j(logsumexp_n log p[n][b][j]) = sum_n p[n][b] / sum_j sum_n p[n][b][j] (summed in n
+ * order), projected onto the support as in D4PG (l2_project).  The sampled values the MPO loss
+ * weighs are sampled_q[n][b] = sum_j p[n][b][j] values[j].
+ *
+ * Row limit: max_batch * num_samples <= ACME_MPO_MAX_ROWS as for MPO; at ACME_D4PG_MAX_ATOMS
+ * atoms the sampled logits are then 32 MiB. */
+typedef struct acme_dmpo acme_dmpo;
+
+typedef struct acme_dmpo_config {
+  acme_mpo_config mpo;
+  int32_t num_atoms;            /* in [2, ACME_D4PG_MAX_ATOMS] */
+  float vmin, vmax;             /* vmax > vmin */
+} acme_dmpo_config;
+
+int acme_dmpo_create(const acme_dmpo_config* cfg, acme_dmpo** out);
+int acme_dmpo_destroy(acme_dmpo* l);
+int64_t acme_dmpo_flat_size(const acme_dmpo* l);
+/* Floats [0, policy_size) are the policy's, [policy_size, dual_offset) the critic's,
+ * [dual_offset, flat_size) the duals'. */
+int64_t acme_dmpo_policy_size(const acme_dmpo* l);
+int64_t acme_dmpo_dual_offset(const acme_dmpo* l);
+int32_t acme_dmpo_num_tensors(const acme_dmpo* l);
+int acme_dmpo_tensor_info(const acme_dmpo* l, int32_t i, int64_t* offset, int64_t* numel,
+                          int32_t* ndim, int64_t* shape4, const char** name);
+int acme_dmpo_bind(acme_dmpo* l, float* params, float* target, float* grads, float* adam_m,
+                   float* adam_v);
+int acme_dmpo_init_duals(acme_dmpo* l);
+/* One learner step: the two target copies under their own periods, num_steps += 1, the
+ * categorical critic loss against the mixture of the N sampled target distributions, the MPO
+ * loss, global-norm clipping of the policy and critic gradients, three Adams. */
+int acme_dmpo_step(acme_dmpo* l, const acme_mpo_batch* batch, const acme_mpo_outputs* out,
+                   void* stream);
+int acme_dmpo_policy(acme_dmpo* l, const float* obs, int64_t rows, int32_t use_target,
+                     float* mean_out, float* stddev_out, void* stream);
+int64_t acme_dmpo_num_steps(const acme_dmpo* l);
+int acme_dmpo_set_num_steps(acme_dmpo* l, int64_t n);
+/* Internal device workspaces (tests): acme_mpo's names without the scalar critic's ("q_tm1",
+ * "q_t", "td" and "dq" do not exist for this kind, and the lookup says so), plus "logits_tm1"
+ * (B x num_atoms, the online critic), "sampled_logits" (N B x num_atoms), "mixture"
+ * (B x num_atoms, the normalised bootstrap probabilities), "dlogits" (B x num_atoms) and "ce"
+ * (B, the per-row cross entropies). */
+int acme_dmpo_debug_buffer(const acme_dmpo* l, const char* name, const float** out,
+                           int64_t* count);
+
 /* ---------------------------------------------------------------- IMPALA -- */
 /* Replaces IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with
  * IMPALAAtariNetwork (acme/tf/networks/atari.py:115-144): OAREmbedding(AtariTorso) ->
