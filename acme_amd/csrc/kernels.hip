@@ -17,8 +17,11 @@
 namespace acme {
 namespace {
 
-// Duelling head epilogue: one wave per row; lane j <= A sums the split-K partials of
-// output j (fixed split order) and adds its bias; lane A holds the value.
+// Duelling head epilogue: one wave per row; the lanes stride over the A advantages (lane j
+// takes j, j + 64, ...: any A), each summing the split-K partials of its output (fixed split
+// order) and adding its bias; every lane sums the value (output A) itself.  The first
+// advantage of a lane stays in a register, the later ones are parked in q until the mean is
+// known, so for A <= 64 a lane holds one output and the sums are those of one lane per output.
 __global__ void __launch_bounds__(256) duel_head_finish_kernel(const float* __restrict__ slab,
                                                                int splits, int rows, int A,
                                                                const float* __restrict__ bv,
@@ -28,14 +31,24 @@ __global__ void __launch_bounds__(256) duel_head_finish_kernel(const float* __re
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int N = A + 1;
-  float acc = 0.f;
-  if (lane <= A) {
-    for (int s = 0; s < splits; ++s) acc += slab[((size_t)s * rows + row) * N + lane];
-    acc += lane < A ? ba[lane] : bv[0];
+  float* qr = q + (size_t)row * A;
+  float v = 0.f;
+  for (int s = 0; s < splits; ++s) v += slab[((size_t)s * rows + row) * N + A];
+  v += bv[0];
+  float first = 0.f, part = 0.f;
+  for (int j = lane; j < A; j += 64) {
+    float acc = 0.f;
+    for (int s = 0; s < splits; ++s) acc += slab[((size_t)s * rows + row) * N + j];
+    acc += ba[j];
+    if (j == lane) {
+      first = part = acc;
+    } else {
+      part += acc;
+      qr[j] = acc;
+    }
   }
-  const float v = __shfl(acc, A, 64);
-  const float mean = wave_sum(lane < A ? acc : 0.f) / (float)A;
-  if (lane < A) q[(size_t)row * A + lane] = v + (acc - mean);
+  const float mean = wave_sum(part) / (float)A;
+  for (int j = lane; j < A; j += 64) qr[j] = v + ((j == lane ? first : qr[j]) - mean);
 }
 
 // dZ of the fused hidden layer: thread per (b, k).
@@ -316,6 +329,7 @@ __global__ void __launch_bounds__(256) slab_reduce4_kernel(const float* __restri
 // partial dot products and a fixed shuffle tree (deterministic).
 constexpr int kHeadRows = 4;
 constexpr int kHeadChunk = 8;  // advantage outputs per accumulation pass
+constexpr size_t kHeadLdsMax = 160 * 1024;  // a workgroup's LDS on gfx950
 template <int SPL, int HC>
 __global__ void __launch_bounds__(256) fc_head_forward_kernel(
     const float* __restrict__ slab, int splits, int rows, int H_, const float* __restrict__ fcb,
@@ -1362,7 +1376,16 @@ int launch_fc_head_forward(const float* slab, int splits, int rows, int H, const
   const size_t shmem =
       sizeof(float) * (kHeadRows * 2 * H + (size_t)H * A + H + kHeadRows * (A + 1) +
                        4 * kHeadChunk * 64 + 4);
-  ACME_CHECK_ARG(shmem <= 65536, "head too large for the fused head kernel");
+  // Past 64 KB (A > 18 at H = 512) the kernel asks for the workgroup's larger share of the
+  // CU's 160 KB of LDS: A = 63 at H = 512 takes 153 KB.
+  ACME_CHECK_ARG(shmem <= kHeadLdsMax, "head too large for the fused head kernel");
+  auto lds = [&](auto* kernel) {
+    return shmem <= 65536 ||
+           hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)shmem) == hipSuccess;
+  };
+  constexpr const char* kLdsRefused = "fused head kernel: %zu B of LDS refused";
   const bool wa16 = reinterpret_cast<uintptr_t>(wa) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(wv) % 16 == 0 &&
                     reinterpret_cast<uintptr_t>(fcb) % 16 == 0;
@@ -1378,15 +1401,19 @@ int launch_fc_head_forward(const float* slab, int splits, int rows, int H, const
     return ACME_OK;
   }
   const unsigned grid = (unsigned)ceil_div(rows, kHeadRows);
-  if (H == 512 && wa16 && splits == 8)
+  if (H == 512 && wa16 && splits == 8) {
+    if (!lds(fc_head_forward_kernel<8, 512>)) return (set_error(kLdsRefused, shmem), ACME_ERR_HIP);
     fc_head_forward_kernel<8, 512><<<grid, 256, shmem, st>>>(slab, splits, rows, H, fcb, wv, bv, wa,
                                                               ba, A, hid, q);
-  else if (H == 512 && wa16 && splits == 4)
+  } else if (H == 512 && wa16 && splits == 4) {
+    if (!lds(fc_head_forward_kernel<4, 512>)) return (set_error(kLdsRefused, shmem), ACME_ERR_HIP);
     fc_head_forward_kernel<4, 512><<<grid, 256, shmem, st>>>(slab, splits, rows, H, fcb, wv, bv, wa,
                                                               ba, A, hid, q);
-  else
+  } else {
+    if (!lds(fc_head_forward_kernel<0, 0>)) return (set_error(kLdsRefused, shmem), ACME_ERR_HIP);
     fc_head_forward_kernel<0, 0><<<grid, 256, shmem, st>>>(slab, splits, rows, H, fcb, wv, bv, wa,
                                                             ba, A, hid, q);
+  }
   ACME_LAUNCH_CHECK();
   return ACME_OK;
 }

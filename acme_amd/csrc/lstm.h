@@ -909,16 +909,25 @@ __global__ void __launch_bounds__(256) oar_finish_kernel(const float* __restrict
 // accumulator row [w][a][lane]; the W wave partials of each output are then added in wave
 // order.  Deterministic.  (One block per output row, each re-reading all of dgates with 80
 // dependent loads per wave, took 21.6 us.)
+// Beyond kTailRows output rows (A >= 64) blockIdx.y takes the rows [j0, j0 + J) of its chunk,
+// each chunk with its own pass over dgates, so the accumulators stay within 64 KB of LDS.
 constexpr int kTailBatch = 10;
+constexpr int kTailRows = 64;
 inline int tail_waves(int A) { return A + 1 <= 32 ? 8 : 4; }  // LDS W (A + 1) 256 B <= 64 KB
+inline int tail_chunk(int A) { return A + 1 <= kTailRows ? A + 1 : kTailRows; }
 __global__ void __launch_bounds__(512) oar_wgrad_tail_kernel(
     const float* __restrict__ dg, int rows, int N, const int32_t* __restrict__ prev_a,
-    const float* __restrict__ prev_r, int A, float* __restrict__ dw_tail) {
-  extern __shared__ float tacc[];  // [W][A + 1][64]
+    const float* __restrict__ prev_r, int A_all, int chunk, float* __restrict__ dw_tail) {
+  extern __shared__ float tacc[];  // [W][J][64]
   const int W = blockDim.x >> 6;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = blockIdx.x * 64 + lane, nc = min(n, N - 1);
-  const int J = A + 1;
+  // This block's rows j0 .. j0 + J - 1 of the A_all + 1: A of them one-hot rows (actions
+  // j0 .. j0 + A - 1), then the tanh(prev r) row if the chunk holds the last row.
+  const int j0 = blockIdx.y * chunk;
+  const int J = min(chunk, A_all + 1 - j0);
+  const int A = min(J, A_all - j0);
+  dw_tail += (size_t)j0 * N;
   float* my = tacc + (size_t)wave * J * 64;
   for (int j = 0; j < J; ++j) my[j * 64 + lane] = 0.f;
   float racc = 0.f;
@@ -935,12 +944,12 @@ __global__ void __launch_bounds__(512) oar_wgrad_tail_kernel(
 #pragma unroll
     for (int b = 0; b < kTailBatch; ++b) {
       if (m0 + b * W >= rows) break;
-      const int a = __builtin_amdgcn_readfirstlane(act[b]);
+      const int a = __builtin_amdgcn_readfirstlane(act[b]) - j0;
       if ((unsigned)a < (unsigned)A) my[a * 64 + lane] += g[b];
       racc = fmaf(tanhf(tr[b]), g[b], racc);
     }
   }
-  my[A * 64 + lane] = racc;
+  if (A < J) my[A * 64 + lane] = racc;
   __syncthreads();
   for (int e = threadIdx.x; e < J * 64; e += blockDim.x) {
     const int j = e >> 6, nn = blockIdx.x * 64 + (e & 63);

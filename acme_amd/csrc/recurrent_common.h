@@ -312,10 +312,11 @@ int wi_backward_p3(RecurrentNet* l, const torso::Frames& frames, int rows, int64
   const torso::Plane x3s = rows_from(l->x3p, off, F);
   {
     ACME_PROF(tail_name, st, 0.0, 4.0 * (double)rows * N);
-    const int tw = tail_waves(A);
-    oar_wgrad_tail_kernel<<<(unsigned)ceil_div(N, 64), 64 * tw,
-                            (size_t)tw * (A + 1) * 64 * sizeof(float), st>>>(
-        l->dgates, rows, N, prev_a + off, prev_r + off, A, Pm(l, gr, l->t_wi) + (size_t)F * N);
+    const int tw = tail_waves(A), tc = tail_chunk(A);
+    const dim3 grid((unsigned)ceil_div(N, 64), (unsigned)ceil_div(A + 1, tc));
+    oar_wgrad_tail_kernel<<<grid, 64 * tw, (size_t)tw * tc * 64 * sizeof(float), st>>>(
+        l->dgates, rows, N, prev_a + off, prev_r + off, A, tc,
+        Pm(l, gr, l->t_wi) + (size_t)F * N);
     ACME_LAUNCH_CHECK();
   }
   {

@@ -926,7 +926,7 @@ typedef struct acme_r2d2 acme_r2d2;
 typedef struct acme_r2d2_config {
   int32_t torso;                /* ACME_IMPALA_TORSO_ATARI or ACME_IMPALA_TORSO_FLAT */
   int32_t obs_dim;              /* FLAT torso only */
-  int32_t num_actions;
+  int32_t num_actions;          /* in [1, 1024] */
   int32_t max_batch;            /* sequences per step (B) */
   int32_t max_sequence_length;  /* T = burn_in + trace + 1, <= 256 */
   int32_t burn_in_length;

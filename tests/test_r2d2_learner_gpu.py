@@ -146,7 +146,9 @@ def _relu_masks(cfg, n, params, b):
     return masks
 
 
-def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False):
+def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False, errors_rtol=1e-4):
+    """errors_rtol: the relative bar of the end-to-end errors (1e-4 unless a caller derives
+    another from the float32 oracle's own error at its shape)."""
     from acme_amd._lib import lib
     from oracle.dqn_oracle import adam_update
     if f32_engine:
@@ -189,7 +191,8 @@ def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False):
         np.testing.assert_array_equal(g_k[:L - 1], g_tf, err_msg=f"g {k}")
         assert not g_k[L - 1].any()
         # End to end against the f64 networks: the f32 value transforms resolve ~6e-5.
-        _close(n.errors.cpu().numpy(), ref["errors"], rtol=1e-4, floor=0, name=f"errors {k}")
+        _close(n.errors.cpu().numpy(), ref["errors"], rtol=errors_rtol, floor=0,
+               name=f"errors {k}")
         np.testing.assert_allclose(n.errors.cpu().numpy(), ref["errors"], atol=2.5e-4)
         np.testing.assert_allclose(n.loss.item(), ref["loss"], rtol=2e-4, err_msg=f"loss {k}")
         # Gradients: the f64 backward from the kernel's d loss / d q (teacher-forced).
