@@ -206,14 +206,12 @@ __device__ __forceinline__ double top_entry(const double* const* level, int nlev
   return v;
 }
 
-// Draw j of a prioritized sample by one wave (every lane returns the same slot and
-// probability): the descent the oracle restates (oracle/replay_oracle.c).
-__device__ __forceinline__ void draw_prioritized(const TreeView& tree, int64_t size,
-                                                 uint64_t seed, uint64_t step, int64_t j,
+// The descent of one prioritized draw by one wave, from its uniform u (every lane returns the
+// same slot and probability), as the oracle restates it (oracle/replay_oracle.c).  False
+// when every priority is zero: the caller draws uniformly instead.
+__device__ __forceinline__ bool draw_prioritized(const TreeView& tree, double u,
                                                  int64_t* slot_out, double* prob_out) {
   const int lane = threadIdx.x & 63;
-  const double u = sample_uniform(seed, step, (uint32_t)j);
-
   int64_t node = 0;
   double t = 0.0, total = 0.0, leaf_value = 0.0;
   // A computed top level's children rows (level nlevels - 2) are already in registers when
@@ -259,18 +257,46 @@ __device__ __forceinline__ void draw_prioritized(const TreeView& tree, int64_t s
     t = t - excl;
     node = base + idx;
   }
-  int64_t slot;
-  double prob;
-  if (!(total > 0.0)) {  // every priority is zero: uniform fallback
-    slot = (int64_t)(u * (double)size);
-    if (slot >= size) slot = size - 1;
-    prob = 1.0 / (double)size;
-  } else {
-    slot = node;
-    prob = leaf_value / total;
-  }
+  if (!(total > 0.0)) return false;
+  *slot_out = node;
+  *prob_out = leaf_value / total;
+  return true;
+}
+
+// Draw j of a sample: the prioritized descent (one wave per draw: the whole wave calls this),
+// or Uniform()'s slot = floor(u * size), also the fallback of a table whose priorities are
+// all zero.  The only copy of this arithmetic; the oracle restates it.
+template <bool PRIO>
+__device__ __forceinline__ void draw_item(const TreeView& tree, int64_t size, uint64_t seed,
+                                          uint64_t step, int64_t j, int64_t* slot_out,
+                                          double* prob_out) {
+  const double u = sample_uniform(seed, step, (uint32_t)j);
+  if (PRIO && draw_prioritized(tree, u, slot_out, prob_out)) return;
+  int64_t slot = (int64_t)(u * (double)size);
+  if (slot >= size) slot = size - 1;
   *slot_out = slot;
-  *prob_out = prob;
+  *prob_out = 1.0 / (double)size;
+}
+
+// Item j's sample record, by the one thread that calls this.  Every output but the slot is
+// optional.  prob_scale: 1 (exact) unless this table is one shard of a global draw.  A caller
+// may write the record in two parts: what the draw gives (slot, probability, table size) and
+// what is loaded from the slot (key, raw priority).
+enum : int { kRecDraw = 1, kRecSlot = 2, kRecAll = kRecDraw | kRecSlot };
+template <int PARTS = kRecAll>
+__device__ __forceinline__ void write_record(int64_t j, int64_t slot, double prob,
+                                             double prob_scale, int64_t size,
+                                             const double* raw_prio, const uint64_t* keys,
+                                             int64_t* out_slots, uint64_t* out_keys,
+                                             double* out_probs, int64_t* out_size,
+                                             double* out_prio) {
+  if (PARTS & kRecDraw) out_slots[j] = slot;
+  if ((PARTS & kRecSlot) && out_keys) out_keys[j] = keys[slot];
+  if (PARTS & kRecDraw) {
+    if (out_probs) out_probs[j] = prob * prob_scale;
+    if (out_size) out_size[j] = size;
+  }
+  if ((PARTS & kRecSlot) && out_prio) out_prio[j] = raw_prio[slot];
 }
 
 __global__ void __launch_bounds__(256) sample_prioritized_kernel(
@@ -283,17 +309,13 @@ __global__ void __launch_bounds__(256) sample_prioritized_kernel(
   if (j >= batch) return;  // wave-uniform
   int64_t slot;
   double prob;
-  draw_prioritized(tree, size, seed, step, j, &slot, &prob);
-  prob *= prob_scale;  // 1 (exact) unless this table is one shard of a global draw
-  if (lane == 0) {
-    out_slots[j] = slot;
-    if (out_keys) out_keys[j] = keys[slot];
-    if (out_probs) out_probs[j] = prob;
-    if (out_size) out_size[j] = size;
-    if (out_prio) out_prio[j] = raw_prio[slot];
-  }
+  draw_item<true>(tree, size, seed, step, j, &slot, &prob);
+  if (lane == 0)
+    write_record(j, slot, prob, prob_scale, size, raw_prio, keys, out_slots, out_keys,
+                 out_probs, out_size, out_prio);
 }
 
+// Uniform(): one thread per item (no tree, no wave).
 __global__ void sample_uniform_kernel(const double* __restrict__ raw_prio,
                                       const uint64_t* __restrict__ keys, int64_t batch,
                                       int64_t size, uint64_t seed, uint64_t step,
@@ -302,14 +324,11 @@ __global__ void sample_uniform_kernel(const double* __restrict__ raw_prio,
                                       double* out_prio) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= batch) return;
-  const double u = sample_uniform(seed, step, (uint32_t)j);
-  int64_t slot = (int64_t)(u * (double)size);
-  if (slot >= size) slot = size - 1;
-  out_slots[j] = slot;
-  if (out_keys) out_keys[j] = keys[slot];
-  if (out_probs) out_probs[j] = (1.0 / (double)size) * prob_scale;
-  if (out_size) out_size[j] = size;
-  if (out_prio) out_prio[j] = raw_prio[slot];
+  int64_t slot;
+  double prob;
+  draw_item<false>(TreeView{}, size, seed, step, j, &slot, &prob);
+  write_record(j, slot, prob, prob_scale, size, raw_prio, keys, out_slots, out_keys, out_probs,
+               out_size, out_prio);
 }
 
 // The top level's entries with children, when few enough for readers to compute them
@@ -406,7 +425,9 @@ template <int K>
 __global__ void __launch_bounds__(256) gather_pieces_kernel(PieceArgs args,
                                                             const int64_t* __restrict__ slots,
                                                             int32_t batch) {
-  __shared__ PieceArgs a;  // LDS copy of the tables (see gather_row_kernel)
+  // LDS copy of the tables: they are indexed by values known only at run time, which a
+  // by-value kernel argument supports only through a private (scratch) copy.
+  __shared__ PieceArgs a;
   if (threadIdx.x == 0) a = args;
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -465,7 +486,60 @@ struct SmallFields {
   int32_t n;
 };
 
-template <int T, int MAXC, bool NT>
+// Both big rows of table slot `slot` to output row r, by T threads of which the caller is
+// thread t, chunks t, t + T, ... of the 2 x nvec.  v keeps the thread's chunks for a caller
+// that converts them afterwards.  t has the caller's type (unsigned threadIdx.x in the pair
+// kernels, int in the pipe's): the clamp's min() overload follows from it, and with it the
+// instructions each kernel had before it shared this function.
+// The loads are unconditional (a lane past the end re-reads the last chunk): a load under a
+// branch gets a full vmcnt(0) wait at the join, which would serialise the row.  They are
+// non-temporal: source rows are read once.  NT_STORE: non-temporal stores too, for a reader
+// that looks at the rows only steps later.
+// Measured (1M-slot Atari table, B = 512): 256 threads x 14 chunks 12.05 us (4.80 TB/s),
+// 1024 x 4 12.17 us, 512 x 7 12.45 us; plain loads instead of non-temporal 12.85 us; the
+// contiguous copy of the same bytes 11.2 us.
+template <int T, int MAXC, bool NT_STORE, typename TI>
+__device__ __forceinline__ void copy_pair_rows(const uint8_t* s0, const uint8_t* s1,
+                                               uint8_t* d0, uint8_t* d1, int32_t nvec,
+                                               int64_t slot, int64_t r, TI t,
+                                               vu4 (&v)[MAXC]) {
+  const int64_t rb = (int64_t)nvec * 16;
+  const vu4* a0 = reinterpret_cast<const vu4*>(s0 + slot * rb);
+  const vu4* a1 = reinterpret_cast<const vu4*>(s1 + slot * rb);
+  vu4* b0 = reinterpret_cast<vu4*>(d0 + r * rb);
+  vu4* b1 = reinterpret_cast<vu4*>(d1 + r * rb);
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) {
+    const int32_t c = min(t + k * T, 2 * nvec - 1);
+    const vu4* p = c < nvec ? a0 + c : a1 + (c - nvec);
+    v[k] = __builtin_nontemporal_load(p);
+  }
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) {
+    const int32_t c = t + k * T;
+    vu4* p = c < nvec ? b0 + c : b1 + (c - nvec);
+    if (c < 2 * nvec) {
+      if (NT_STORE) __builtin_nontemporal_store(v[k], p);
+      else *p = v[k];
+    }
+  }
+}
+
+// The small fields of table slot `slot` to output row r by 4-B words, by T threads of which
+// the caller is thread t.  (__restrict__: no store here changes sm, so its loads leave the loops.)
+template <int T>
+__device__ __forceinline__ void copy_small_fields(const SmallFields& __restrict__ sm,
+                                                  int64_t slot, int64_t r, int t) {
+#pragma unroll
+  for (int q = 0; q < ACME_MAX_FIELDS; ++q) {
+    if (q >= sm.n) break;
+    for (int w = t; w < sm.words[q]; w += T)
+      reinterpret_cast<uint32_t*>(sm.dst[q] + r * 4 * sm.words[q])[w] =
+          reinterpret_cast<const uint32_t*>(sm.src[q] + slot * 4 * sm.words[q])[w];
+  }
+}
+
+template <int T, int MAXC>
 __global__ void __launch_bounds__(T) gather_pair_kernel(const uint8_t* __restrict__ s0,
                                                         const uint8_t* __restrict__ s1,
                                                         uint8_t* __restrict__ d0,
@@ -474,39 +548,14 @@ __global__ void __launch_bounds__(T) gather_pair_kernel(const uint8_t* __restric
                                                         const int64_t* __restrict__ slots) {
   const int64_t r = blockIdx.x;
   const int64_t slot = slots[r];
-  const int64_t rb = (int64_t)nvec * 16;
-  const vu4* a0 = reinterpret_cast<const vu4*>(s0 + slot * rb);
-  const vu4* a1 = reinterpret_cast<const vu4*>(s1 + slot * rb);
-  vu4* b0 = reinterpret_cast<vu4*>(d0 + r * rb);
-  vu4* b1 = reinterpret_cast<vu4*>(d1 + r * rb);
   vu4 v[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    // Unconditional loads (a lane past the end re-reads the last chunk): a load under a
-    // branch gets a full vmcnt(0) wait at the join, which would serialise the row.
-    const int32_t c = min(threadIdx.x + k * T, 2 * nvec - 1);
-    const vu4* p = c < nvec ? a0 + c : a1 + (c - nvec);
-    v[k] = NT ? __builtin_nontemporal_load(p) : *p;
-  }
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int32_t c = threadIdx.x + k * T;
-    vu4* p = c < nvec ? b0 + c : b1 + (c - nvec);
-    if (c < 2 * nvec) *p = v[k];
-  }
-#pragma unroll
-  for (int q = 0; q < ACME_MAX_FIELDS; ++q) {
-    if (q >= sm.n) break;
-    for (int w = threadIdx.x; w < sm.words[q]; w += T)
-      reinterpret_cast<uint32_t*>(sm.dst[q] + r * 4 * sm.words[q])[w] =
-          reinterpret_cast<const uint32_t*>(sm.src[q] + slot * 4 * sm.words[q])[w];
-  }
+  copy_pair_rows<T, MAXC, false>(s0, s1, d0, d1, nvec, slot, r, threadIdx.x, v);
+  copy_small_fields<T>(sm, slot, r, threadIdx.x);
 }
 
 // Sample + gather fused for the transition layout: workgroup j's first wave draws item j
-// (prioritized descent or uniform, the same arithmetic as the sampling kernels) and writes
-// the sample record; then the workgroup copies the item's rows as gather_pair_kernel does.
-// One launch instead of two, and no slot round trip through memory.
+// and writes the sample record; then the workgroup copies the item's rows as
+// gather_pair_kernel does.  One launch instead of two, and no slot round trip through memory.
 template <bool PRIO, int T, int MAXC>
 __global__ void __launch_bounds__(T) sample_gather_pair_kernel(
     TreeView tree, const double* __restrict__ raw_prio, const uint64_t* __restrict__ keys,
@@ -519,48 +568,22 @@ __global__ void __launch_bounds__(T) sample_gather_pair_kernel(
   if (threadIdx.x < 64) {
     int64_t slot;
     double prob;
-    if (PRIO) {
-      draw_prioritized(tree, size, seed, step, r, &slot, &prob);
-    } else {
-      const double u = sample_uniform(seed, step, (uint32_t)r);
-      slot = (int64_t)(u * (double)size);
-      if (slot >= size) slot = size - 1;
-      prob = 1.0 / (double)size;
-    }
-    prob *= prob_scale;
+    draw_item<PRIO>(tree, size, seed, step, r, &slot, &prob);
     if (threadIdx.x == 0) {
       s_slot = slot;
-      out_slots[r] = slot;
-      if (out_probs) out_probs[r] = prob;
-      if (out_size) out_size[r] = size;
+      write_record<kRecDraw>(r, slot, prob, prob_scale, size, raw_prio, keys, out_slots,
+                             out_keys, out_probs, out_size, out_prio);
     }
   }
   __syncthreads();
   const int64_t slot = s_slot;
   // The record's key and priority after the barrier: their loads ride with the row copy's
   // instead of delaying it by one round trip (the barrier waits for outstanding loads).
-  if (threadIdx.x == 64) {
-    if (out_keys) out_keys[r] = keys[slot];
-    if (out_prio) out_prio[r] = raw_prio[slot];
-  }
-  const int64_t rb = (int64_t)nvec * 16;
-  const vu4* a0 = reinterpret_cast<const vu4*>(s0 + slot * rb);
-  const vu4* a1 = reinterpret_cast<const vu4*>(s1 + slot * rb);
-  vu4* b0 = reinterpret_cast<vu4*>(d0 + r * rb);
-  vu4* b1 = reinterpret_cast<vu4*>(d1 + r * rb);
+  if (threadIdx.x == 64)
+    write_record<kRecSlot>(r, slot, 0.0, prob_scale, size, raw_prio, keys, out_slots, out_keys,
+                           out_probs, out_size, out_prio);
   vu4 v[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int32_t c = min(threadIdx.x + k * T, 2 * nvec - 1);
-    const vu4* p = c < nvec ? a0 + c : a1 + (c - nvec);
-    v[k] = __builtin_nontemporal_load(p);
-  }
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int32_t c = threadIdx.x + k * T;
-    vu4* p = c < nvec ? b0 + c : b1 + (c - nvec);
-    if (c < 2 * nvec) *p = v[k];
-  }
+  copy_pair_rows<T, MAXC, false>(s0, s1, d0, d1, nvec, slot, r, threadIdx.x, v);
   if (fb) {  // the learner's exact f16 copy of both frames: rows [0, B) o_tm1, [B, 2B) o_t
     const int64_t B = gridDim.x;
 #pragma unroll
@@ -586,20 +609,14 @@ __global__ void __launch_bounds__(T) sample_gather_pair_kernel(
       q[1] = hi;
     }
   }
-#pragma unroll
-  for (int q = 0; q < ACME_MAX_FIELDS; ++q) {
-    if (q >= sm.n) break;
-    for (int w = threadIdx.x; w < sm.words[q]; w += T)
-      reinterpret_cast<uint32_t*>(sm.dst[q] + r * 4 * sm.words[q])[w] =
-          reinterpret_cast<const uint32_t*>(sm.src[q] + slot * 4 * sm.words[q])[w];
-  }
+  copy_small_fields<T>(sm, slot, r, threadIdx.x);
 }
 
 // Pipelined draw + gather (round 6; acme_replay_sample_gather_pipe): workgroup j's first wave
-// draws item j of the NEW batch (the sampling arithmetic above) and writes its record, while
-// waves 1-3 copy row j of the batch the previous launch drew (its slots already in memory,
-// one load away).  The descent's chain of dependent tree loads thus runs under the previous
-// batch's row copy instead of in front of it, and no barrier ties the two together.
+// draws item j of the NEW batch and writes its record, while waves 1-3 copy row j of the
+// batch the previous launch drew (its slots already in memory, one load away).  The
+// descent's chain of dependent tree loads thus runs under the previous batch's row copy
+// instead of in front of it, and no barrier ties the two together.
 template <bool PRIO, int MAXC>
 __global__ void __launch_bounds__(256) sample_gather_pipe_kernel(
     TreeView tree, const double* __restrict__ raw_prio, const uint64_t* __restrict__ keys,
@@ -614,60 +631,30 @@ __global__ void __launch_bounds__(256) sample_gather_pipe_kernel(
     if (r >= batch) return;  // wave-uniform
     int64_t slot;
     double prob;
-    if (PRIO) {
-      draw_prioritized(tree, size, seed, step, r, &slot, &prob);
-    } else {
-      const double u = sample_uniform(seed, step, (uint32_t)r);
-      slot = (int64_t)(u * (double)size);
-      if (slot >= size) slot = size - 1;
-      prob = 1.0 / (double)size;
-    }
-    if (threadIdx.x == 0) {
-      out_slots[r] = slot;
-      if (out_probs) out_probs[r] = prob;
-      if (out_size) out_size[r] = size;
-      if (out_keys) out_keys[r] = keys[slot];
-      if (out_prio) out_prio[r] = raw_prio[slot];
+    draw_item<PRIO>(tree, size, seed, step, r, &slot, &prob);
+    if (threadIdx.x == 0) {  // the parts in the pair kernel's order
+      write_record<kRecDraw>(r, slot, prob, 1.0, size, raw_prio, keys, out_slots, out_keys,
+                             out_probs, out_size, out_prio);
+      write_record<kRecSlot>(r, slot, prob, 1.0, size, raw_prio, keys, out_slots, out_keys,
+                             out_probs, out_size, out_prio);
     }
     return;
   }
   if (r >= pend_batch) return;  // workgroup-uniform
   const int t = threadIdx.x - 64;
   const int64_t slot = pend_slots[r];
-  const int64_t rb = (int64_t)nvec * 16;
-  const vu4* a0 = reinterpret_cast<const vu4*>(s0 + slot * rb);
-  const vu4* a1 = reinterpret_cast<const vu4*>(s1 + slot * rb);
-  vu4* b0 = reinterpret_cast<vu4*>(d0 + r * rb);
-  vu4* b1 = reinterpret_cast<vu4*>(d1 + r * rb);
   vu4 v[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int32_t c = min(t + k * T, 2 * nvec - 1);  // unconditional (see gather_pair_kernel)
-    const vu4* p = c < nvec ? a0 + c : a1 + (c - nvec);
-    v[k] = __builtin_nontemporal_load(p);
-  }
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int32_t c = t + k * T;
-    vu4* p = c < nvec ? b0 + c : b1 + (c - nvec);
-    // Non-temporal: a prefetching reader's learner reads these rows steps later (six
-    // alternating 300-step pairs, DQN 0.4701 -> 0.4679 ms; round 6,
-    // profiles/r06/replay/ab_nt_row_stores.log).
-    if (c < 2 * nvec) __builtin_nontemporal_store(v[k], p);
-  }
-#pragma unroll
-  for (int q = 0; q < ACME_MAX_FIELDS; ++q) {
-    if (q >= sm.n) break;
-    for (int w = t; w < sm.words[q]; w += T)
-      reinterpret_cast<uint32_t*>(sm.dst[q] + r * 4 * sm.words[q])[w] =
-          reinterpret_cast<const uint32_t*>(sm.src[q] + slot * 4 * sm.words[q])[w];
-  }
+  // Non-temporal stores: a prefetching reader's learner reads these rows steps later (six
+  // alternating 300-step pairs, DQN 0.4701 -> 0.4679 ms; round 6,
+  // profiles/r06/replay/ab_nt_row_stores.log).
+  copy_pair_rows<T, MAXC, true>(s0, s1, d0, d1, nvec, slot, r, t, v);
+  copy_small_fields<T>(sm, slot, r, t);
 }
 constexpr int kPipeChunks = 19;  // 16-B chunks per copy thread: rows up to 192 x 19 x 8 B
 
 // Sample + gather fused for rows of small fields only (the control-suite transitions:
-// every field under 1 KB): one wave per sampled row draws it (the sampling kernels'
-// arithmetic) and copies its fields, 4 rows per workgroup, no block barrier.
+// every field under 1 KB): one wave per sampled row draws it and copies its fields, 4 rows
+// per workgroup, no block barrier.
 template <bool PRIO>
 __global__ void __launch_bounds__(256) sample_gather_small_kernel(
     TreeView tree, const double* __restrict__ raw_prio, const uint64_t* __restrict__ keys,
@@ -679,29 +666,11 @@ __global__ void __launch_bounds__(256) sample_gather_small_kernel(
   if (r >= batch) return;  // wave-uniform
   int64_t slot;
   double prob;
-  if (PRIO) {
-    draw_prioritized(tree, size, seed, step, r, &slot, &prob);
-  } else {
-    const double u = sample_uniform(seed, step, (uint32_t)r);
-    slot = (int64_t)(u * (double)size);
-    if (slot >= size) slot = size - 1;
-    prob = 1.0 / (double)size;
-  }
-  prob *= prob_scale;
-  if (lane == 0) {
-    out_slots[r] = slot;
-    if (out_keys) out_keys[r] = keys[slot];
-    if (out_probs) out_probs[r] = prob;
-    if (out_size) out_size[r] = size;
-    if (out_prio) out_prio[r] = raw_prio[slot];
-  }
-#pragma unroll
-  for (int q = 0; q < ACME_MAX_FIELDS; ++q) {
-    if (q >= sm.n) break;
-    for (int w = lane; w < sm.words[q]; w += 64)
-      reinterpret_cast<uint32_t*>(sm.dst[q] + r * 4 * sm.words[q])[w] =
-          reinterpret_cast<const uint32_t*>(sm.src[q] + slot * 4 * sm.words[q])[w];
-  }
+  draw_item<PRIO>(tree, size, seed, step, r, &slot, &prob);
+  if (lane == 0)
+    write_record(r, slot, prob, prob_scale, size, raw_prio, keys, out_slots, out_keys,
+                 out_probs, out_size, out_prio);
+  copy_small_fields<64>(sm, slot, r, lane);
 }
 
 // Recompute level[l] nodes from their 64 children (one wave per node).
@@ -1827,6 +1796,32 @@ int acme_replay_fill_synthetic(acme_replay* r, int64_t n, int32_t layout, int32_
   return ACME_OK;
 }
 
+// Bytes of one item over all fields (the profiler's traffic estimates).
+static double row_bytes(const acme_replay* r) {
+  double b = 0;
+  for (int k = 0; k < r->cfg.num_fields; ++k) b += (double)r->cfg.field_bytes[k];
+  return b;
+}
+
+// Prologue of every sampling entry point: orders the stream after the committed inserts and
+// gives what the draw kernels take.  An empty table is an error (Reverb blocks instead).
+struct SampleTable {
+  int64_t size;  // items the draw may return
+  bool prio;     // Prioritized(alpha), else Uniform()
+  TreeView tv;
+};
+static int sample_prologue(acme_replay* r, hipStream_t st, SampleTable* t) {
+  int rc = order_after_inserts(r, st, &t->size);
+  if (rc != ACME_OK) return rc;
+  if (t->size <= 0) {
+    set_error("cannot sample from an empty table (rate limiter MinSize(1))");
+    return ACME_ERR_EMPTY;
+  }
+  t->prio = r->cfg.sampler == ACME_SAMPLER_PRIORITIZED;
+  t->tv = tree_view(r);
+  return ACME_OK;
+}
+
 static int sample_impl(acme_replay* r, int64_t batch, uint64_t step_counter, double prob_scale,
                        int64_t* slots, uint64_t* keys, double* probabilities,
                        int64_t* table_size, double* priorities, void* stream);
@@ -1887,22 +1882,17 @@ static int sample_impl(acme_replay* r, int64_t batch, uint64_t step_counter, dou
   ACME_CHECK_ARG(r && slots, "null argument");
   ACME_CHECK_ARG(batch > 0 && batch <= (int64_t(1) << 31), "batch must be in [1, 2^31]");
   hipStream_t st = as_stream(stream);
-  int64_t size = 0;
-  int rc = order_after_inserts(r, st, &size);
+  SampleTable t;
+  int rc = sample_prologue(r, st, &t);
   if (rc != ACME_OK) return rc;
-  if (size <= 0) {
-    set_error("cannot sample from an empty table (rate limiter MinSize(1))");
-    return ACME_ERR_EMPTY;
-  }
-  ACME_PROF("replay_sample", st, 0.0, (double)batch * (r->cfg.sampler == ACME_SAMPLER_PRIORITIZED ? 512.0 * r->nlevels + 40.0 : 48.0));
-  if (r->cfg.sampler == ACME_SAMPLER_PRIORITIZED) {
-    const TreeView tv = tree_view(r);
+  ACME_PROF("replay_sample", st, 0.0, (double)batch * (t.prio ? 512.0 * r->nlevels + 40.0 : 48.0));
+  if (t.prio) {
     sample_prioritized_kernel<<<(unsigned)ceil_div(batch, 4), 256, 0, st>>>(
-        tv, r->raw_prio, r->keys, batch, size, r->cfg.seed, step_counter, prob_scale, slots,
+        t.tv, r->raw_prio, r->keys, batch, t.size, r->cfg.seed, step_counter, prob_scale, slots,
         keys, probabilities, table_size, priorities);
   } else {
     sample_uniform_kernel<<<(unsigned)ceil_div(batch, 256), 256, 0, st>>>(
-        r->raw_prio, r->keys, batch, size, r->cfg.seed, step_counter, prob_scale, slots, keys,
+        r->raw_prio, r->keys, batch, t.size, r->cfg.seed, step_counter, prob_scale, slots, keys,
         probabilities, table_size, priorities);
   }
   ACME_LAUNCH_CHECK();
@@ -1958,28 +1948,27 @@ static int sample_gather_impl(acme_replay* r, int64_t batch, uint64_t step_count
                               uint16_t* frames_f16) {
   ACME_CHECK_ARG(slots && out_fields, "null argument");
   ACME_CHECK_ARG(batch > 0 && batch < (int64_t(1) << 31), "bad batch");
-  int f0, f1;
+  int f0 = 0, f1 = 0;
   SmallFields sm;
   const bool pair = pair_layout(r, out_fields, &f0, &f1, &sm);
   ACME_CHECK_ARG(!frames_f16 || (pair && reinterpret_cast<uintptr_t>(frames_f16) % 16 == 0),
                  "a bf16 frame copy needs the transition layout (two equal big fields) and a "
                  "16-byte aligned buffer");
-  if (frames_f16 || pair) {
-    hipStream_t st = as_stream(stream);
-    int64_t size = 0;
-    int rc = order_after_inserts(r, st, &size);
+  const bool small = !pair && small_layout(r, out_fields, &sm);
+  if (!pair && !small) {  // no fused kernel for this layout: the sampling kernel, then the gather
+    int rc = sample_impl(r, batch, step_counter, prob_scale, slots, keys, probabilities,
+                         table_size, priorities, stream);
     if (rc != ACME_OK) return rc;
-    if (size <= 0) {
-      set_error("cannot sample from an empty table (rate limiter MinSize(1))");
-      return ACME_ERR_EMPTY;
-    }
-    double row_bytes = 0;
-    for (int k = 0; k < r->cfg.num_fields; ++k) row_bytes += (double)r->cfg.field_bytes[k];
-    const bool prio = r->cfg.sampler == ACME_SAMPLER_PRIORITIZED;
-    ACME_PROF("replay_sample_gather", st, 0.0,
-              (double)batch * (2.0 * row_bytes + 40.0 + (prio ? 512.0 * r->nlevels : 0.0) +
-                               (frames_f16 ? 4.0 * (double)r->cfg.field_bytes[f0] : 0.0)));
-    const TreeView tv = tree_view(r);
+    return acme_replay_gather(r, slots, batch, out_fields, stream);
+  }
+  hipStream_t st = as_stream(stream);
+  SampleTable t;
+  int rc = sample_prologue(r, st, &t);
+  if (rc != ACME_OK) return rc;
+  ACME_PROF("replay_sample_gather", st, 0.0,
+            (double)batch * (2.0 * row_bytes(r) + 40.0 + (t.prio ? 512.0 * r->nlevels : 0.0) +
+                             (frames_f16 ? 4.0 * (double)r->cfg.field_bytes[f0] : 0.0)));
+  if (pair) {
     const int32_t nvec = (int32_t)(r->cfg.field_bytes[f0] / 16);
     const unsigned gb = (unsigned)batch;
     const uint8_t *s0 = r->fields[f0], *s1 = r->fields[f1];
@@ -1987,50 +1976,29 @@ static int sample_gather_impl(acme_replay* r, int64_t batch, uint64_t step_count
     uint8_t* d1 = static_cast<uint8_t*>(out_fields[f1]);
 #define ACME_SGP(PRIO, T, MAXC)                                                                 \
   sample_gather_pair_kernel<PRIO, T, MAXC><<<gb, T, 0, st>>>(                                   \
-      tv, r->raw_prio, r->keys, size, r->cfg.seed, step_counter, prob_scale, slots, keys,       \
+      t.tv, r->raw_prio, r->keys, t.size, r->cfg.seed, step_counter, prob_scale, slots, keys,   \
       probabilities, table_size, priorities, s0, s1, d0, d1, nvec, sm, frames_f16)
     if (2 * nvec <= 256 * 14) {
-      if (prio) ACME_SGP(true, 256, 14);
+      if (t.prio) ACME_SGP(true, 256, 14);
       else ACME_SGP(false, 256, 14);
     } else {
-      if (prio) ACME_SGP(true, 1024, 32);
+      if (t.prio) ACME_SGP(true, 1024, 32);
       else ACME_SGP(false, 1024, 32);
     }
 #undef ACME_SGP
-    ACME_LAUNCH_CHECK();
-    return ACME_OK;
-  }
-  if (!pair && small_layout(r, out_fields, &sm)) {
-    hipStream_t st = as_stream(stream);
-    int64_t size = 0;
-    int rc = order_after_inserts(r, st, &size);
-    if (rc != ACME_OK) return rc;
-    if (size <= 0) {
-      set_error("cannot sample from an empty table (rate limiter MinSize(1))");
-      return ACME_ERR_EMPTY;
-    }
-    double row_bytes = 0;
-    for (int k = 0; k < r->cfg.num_fields; ++k) row_bytes += (double)r->cfg.field_bytes[k];
-    const bool prio = r->cfg.sampler == ACME_SAMPLER_PRIORITIZED;
-    ACME_PROF("replay_sample_gather", st, 0.0,
-              (double)batch * (2.0 * row_bytes + 40.0 + (prio ? 512.0 * r->nlevels : 0.0)));
-    const TreeView tv = tree_view(r);
+  } else {
     const unsigned gb = (unsigned)ceil_div(batch, 4);
-    if (prio)
+    if (t.prio)
       sample_gather_small_kernel<true><<<gb, 256, 0, st>>>(
-          tv, r->raw_prio, r->keys, batch, size, r->cfg.seed, step_counter, prob_scale, slots,
-          keys, probabilities, table_size, priorities, sm);
+          t.tv, r->raw_prio, r->keys, batch, t.size, r->cfg.seed, step_counter, prob_scale,
+          slots, keys, probabilities, table_size, priorities, sm);
     else
       sample_gather_small_kernel<false><<<gb, 256, 0, st>>>(
-          tv, r->raw_prio, r->keys, batch, size, r->cfg.seed, step_counter, prob_scale, slots,
-          keys, probabilities, table_size, priorities, sm);
-    ACME_LAUNCH_CHECK();
-    return ACME_OK;
+          t.tv, r->raw_prio, r->keys, batch, t.size, r->cfg.seed, step_counter, prob_scale,
+          slots, keys, probabilities, table_size, priorities, sm);
   }
-  int rc = sample_impl(r, batch, step_counter, prob_scale, slots, keys, probabilities,
-                       table_size, priorities, stream);
-  if (rc != ACME_OK) return rc;
-  return acme_replay_gather(r, slots, batch, out_fields, stream);
+  ACME_LAUNCH_CHECK();
+  return ACME_OK;
 }
 
 int acme_replay_gather(acme_replay* r, const int64_t* slots, int64_t batch,
@@ -2046,9 +2014,7 @@ int acme_replay_gather(acme_replay* r, const int64_t* slots, int64_t batch,
     g.dst[f] = static_cast<uint8_t*>(out_fields[f]);
     g.bytes[f] = r->cfg.field_bytes[f];
   }
-  double row_bytes = 0;
-  for (int k = 0; k < r->cfg.num_fields; ++k) row_bytes += (double)r->cfg.field_bytes[k];
-  ACME_PROF("replay_gather", st, 0.0, 2.0 * row_bytes * (double)batch + 8.0 * (double)batch);
+  ACME_PROF("replay_gather", st, 0.0, 2.0 * row_bytes(r) * (double)batch + 8.0 * (double)batch);
   // Pieces path: every field a multiple of 4 B (always: acme_replay_create checks it) and
   // 16-B aligned rows and buffers for the big fields.
   bool pieces = true;
@@ -2065,35 +2031,22 @@ int acme_replay_gather(acme_replay* r, const int64_t* slots, int64_t batch,
     pa.nbig++;
   }
   pieces = pieces && total < (int64_t(1) << 30) && pa.nbig > 0;
-  // Transition layout: exactly two big fields of equal bytes, the rest small.
-  if (pieces && pa.nbig == 2 && r->cfg.field_bytes[pa.big[0]] == r->cfg.field_bytes[pa.big[1]]) {
-    const int f0 = pa.big[0], f1 = pa.big[1];
-    const int32_t nvec = (int32_t)(r->cfg.field_bytes[f0] / 16);
-    SmallFields sm = {};
-    for (int f = 0; f < r->cfg.num_fields; ++f)
-      if (f != f0 && f != f1) {
-        sm.src[sm.n] = g.src[f];
-        sm.dst[sm.n] = g.dst[f];
-        sm.words[sm.n] = (int32_t)(r->cfg.field_bytes[f] / 4);
-        sm.n++;
-      }
+  // Transition layout, rows of up to 1024 x 16 chunks: one workgroup per row (wider rows,
+  // which the fused kernel still takes, go by pieces here).
+  int f0, f1;
+  SmallFields sm;
+  const bool pair = pieces && pair_layout(r, out_fields, &f0, &f1, &sm);
+  const int32_t nvec = pair ? (int32_t)(r->cfg.field_bytes[f0] / 16) : 0;
+  if (pair && 2 * nvec <= 1024 * 16) {
     const unsigned gb = (unsigned)batch;
-    bool done = true;
-    // Measured (tools/gather_bench.py, 1M-slot Atari table, B = 512): 256 threads x 14
-    // chunks 12.05 us (4.80 TB/s), 1024 x 4 12.17 us, 512 x 7 12.45 us; plain loads instead
-    // of non-temporal 12.85 us; the contiguous copy of the same bytes 11.2 us.
     if (2 * nvec <= 256 * 14)
-      gather_pair_kernel<256, 14, true><<<gb, 256, 0, st>>>(g.src[f0], g.src[f1], g.dst[f0],
-                                                             g.dst[f1], nvec, sm, slots);
-    else if (2 * nvec <= 1024 * 16)
-      gather_pair_kernel<1024, 16, true><<<gb, 1024, 0, st>>>(g.src[f0], g.src[f1], g.dst[f0],
-                                                               g.dst[f1], nvec, sm, slots);
+      gather_pair_kernel<256, 14><<<gb, 256, 0, st>>>(g.src[f0], g.src[f1], g.dst[f0],
+                                                       g.dst[f1], nvec, sm, slots);
     else
-      done = false;
-    if (done) {
-      ACME_LAUNCH_CHECK();
-      return ACME_OK;
-    }
+      gather_pair_kernel<1024, 16><<<gb, 1024, 0, st>>>(g.src[f0], g.src[f1], g.dst[f0],
+                                                         g.dst[f1], nvec, sm, slots);
+    ACME_LAUNCH_CHECK();
+    return ACME_OK;
   }
   if (pieces) {
     pa.first[pa.nbig] = (int32_t)total;
@@ -2204,13 +2157,9 @@ int acme_replay_sample_gather_pipe(acme_replay* r, int32_t pipe, int64_t batch,
     return sample_gather_impl(r, batch, step_counter, 1.0, slots, keys, probabilities,
                               table_size, priorities, out_fields, stream);
   }
-  int64_t size = 0;
-  int rc = order_after_inserts(r, st, &size);
+  SampleTable t;
+  int rc = sample_prologue(r, st, &t);
   if (rc != ACME_OK) return rc;
-  if (size <= 0) {
-    set_error("cannot sample from an empty table (rate limiter MinSize(1))");
-    return ACME_ERR_EMPTY;
-  }
   // The pending batch's outputs (same layout: the pipe only ever holds pair-layout batches).
   const int64_t pend = ride ? p.batch : 0;
   SmallFields psm = {};
@@ -2223,20 +2172,16 @@ int acme_replay_sample_gather_pipe(acme_replay* r, int32_t pipe, int64_t batch,
     pd0 = static_cast<uint8_t*>(po[g0]);
     pd1 = static_cast<uint8_t*>(po[g1]);
   }
-  double row_bytes = 0;
-  for (int k = 0; k < r->cfg.num_fields; ++k) row_bytes += (double)r->cfg.field_bytes[k];
-  const bool prio = r->cfg.sampler == ACME_SAMPLER_PRIORITIZED;
   ACME_PROF("replay_sample_gather", st, 0.0,
-            (double)batch * (40.0 + (prio ? 512.0 * r->nlevels : 0.0)) +
-                (double)pend * 2.0 * row_bytes);
-  const TreeView tv = tree_view(r);
+            (double)batch * (40.0 + (t.prio ? 512.0 * r->nlevels : 0.0)) +
+                (double)pend * 2.0 * row_bytes(r));
   const unsigned grid = (unsigned)std::max(batch, pend);
 #define ACME_SGPIPE(PRIO)                                                                       \
   sample_gather_pipe_kernel<PRIO, kPipeChunks><<<grid, 256, 0, st>>>(                           \
-      tv, r->raw_prio, r->keys, size, r->cfg.seed, step_counter, batch, slots, keys,            \
+      t.tv, r->raw_prio, r->keys, t.size, r->cfg.seed, step_counter, batch, slots, keys,        \
       probabilities, table_size, priorities, ride ? p.slots : nullptr, pend, r->fields[f0],     \
       r->fields[f1], pd0, pd1, nvec, psm)
-  if (prio) ACME_SGPIPE(true);
+  if (t.prio) ACME_SGPIPE(true);
   else ACME_SGPIPE(false);
 #undef ACME_SGPIPE
   ACME_LAUNCH_CHECK();

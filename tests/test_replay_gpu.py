@@ -268,33 +268,39 @@ def test_prefetched_dataset_draw_order(prefetch):
         o.update(keys, newp)
 
 
+# (capacity, items inserted, batch) of the replay cases: rows of 32 KiB and more get a table of
+# a few MB.  More items than capacity everywhere, so the ring wraps.
+def _case_sizes(fields, default):
+    if max(fields) >= 131072:
+        return 24, 30, 9
+    if max(fields) >= 32768:
+        return 40, 50, 9
+    return default
+
+
 @pytest.mark.parametrize("fields", [[28224, 4, 4, 4, 28224], [28224, 4, 4], [2048, 1040, 8],
-                                    [96, 24, 4, 4, 96], [1024, 4, 1024], [3072, 12, 3072]])
+                                    [96, 24, 4, 4, 96], [1024, 4, 1024], [3072, 12, 3072],
+                                    [1020, 8], [32768, 4, 32768], [131088, 4, 131088]])
 def test_gather_kernels_bit_identical(fields):
-    """The gather kernels (acme_tune_set GATH: 0 = transition pair / pieces default, 1 =
-    row-per-workgroup, 2 = wave pieces) copy exactly the sampled rows."""
-    from acme_amd._lib import lib
+    """acme_replay_gather copies exactly the sampled rows, whichever kernel the layout reaches:
+    two equal big fields of at most 28,672 B take gather_pair_kernel<256,14> ([28224, 4, 4, 4,
+    28224], [1024, 4, 1024], [3072, 12, 3072]) and up to 131,072 B gather_pair_kernel<1024,16>
+    ([32768, 4, 32768]); any other layout with a big field takes gather_pieces_kernel
+    ([28224, 4, 4], [2048, 1040, 8], and [131088, 4, 131088], which is past the pair limit);
+    rows without a big field take gather_fields_kernel, by 16-B vectors ([96, 24, 4, 4, 96]) or,
+    where a row is no 16-B multiple, by 4-B words ([1020, 8])."""
     rng = np.random.default_rng(len(fields) * 31 + fields[0])
-    cap, n, B = 700, 900, 333
+    cap, n, B = _case_sizes(fields, (700, 900, 333))
     data = [rng.integers(0, 256, (n, b), dtype=np.uint8) for b in fields]
     pr = rng.uniform(0.1, 2.0, n)
-    outs = {}
-    for gv in (0, 1, 2):
-        lib().acme_tune_set(b"GATH", gv)  # read once, at the table's creation
-        try:
-            r = _native(cap, fields, True)
-        finally:
-            lib().acme_tune_set(b"GATH", 0)
-        r.insert(data, pr)
-        s = r.sample(B, 4)
-        keys = s["keys"].cpu().numpy().view(np.int64)
-        o = [torch.full((B, b), 7, dtype=torch.uint8, device="cuda") for b in fields]
-        r.gather(s["slots"], o)
-        outs[gv] = [x.cpu().numpy() for x in o]
-    for f, b in enumerate(fields):
-        np.testing.assert_array_equal(outs[0][f], data[f][keys])
-        np.testing.assert_array_equal(outs[1][f], outs[0][f])
-        np.testing.assert_array_equal(outs[2][f], outs[0][f])
+    r = _native(cap, fields, True)
+    r.insert(data, pr)
+    s = r.sample(B, 4)
+    keys = s["keys"].cpu().numpy().view(np.int64)
+    outs = [torch.full((B, b), 7, dtype=torch.uint8, device="cuda") for b in fields]
+    r.gather(s["slots"], outs)
+    for f in range(len(fields)):
+        np.testing.assert_array_equal(outs[f].cpu().numpy(), data[f][keys])
 
 
 def _pipe_buffers(r, B, fields):
@@ -308,18 +314,23 @@ def _pipe_buffers(r, B, fields):
 
 
 @pytest.mark.parametrize("prioritized", [True, False])
-@pytest.mark.parametrize("fields", [[28224, 4, 4, 4, 28224], [2048, 4, 2048], [96, 24, 4, 4, 96]])
+@pytest.mark.parametrize("fields", [[28224, 4, 4, 4, 28224], [2048, 4, 2048], [96, 24, 4, 4, 96],
+                                    [32768, 4, 32768]])
 def test_pipelined_sample_gather(prioritized, fields):
     """acme_replay_sample_gather_pipe (round 6): batch k's rows are copied by call k + 1's
     launch (or a flush); every batch equals the oracle's draw of its step counter and the
     rows of its keys.  Three buffer sets in rotation, a batch-size change mid-stream, and
     an insert between a draw and its copy (the commit issues the pending copy first, so the
-    batch still gets the rows of its drawn keys, not the new items')."""
+    batch still gets the rows of its drawn keys, not the new items').  [96, 24, 4, 4, 96] (no
+    transition layout) and [32768, 4, 32768] (rows too wide for the pipe's copy waves) are not
+    pipelined: the call falls back to the fused launch and meets the same checks."""
     import ctypes
     from acme_amd._lib import lib
     L = lib()
     rng = np.random.default_rng(9)
-    cap, n = 3000, 3000
+    wide = max(fields) >= 32768  # a small table and small batches: a few MB in all
+    cap, n = (40, 40) if wide else (3000, 3000)
+    bmax = 12 if wide else 300
     data = [rng.integers(0, 256, (n, b), dtype=np.uint8) for b in fields]
     pr = rng.uniform(0.0, 2.0, n)
     o = OracleTable(cap, prioritized, 0.6, 1234)
@@ -329,8 +340,10 @@ def test_pipelined_sample_gather(prioritized, fields):
     pid = ctypes.c_int32()
     assert L.acme_replay_pipe_open(r.handle, ctypes.byref(pid)) == 0
     st = torch.cuda.Stream()
-    sets = [_pipe_buffers(r, 300, fields) for _ in range(3)]
+    sets = [_pipe_buffers(r, bmax, fields) for _ in range(3)]
     plan = [(0, 257, 11), (1, 257, 12), (2, 300, 13), (0, 64, 14), (1, 257, 15)]
+    if wide:
+        plan = [(0, 9, 11), (1, 9, 12), (2, 12, 13), (0, 4, 14), (1, 9, 15)]
 
     def check(k):
         s, B, step = plan[k]
@@ -362,42 +375,47 @@ def test_pipelined_sample_gather(prioritized, fields):
 
 @pytest.mark.parametrize("prioritized", [True, False])
 @pytest.mark.parametrize("fields", [[28224, 4, 4, 4, 28224], [2048, 4, 2048],
-                                    [96, 24, 4, 4, 96], [1020, 8]])
+                                    [96, 24, 4, 4, 96], [1020, 8], [32768, 4, 32768],
+                                    [131088, 4, 131088]])
 def test_fused_sample_gather_matches_two_launches(prioritized, fields):
     """acme_replay_sample_gather's fused kernels (the transition layout: draw + row copy in
-    one workgroup; rows of small fields: draw + copy per wave, e.g. D4PG's control
-    transitions) against the sampling kernel + gather (SGF=1) and the oracle's draw."""
+    one workgroup, sample_gather_pair_kernel<*,256,14> up to 28,672 B a row and <*,1024,32>
+    for the two wide layouts; rows of small fields: draw + copy per wave, e.g. D4PG's control
+    transitions) against two launches on a second table built the same way (the sampling
+    kernel, then acme_replay_gather: gather_pair_kernel<256,14>, <1024,16> for
+    [32768, 4, 32768], pieces for [131088, 4, 131088], gather_fields_kernel for the small
+    rows) and the oracle's draw."""
     import ctypes
     from acme_amd._lib import lib
     rng = np.random.default_rng(5)
-    cap, n, B = 3000, 3500, 257
+    cap, n, B = _case_sizes(fields, (3000, 3500, 257))
     data = [rng.integers(0, 256, (n, b), dtype=np.uint8) for b in fields]
     pr = rng.uniform(0.0, 2.0, n)
     o = OracleTable(cap, prioritized, 0.6, 1234)
     o.insert(pr)
     L = lib()
     res = {}
-    for sgf in (0, 1):
-        L.acme_tune_set(b"SGF", sgf)  # read once, at the table's creation
-        try:
-            r = _native(cap, fields, prioritized)
-        finally:
-            L.acme_tune_set(b"SGF", 0)
+    for fused in (True, False):
+        r = _native(cap, fields, prioritized)
         r.insert(data, pr)
-        info = r.alloc_sample_info(B)
         outs = [torch.zeros(B, b, dtype=torch.uint8, device="cuda") for b in fields]
-        ptrs = (ctypes.c_void_p * len(outs))(*[x.data_ptr() for x in outs])
-        raw = [info[k].data_ptr() for k in ("slots", "keys", "probabilities", "table_size",
-                                              "priorities")]
-        assert L.acme_replay_sample_gather(r.handle, B, 77, *raw, ptrs, None) == 0
+        if fused:
+            info = r.alloc_sample_info(B)
+            ptrs = (ctypes.c_void_p * len(outs))(*[x.data_ptr() for x in outs])
+            raw = [info[k].data_ptr() for k in ("slots", "keys", "probabilities", "table_size",
+                                                  "priorities")]
+            assert L.acme_replay_sample_gather(r.handle, B, 77, *raw, ptrs, None) == 0
+        else:
+            info = r.sample(B, 77)
+            r.gather(info["slots"], outs)
         torch.cuda.synchronize()
-        res[sgf] = ({k: v.cpu().numpy() for k, v in info.items()},
-                    [x.cpu().numpy() for x in outs])
+        res[fused] = ({k: v.cpu().numpy() for k, v in info.items()},
+                      [x.cpu().numpy() for x in outs])
     ref = o.sample(B, 77)
     for k in ("slots", "probabilities", "table_size", "priorities"):
-        np.testing.assert_array_equal(res[0][0][k], ref[k])
-        np.testing.assert_array_equal(res[1][0][k], ref[k])
-    keys = res[0][0]["keys"].view(np.int64)
+        np.testing.assert_array_equal(res[True][0][k], ref[k])
+        np.testing.assert_array_equal(res[False][0][k], ref[k])
+    keys = res[True][0]["keys"].view(np.int64)
     for f in range(len(fields)):
-        np.testing.assert_array_equal(res[0][1][f], data[f][keys])
-        np.testing.assert_array_equal(res[1][1][f], res[0][1][f])
+        np.testing.assert_array_equal(res[True][1][f], data[f][keys])
+        np.testing.assert_array_equal(res[False][1][f], res[True][1][f])
