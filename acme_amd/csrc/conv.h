@@ -13,6 +13,7 @@
 // dZ always denotes the gradient w.r.t. a layer's pre-activation.
 #pragma once
 
+#include "conv_geom.h"
 #include "gemm.h"
 
 namespace acme {
@@ -22,16 +23,6 @@ using gemm::f32x4;
 using gemm::KCONTIG;
 using gemm::RCONTIG;
 using gemm::zero4;
-
-template <int IH_, int IW_, int CI_, int OH_, int OW_, int CO_, int KH_, int KW_, int S_,
-          int PT_, int PL_>
-struct Geom {
-  static constexpr int IH = IH_, IW = IW_, CI = CI_, OH = OH_, OW = OW_, CO = CO_;
-  static constexpr int KH = KH_, KW = KW_, S = S_, PT = PT_, PL = PL_;
-  static constexpr int K = KH * KW * CI;
-  static constexpr int IPIX = IH * IW, OPIX = OH * OW;
-  static_assert(CI % 4 == 0 && CO % 4 == 0, "channel counts must be multiples of 4");
-};
 
 // Input element types: uint8 observations scaled by 1/255 (AtariWrapper to_float,
 // acme/wrappers/atari_wrapper.py:284-306) or f32 activations.

@@ -149,9 +149,11 @@ struct acme_dqn : PlaneGuard {
   double* loss_part = nullptr;  // per-block loss partials of the fused loss + head dZ
   // Schedule variants fixed at creation (tests compare them bit for bit): one stream
   // (ACME_V_SIDE=1), the single-role GEMM kernels instead of the producer / consumer ones
-  // (ACME_V_WSN=1).
+  // (ACME_V_WSN=1), the image-resident convolutions at a stage depth of 32 k instead of
+  // each kernel's own (ACME_V_BK32=1).
   bool single_stream = false;
   bool single_role = false;
+  bool bk32 = false;
   // conv1 reads the batch's uint8 frames (unless the batch carries the f16 copy, obs_f16, or
   // the frames are not 16-byte aligned: then the step makes the f16 copy, the round-4 path)
   bool frames_u8 = true;
@@ -310,7 +312,7 @@ int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso:
   if (!slab) slab = l->slab;
   torso::PWeights w{WP(l, wpl, l->t_c1w), WP(l, wpl, l->t_c2w), WP(l, wpl, l->t_c3w),
                     P(l, prm, l->t_c1b), P(l, prm, l->t_c2b), P(l, prm, l->t_c3b)};
-  int rc = torso::forward_p3(w, frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1);
+  int rc = torso::forward_p3(w, frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1, l->bk32);
   if (rc != ACME_OK) return rc;
   {
     P3DenseFwd p;
@@ -663,6 +665,7 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
   l->cfg = *cfg;
   l->single_stream = tune_variant("SIDE") == 1;
   l->single_role = tune_variant("WSN") == 1;
+  l->bk32 = tune_variant("BK32") == 1;
   l->stamps_on = tune_variant("STAMPS") == 1;
   const int A = cfg->num_actions;
   const int B = cfg->max_batch;
@@ -1092,8 +1095,9 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
                         P(l, l->params, l->t_c2b), P(l, l->params, l->t_c3b)};
       torso::Side sd;
       sd.single_role = l->single_role;
+      sd.bk32 = l->bk32;
       // conv1's weight gradient on the single-role kernel: its two 20-KB stages (40 KB of
-      // LDS) fit beside the next step's fused target convolution (121 KB) that runs on the
+      // LDS) fit beside the next step's fused target convolution (117 KB) that runs on the
       // side stream at the same time; the producer / consumer kernel's three stages (60 KB)
       // do not.  Step 0.4957 -> 0.4920 ms (three alternating 300-step pairs, round 6,
       // profiles/r06/schedule/ab_conv1_wgrad_single_role.log).

@@ -10,151 +10,52 @@
 // directly, with the tap offset applied per lane (padding taps read a zero unit).  Only
 // the weight panel B (K x BN) streams through a two-stage register-staged LDS ring.
 //
-// A geometry GI says where each 16-B unit (8 consecutive k of one GEMM row) lives:
-//   UNITS            16-B HBM units per frame (frames contiguous in HBM);
-//   IMG              LDS bytes of one frame's image (one plane);
-//   fill(f, u)       LDS byte offset of HBM unit u of the block's frame f;
-//   Lane lane(f, pp, ok)         per-lane state of output pixel pp of frame f;
-//   Stage stage(lane, k0)        per 32-k stage (k0 a multiple of 32);
-//   int unit(stage, lane, k0, s, h)  byte offset of the lane's unit in k16 step s (lane
-//                                    half h), or -1 for padding (the zero unit).
+// A geometry GI (gemm_p3i_geom.h) says where each 16-B unit (8 consecutive k of one GEMM
+// row) lives, and which of the plane's 16 zero units a padding tap reads.
+//
+// A stage is BK k (a multiple of 32): one barrier and one ring hand-off per BK / 16 k16
+// steps.  Within a stage the fragments are read in 32-k groups, each group's reads fenced
+// before its MFMAs, so the register count does not grow with BK and the k order -- hence
+// every sum -- is that of BK = 32.  The last stage is shorter when K % BK != 0.
 #pragma once
 
 #include "gemm_p3.h"
+#include "gemm_p3i_geom.h"
 
 namespace acme {
 namespace gemm {
 
-// Channel-chunk images (conv2 / conv3 forward, stride-1 input gradient) over conv.h's Geom
-// G.  Forward (DGRAD = false): the image is the layer input X [IH][IW][CI], GEMM rows are
-// (frame, oh, ow), tap (kh, kw) reads (oh*S - PT + kh, ow*S - PL + kw).  Input gradient
-// (DGRAD = true, stride 1): the image is dZ [OH][OW][CO], rows are (frame, ih, iw), tap
-// (kh, kw) reads (ih + PT - kh, iw + PL - kw).  K is ordered (kh, kw, channel), as
-// conv_p3.h; C is 32 or 64, so a 32-k stage stays within one tap.
-// LDS layout, per plane: pixel q = (frame * H + ih) * W + col, col = iw (stride 1) or, for
-// stride 2, the even columns then the odd ones (consecutive output columns, i.e. the
-// consecutive rows of an MFMA fragment, read consecutive pixels); the 16-B channel chunk c
-// of pixel q sits at chunk c ^ ((q >> SWZ) & (CPX - 1)), CPX chunks per pixel, so 16
-// consecutive pixels' reads of one chunk fall in 16 distinct 4-bank groups.
-template <class G, bool DGRAD>
-struct ImgGeom {
-  static constexpr int H = DGRAD ? G::OH : G::IH, W = DGRAD ? G::OW : G::IW;
-  static constexpr int C = DGRAD ? G::CO : G::CI;
-  static constexpr int OH = DGRAD ? G::IH : G::OH, OW = DGRAD ? G::IW : G::OW;
-  static constexpr int S = DGRAD ? 1 : G::S;
-  static constexpr int KW = G::KW;
-  static constexpr int OPIX = OH * OW, IPIX = H * W;
-  static constexpr int CPX = C / 8;         // 16-B chunks per pixel
-  static constexpr int HALF = (W + 1) / 2;  // stride 2: even columns first
-  static constexpr int SWZ = CPX == 8 ? 1 : 2;
-  static constexpr int UNITS = IPIX * CPX, IMG = IPIX * 2 * C;
-  static_assert(!DGRAD || G::S == 1, "strided input gradients are not image-resident");
-  static_assert(C == 32 || C == 64, "a 32-k stage must stay within one tap");
-  static_assert(S == 1 || S == 2, "stride 1 or 2");
-  __device__ static __forceinline__ int dh(int kh) { return DGRAD ? G::PT - kh : kh - G::PT; }
-  __device__ static __forceinline__ int dw(int kw) { return DGRAD ? G::PL - kw : kw - G::PL; }
-  __device__ static __forceinline__ int pix(int fr, int ih, int iw) {
-    return (fr * H + ih) * W + (S == 1 ? iw : (iw & 1) * HALF + (iw >> 1));
-  }
-  __device__ static __forceinline__ int swz(int q) { return (q >> SWZ) & (CPX - 1); }
-  __device__ static __forceinline__ int fill(int f, int u) {
-    const int px = u / CPX, c = u - px * CPX;
-    const int ih = px / W, iw = px - ih * W;
-    const int q = pix(f, ih, iw);
-    return q * (2 * C) + 16 * (c ^ swz(q));
-  }
-  struct Lane {
-    int f, ih, iw;
-    bool ok;
-  };
-  __device__ static __forceinline__ Lane lane(int f, int pp, bool ok) {
-    const int oh = pp / OW, ow = pp - oh * OW;
-    return Lane{f, oh * S, ow * S, ok};
-  }
-  struct Stage {
-    int base, x;  // pixel byte base (-1: padding), chunk swizzle
-  };
-  __device__ static __forceinline__ Stage stage(const Lane& l, int k0) {
-    const int tap = k0 / C;  // wave-uniform
-    const int kh = tap / KW, kw = tap - kh * KW;
-    const int ih = l.ih + dh(kh), iw = l.iw + dw(kw);
-    const bool in = l.ok && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-    const int q = pix(l.f, ih, iw);
-    return Stage{in ? q * (2 * C) : -1, swz(q)};
-  }
-  __device__ static __forceinline__ int unit(const Stage& st, const Lane&, int k0, int s, int h) {
-    const int c = ((k0 % C) >> 3) + 2 * s + h;
-    return st.base >= 0 ? st.base + 16 * (c ^ st.x) : -1;
-  }
-};
-
-// Pixel-pair images for a 4-channel input (conv1 over the frames, one plane): a unit is two
-// horizontally adjacent pixels x 4 channels, which is exactly the 8 k of one MFMA lane
-// (k = (kh, kw, c): kw even, kw + 1) -- 16 B of the f16 frame copy.  A 32-k stage is one
-// kernel row kh (KW * CI = 32).  LDS layout: unit (ih, pw) (pw = iw / 2) at (frame * IH +
-// ih) * PAIRS + col, col = the even pairs then the odd ones, so stride-S output columns
-// read consecutive units (conflict-free ds_read_b128 lane groups).
-template <class G>
-struct ImgGeomPairs {
-  static constexpr int UNIT = 16;  // LDS bytes per unit
-  static constexpr int H = G::IH, W = G::IW;
-  static constexpr int OW = G::OW, OPIX = G::OPIX;
-  static constexpr int PAIRS = W / 2, HALF = (PAIRS + 1) / 2;
-  static constexpr int UNITS = H * PAIRS, IMG = UNITS * UNIT;
-  static_assert(G::CI == 4 && G::KW * G::CI == 32, "4 channels, one kernel row per stage");
-  static_assert(W % 2 == 0 && G::S % 2 == 0 && G::PL % 2 == 0, "pairs never straddle the border");
-  __device__ static __forceinline__ int col(int pw) { return (pw & 1) * HALF + (pw >> 1); }
-  __device__ static __forceinline__ int fill(int f, int u) {
-    const int ih = u / PAIRS, pw = u - ih * PAIRS;
-    return ((f * H + ih) * PAIRS + col(pw)) * UNIT;
-  }
-  struct Lane {
-    int f, ih, iw;
-    bool ok;
-  };
-  __device__ static __forceinline__ Lane lane(int f, int pp, bool ok) {
-    const int oh = pp / OW, ow = pp - oh * OW;
-    return Lane{f, oh * G::S - G::PT, ow * G::S - G::PL, ok};
-  }
-  struct Stage {
-    int base;  // image row byte base (-1: padding row)
-  };
-  __device__ static __forceinline__ Stage stage(const Lane& l, int k0) {
-    const int ih = l.ih + k0 / 32;
-    const bool in = l.ok && (unsigned)ih < (unsigned)H;
-    return Stage{in ? (l.f * H + ih) * PAIRS * UNIT : -1};
-  }
-  __device__ static __forceinline__ int unit(const Stage& st, const Lane& l, int, int s, int h) {
-    const int iw = l.iw + 4 * s + 2 * h;  // kw = (16 s + 8 h) / 4
-    return st.base >= 0 && (unsigned)iw < (unsigned)W ? st.base + col(iw >> 1) * UNIT : -1;
-  }
-};
-
-
-template <class GI, int FPB, int BN, int WM, int WN, int MT, class P>
+template <class GI, int FPB, int BN, int WM, int WN, int MT, int BK_, class P>
 struct P3ICfg {
-  static constexpr int BK = 32, KS = 2;
+  static constexpr int BK = BK_;            // k per stage (one barrier, one ring hand-off)
+  static constexpr int GK = 32, KS = 2;     // k per fragment group, its k16 steps
+  static constexpr int NG = BK / GK;        // groups per stage
+  static_assert(BK % GK == 0 && NG >= 1, "a stage is whole 32-k groups");
   static constexpr int NW = WM * WN, NT = 64 * NW;
   static constexpr int TN = BN / WN, NTL = TN / 32;
   static constexpr int BM = WM * 32 * MT;
   static_assert(BM >= FPB * GI::OPIX, "the block's waves must cover its frames' rows");
   static_assert(TN % 32 == 0, "wave panel of whole 32-column MFMA tiles");
-  using Core = P3Core<BM, BN, WM, WN, BK, P>;
+  using Core = P3Core<BM, BN, WM, WN, GK, P>;
   using PB = typename Core::PB;
   static constexpr int NPA = P::A_PLANES;
-  static constexpr int PLANE = FPB * GI::IMG + 16;  // + the zero unit
+  static constexpr int ZERO = img_zero_base(FPB * GI::IMG);  // the plane's zero area
+  static constexpr int PLANE = ZERO + kImgZeroBytes;
   static constexpr int IMG = NPA * PLANE;
-  static constexpr int STAGE_B = PB::BYTES;
+  static constexpr int STAGE_B = NG * PB::BYTES;     // a group's B panel is one PlanP3 tile
+  static constexpr int B_UNITS = NG * PB::UNITS;     // 16-B units of a stage's B, per plane
+  static constexpr int B_PER = (B_UNITS + NT - 1) / NT;
   static constexpr int MAIN = IMG + 2 * STAGE_B;
   static constexpr int LDS = MAIN > Core::EPI_BYTES ? MAIN : Core::EPI_BYTES;
 };
 
-template <class GI, int FPB, int BN, int WM, int WN, int MT, class P>
+template <class GI, int FPB, int BN, int WM, int WN, int MT, int BK_, class P>
 __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, int frames) {
-  using Cfg = P3ICfg<GI, FPB, BN, WM, WN, MT, P>;
+  using Cfg = P3ICfg<GI, FPB, BN, WM, WN, MT, BK_, P>;
   using C = typename Cfg::Core;
   using PB = typename Cfg::PB;
   constexpr int NT = Cfg::NT, NTL = Cfg::NTL, TN = Cfg::TN, BK = Cfg::BK, KS = Cfg::KS;
+  constexpr int GK = Cfg::GK, NG = Cfg::NG, B_PER = Cfg::B_PER, B_UNITS = Cfg::B_UNITS;
   constexpr int PLANE = Cfg::PLANE, NPA = Cfg::NPA;
   constexpr int NPB = kPlanes;
   static_assert(P::A_MODE == KCONTIG && (NPA == 1 || NPA == kPlanes) && P::B_PLANES == NPB,
@@ -181,27 +82,32 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
   const int m0 = f0 * GI::OPIX;
   P p = p_in;
   p.M = m0 + rows < p_in.M ? m0 + rows : p_in.M;  // the epilogue writes this block's rows only
-  const int nk = p.K / BK;
+  const int nk = (p.K + BK - 1) / BK;  // the last stage may be short (whole groups)
 
   // ---- B: the weight panel, register-staged double buffer.
-  typename P::BRow brow[PB::PER_THREAD];
+  // Unit u of a stage is unit u % PB::UNITS of group u / PB::UNITS.
+  typename P::BRow brow[B_PER];
 #pragma unroll
-  for (int i = 0; i < PB::PER_THREAD; ++i)
-    brow[i] = p.b_row(PB::owns(tid + i * NT) ? PB::row_of(tid + i * NT) : 0);
+  for (int i = 0; i < B_PER; ++i) {
+    const int u = tid + i * NT;
+    brow[i] = p.b_row(u < B_UNITS ? PB::row_of(u % PB::UNITS) : 0);
+  }
   __amdgpu_buffer_rsrc_t srcB[NPB];
 #pragma unroll
   for (int pl = 0; pl < NPB; ++pl) srcB[pl] = plane_rsrc(p.b_src, pl);
   // Two register sets (round 5: a third, loads two iterations ahead, measured slower on the
   // step: 0.4949 -> 0.5011 ms).
   constexpr int RS = 2;
-  u32x4 rb[RS][PB::PER_THREAD][NPB];
+  u32x4 rb[RS][B_PER][NPB];
   auto fetch_b = [&](auto S, int k0) {
     constexpr int set = decltype(S)::value;
 #pragma unroll
-    for (int i = 0; i < PB::PER_THREAD; ++i) {
+    for (int i = 0; i < B_PER; ++i) {
       const int u = tid + i * NT;
-      const int kk = PB::kk_of(u);
-      const uint32_t off = (PB::owns(u) && k0 + kk < p.K) ? p.b_off(brow[i], k0, kk) : kOOB;
+      const int g = u / PB::UNITS, kk = PB::kk_of(u % PB::UNITS);
+      const int kg = k0 + g * GK;
+      const uint32_t off =
+          ((B_UNITS % NT == 0 || u < B_UNITS) && kg + kk < p.K) ? p.b_off(brow[i], kg, kk) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NPB; ++pl)
         rb[set][i][pl] =
@@ -212,10 +118,10 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
     constexpr int set = decltype(S)::value;
     uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B;
 #pragma unroll
-    for (int i = 0; i < PB::PER_THREAD; ++i) {
+    for (int i = 0; i < B_PER; ++i) {
       const int u = tid + i * NT;
-      if (!PB::owns(u)) continue;
-      const int off = PB::offset(u);
+      if (B_UNITS % NT != 0 && u >= B_UNITS) continue;
+      const int off = (u / PB::UNITS) * PB::BYTES + PB::offset(u % PB::UNITS);
 #pragma unroll
       for (int pl = 0; pl < NPB; ++pl)
         *reinterpret_cast<u32x4*>(sb + pl * PB::PLANE + off) = rb[set][i][pl];
@@ -254,7 +160,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
         *reinterpret_cast<u32x4*>(smem + GI::fill(0, 2 * u + 1)) = f16x8_of_bytes(v[j][2], v[j][3]);
       }
     }
-    if (tid == 0) *reinterpret_cast<u32x4*>(smem + PLANE - 16) = zero_u4();
+    if (tid < 16) *reinterpret_cast<u32x4*>(smem + Cfg::ZERO + 16 * tid) = zero_u4();
   } else {
     constexpr int UNITS = FPB * GI::UNITS;
     constexpr int PER = (UNITS + NT - 1) / NT;
@@ -284,7 +190,8 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
         for (int pl = 0; pl < NPA; ++pl) *reinterpret_cast<UT*>(smem + pl * PLANE + a) = v[j][pl];
       }
     }
-    if (tid < NPA) *reinterpret_cast<u32x4*>(smem + tid * PLANE + PLANE - 16) = zero_u4();
+    if (tid < 16 * NPA)
+      *reinterpret_cast<u32x4*>(smem + (tid >> 4) * PLANE + Cfg::ZERO + 16 * (tid & 15)) = zero_u4();
   }
   stash_b(S0{}, 0);
 
@@ -306,13 +213,13 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
   typename EpiPre<P>::type pre{};
   if constexpr (EpiPre<P>::has) pre = p.pre(wn * TN + C::epi_col(lane));
 
-  auto compute = [&](int k0, int buf) {
-    const uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B;
+  // One 32-k group: its B panel at sb.
+  auto group = [&](int k0, const uint8_t* sb) {
     typename GI::Stage sg[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) sg[i] = GI::stage(ln[i], k0);
-    // Every fragment of the stage read first, then the MFMAs (fenced): one LDS latency per
-    // stage instead of one per k16 step (the scheduler otherwise sinks each read to its first
+    for (int i = 0; i < MT; ++i) sg[i] = GI::stage(ln[i], k0, Cfg::ZERO);
+    // Every fragment of the group read first, then the MFMAs (fenced): one LDS latency per
+    // group instead of one per k16 step (the scheduler otherwise sinks each read to its first
     // use; round 5: step 0.4969 -> 0.4949 ms with the fences here and in iter below).
     f16x8 fb[KS][NTL][NPB], fa[KS][MT][NPA];
 #pragma unroll
@@ -323,8 +230,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
         for (int pl = 0; pl < NPB; ++pl) fb[s][j][pl] = PB::frag(sb, pl, wn * TN + j * 32, s, lane);
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        const int u = GI::unit(sg[i], ln[i], k0, s, lane >> 5);
-        const int a = u >= 0 ? u : PLANE - 16;
+        const int a = GI::unit(sg[i], ln[i], k0, s, lane >> 5);
 #pragma unroll
         for (int pl = 0; pl < NPA; ++pl)
           fa[s][i][pl] = *reinterpret_cast<const f16x8*>(smem + pl * PLANE + a);
@@ -337,6 +243,18 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NTL; ++j) acc.terms(i, j, fa[s][i], fb[s][j]);
+  };
+  // One stage: its groups in k order (fewer in a short last stage; block-uniform).
+  auto compute = [&](int k0, int buf) {
+    const uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      if (g > 0) {
+        if (k0 + g * GK >= p.K) break;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      group(k0 + g * GK, sb + g * PB::BYTES);
+    }
   };
 
   // Iteration kt: LDS buffer kt & 1 holds B of stage kt, register set (kt + 1) % RS holds
@@ -378,15 +296,15 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
 }
 
 // frames: the number of images (p.M = frames * GI::OPIX rows).
-template <class GI, int FPB, int BN, int WM, int WN, int MT, class P>
+template <class GI, int FPB, int BN, int WM, int WN, int MT, int BK_, class P>
 inline hipError_t launch_gemm_p3i(const P& p, int frames, hipStream_t st) {
-  using Cfg = P3ICfg<GI, FPB, BN, WM, WN, MT, P>;
+  using Cfg = P3ICfg<GI, FPB, BN, WM, WN, MT, BK_, P>;
   static_assert(Cfg::LDS <= 160 * 1024, "image + two B stages must fit the 160-KiB LDS");
-  static hipError_t attr = p3_set_lds(&gemm_p3i_kernel<GI, FPB, BN, WM, WN, MT, P>, Cfg::LDS);
+  static hipError_t attr = p3_set_lds(&gemm_p3i_kernel<GI, FPB, BN, WM, WN, MT, BK_, P>, Cfg::LDS);
   if (attr != hipSuccess) return attr;
-  if (p.N > BN || p.M != frames * GI::OPIX || p.K % Cfg::BK != 0) return hipErrorInvalidValue;
+  if (p.N > BN || p.M != frames * GI::OPIX || p.K % Cfg::GK != 0) return hipErrorInvalidValue;
   const int blocks = (frames + FPB - 1) / FPB;
-  hipLaunchKernelGGL((gemm_p3i_kernel<GI, FPB, BN, WM, WN, MT, P>), dim3(blocks), dim3(Cfg::NT),
+  hipLaunchKernelGGL((gemm_p3i_kernel<GI, FPB, BN, WM, WN, MT, BK_, P>), dim3(blocks), dim3(Cfg::NT),
                      Cfg::LDS, st, p, frames);
   return hipGetLastError();
 }

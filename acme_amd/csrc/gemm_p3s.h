@@ -10,64 +10,76 @@
 // most 128: 64 each, MT = 2) -- with the four classes' weight panels streamed together
 // through the two-stage register-staged ring (one 16-B unit per thread per plane).  The
 // epilogue is the problem's own (ReLU mask from the previous activation, plane stores).
+// Where the image's units lie and what each lane reads: gemm_p3i_geom.h ImgGeomSub.
 #pragma once
 
 #include "conv_p3.h"
 #include "gemm_p3.h"
+#include "gemm_p3i_geom.h"
 
 namespace acme {
 namespace gemm {
 
-template <class G, int FPB = 1>
+// BK_: the stage depth (gemm_p3i.h: one barrier and ring hand-off per stage of BK_ / 32
+// fragment groups, the same sums at any depth).  Only 32 is viable today: at 64 the kernel
+// spills 300 B per lane and takes twice as long.
+
+template <class G, int FPB = 1, int BK_ = 32>
 struct P3SCfg {
   using P = conv::P3ConvDgradSubZ<G>;
   static constexpr int S = G::S, CLASSES = G::S * G::S;
-  static constexpr int MT = 2, NW = 2 * CLASSES * FPB, NT = 64 * NW, BK = 32, KS = 2;
+  static constexpr int MT = 2, NW = 2 * CLASSES * FPB, NT = 64 * NW, GK = 32, KS = 2;
+  static constexpr int BK = BK_, NG = BK / GK;                 // groups per stage
   static constexpr int BN = 32;                                // N = CI
-  static constexpr int H = G::OH, W = G::OW, C = G::CO;        // the dZ image
-  static constexpr int CPX = C / 8;
-  static constexpr int FRAME = H * W * 2 * C;                  // one frame's image, one plane
-  static constexpr int PLANE = FPB * FRAME + 16;               // + the zero unit
+  using GI = ImgGeomSub<G>;                    // the dZ image
+  static constexpr int C = GI::C, CPX = GI::CPX;
+  static constexpr int FRAME = GI::IMG;                        // one frame's image, one plane
+  static constexpr int ZERO = img_zero_base(FPB * FRAME);      // the plane's 16 zero units
+  static constexpr int PLANE = ZERO + kImgZeroBytes;
   static constexpr int NP = kPlanes;
   static constexpr int IMG = NP * PLANE;
-  using PB = PlanP3<BN, 64 * 2 * CLASSES, KCONTIG, NP, BK>;    // one class's B stage
-  static constexpr int STAGE_B = CLASSES * PB::BYTES;
+  using PB = PlanP3<BN, 64 * 2 * CLASSES, KCONTIG, NP, GK>;    // one class's B group
+  static constexpr int GROUP_B = CLASSES * PB::BYTES;
+  static constexpr int STAGE_B = NG * GROUP_B;
   static constexpr int MAIN = IMG + 2 * STAGE_B;
   static constexpr int EPI = NW * 32 * (BN + 4) * 4;
   static constexpr int LDS = MAIN > EPI ? MAIN : EPI;
-  using Core = P3Core<2 * 32 * MT, BN, 2, 1, BK, P>;           // a class's 2 waves x 64 rows
+  using Core = P3Core<2 * 32 * MT, BN, 2, 1, GK, P>;           // a class's 2 waves x 64 rows
   static_assert(G::CI == BN && C == 64 && CPX == 8, "conv2 geometry (CI 32, CO 64)");
-  static constexpr int BT = PB::UNITS * CLASSES;               // B loader threads
+  static constexpr int BT = PB::UNITS * CLASSES;               // B loader threads per group
   static_assert(BT == 64 * 2 * CLASSES, "one B unit per loader thread per plane");
+  static_assert(BK % GK == 0 && NG * BT <= NT, "one B unit per loader thread per plane and stage");
   static_assert(P::KR % BK == 0 && (P::KR / BK) % 2 == 0, "whole, even stage count");
-  __device__ static __forceinline__ int swz(int q) { return (q >> 1) & (CPX - 1); }
 };
 
-template <class G, int FPB>
+template <class G, int FPB, int BK_>
 __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
     const conv::P3ConvDgradSubZ<G> p_in, int frames) {
-  using Cfg = P3SCfg<G, FPB>;
+  using Cfg = P3SCfg<G, FPB, BK_>;
   using PB = typename Cfg::PB;
   using C = typename Cfg::Core;
   using P = conv::P3ConvDgradSubZ<G>;
-  constexpr int NT = Cfg::NT, BK = Cfg::BK, KS = Cfg::KS, MT = Cfg::MT, PLANE = Cfg::PLANE;
-  constexpr int W = Cfg::W, H = Cfg::H, CPX = Cfg::CPX, NP = Cfg::NP;
+  constexpr int NT = Cfg::NT, BK = Cfg::BK, GK = Cfg::GK, NG = Cfg::NG, KS = Cfg::KS, MT = Cfg::MT;
+  constexpr int PLANE = Cfg::PLANE;
+  constexpr int NP = Cfg::NP;
+  using GI = typename Cfg::GI;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fi = wave / (2 * Cfg::CLASSES);  // this wave's frame in the block
   const int f = blockIdx.x * FPB + fi;
   const int z = (wave >> 1) % Cfg::CLASSES, half = wave & 1;  // its class, half of the rows
-  const uint8_t* img = smem + fi * Cfg::FRAME;
   P pz = p_in.for_z(z);
   const int nhw = pz.nh * pz.nw;
   const int m0 = f * nhw;
   pz.M = m0 + nhw < pz.M ? m0 + nhw : pz.M;  // this frame's rows of the class only
   const int nk = P::KR / BK;
 
-  // ---- B: loader thread tid loads unit tid % 128 of class tid / 128's panel (each plane).
-  const bool bload = tid < Cfg::BT;
-  const int bz = bload ? tid / PB::UNITS : 0, bu = tid - bz * PB::UNITS;
+  // ---- B: loader thread tid loads, for group bg = tid / BT of the stage, unit t % 128 of
+  // class t / 128's panel (t = tid % BT; each plane).
+  const bool bload = tid < NG * Cfg::BT;
+  const int bg = bload ? tid / Cfg::BT : 0, bt = tid - bg * Cfg::BT;
+  const int bz = bload ? bt / PB::UNITS : 0, bu = bt - bz * PB::UNITS;
   const P pb = p_in.for_z(bz);
   const typename P::BRow brow = pb.b_row(PB::row_of(bu));
   __amdgpu_buffer_rsrc_t srcB[NP];
@@ -76,7 +88,8 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
   u32x4 rb[2][NP];
   auto fetch_b = [&](auto S_, int k0) {
     constexpr int set = decltype(S_)::value;
-    const uint32_t off = bload && k0 < P::KR ? pb.b_off(brow, k0, PB::kk_of(bu)) : kOOB;
+    const uint32_t off =
+        bload && k0 + bg * GK < P::KR ? pb.b_off(brow, k0 + bg * GK, PB::kk_of(bu)) : kOOB;
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl)
       rb[set][pl] =
@@ -84,7 +97,7 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
   };
   auto stash_b = [&](auto S_, int buf) {
     constexpr int set = decltype(S_)::value;
-    uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B + bz * PB::BYTES;
+    uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B + bg * Cfg::GROUP_B + bz * PB::BYTES;
     if (!bload) return;
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl)
@@ -97,7 +110,7 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
 
   // ---- A: the block's dZ images, each 16-B unit of each plane once.
   {
-    constexpr int UNITS = FPB * H * W * CPX;
+    constexpr int UNITS = FPB * GI::UNITS;
     constexpr int PER = (UNITS + NT - 1) / NT;
     __amdgpu_buffer_rsrc_t srcA[NP];
 #pragma unroll
@@ -106,7 +119,7 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int u = tid + j * NT;
-      const bool ok = u < UNITS && blockIdx.x * FPB + u / (H * W * CPX) < frames;
+      const bool ok = u < UNITS && blockIdx.x * FPB + u / GI::UNITS < frames;
       const uint32_t off = ok ? (uint32_t)(((int64_t)blockIdx.x * UNITS + u) * 16) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl)
@@ -117,56 +130,39 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
     for (int j = 0; j < PER; ++j) {
       const int u = tid + j * NT;
       if (u < UNITS) {
-        const int fu = u / (H * W * CPX), uu = u - fu * (H * W * CPX);
-        const int q = uu / CPX, c = uu - q * CPX;
-        const int a = fu * Cfg::FRAME + q * (2 * Cfg::C) + 16 * (c ^ Cfg::swz(q));
+        const int fu = u / GI::UNITS;
+        const int a = GI::fill(fu, u - fu * GI::UNITS);
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x4*>(smem + pl * PLANE + a) = v[j][pl];
       }
     }
-    if (tid < NP) *reinterpret_cast<u32x4*>(smem + tid * PLANE + PLANE - 16) = zero_u4();
+    if (tid < 16 * NP)
+      *reinterpret_cast<u32x4*>(smem + (tid >> 4) * PLANE + Cfg::ZERO + 16 * (tid & 15)) = zero_u4();
   }
   stash_b(S0{}, 0);
 
-  // ---- This lane's rows: dZ anchor (oh0, ow0) of output pixel (rh + S i, rw + S j).
-  int oh0[MT], ow0[MT];
-  bool rok[MT];
+  // ---- This lane's rows of the class (their dZ anchors).
+  typename GI::Lane ln[MT];
 #pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int lr = half * 32 * MT + i * 32 + (lane & 31);
-    rok[i] = lr < nhw && f < frames;
-    const int ii = rok[i] ? lr / pz.nw : 0, jj = rok[i] ? lr - ii * pz.nw : 0;
-    oh0[i] = (pz.rh + Cfg::S * ii + G::PT - pz.ph) / Cfg::S;
-    ow0[i] = (pz.rw + Cfg::S * jj + G::PL - pz.pw) / Cfg::S;
-  }
+  for (int i = 0; i < MT; ++i)
+    ln[i] = GI::lane(fi, z, half * 32 * MT + i * 32 + (lane & 31), f < frames);
   __syncthreads();
 
   typename C::Acc acc;
   acc.zero();
 
-  auto compute = [&](int k0, int buf) {
-    const uint8_t* sb = smem + Cfg::IMG + buf * Cfg::STAGE_B + z * PB::BYTES;
-    constexpr int T = P::JW * Cfg::C;
-    const int jh = k0 / T, jw = (k0 - jh * T) / Cfg::C;  // wave-uniform
-    const int cb = (k0 % Cfg::C) >> 3;
-    int qb[MT], qs[MT];
+  auto group = [&](int k0, const uint8_t* sb) {
+    typename GI::Stage sg[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int oh = oh0[i] - jh, ow = ow0[i] - jw;
-      const bool in = rok[i] && (unsigned)oh < (unsigned)H && (unsigned)ow < (unsigned)W;
-      const int q = oh * W + ow;
-      qb[i] = in ? q * (2 * Cfg::C) : -1;
-      qs[i] = Cfg::swz(q);
-    }
+    for (int i = 0; i < MT; ++i) sg[i] = GI::stage(ln[i], k0, Cfg::ZERO);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       f16x8 fb[NP];
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) fb[pl] = PB::frag(sb, pl, 0, s, lane);
-      const int c = cb + 2 * s + (lane >> 5);
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        const uint8_t* a = qb[i] >= 0 ? img + qb[i] + 16 * (c ^ qs[i]) : smem + PLANE - 16;
+        const uint8_t* a = smem + GI::unit(sg[i], ln[i], k0, s, lane >> 5);
         f16x8 fa[NP];
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
@@ -174,6 +170,11 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
         acc.terms(i, 0, fa, fb);
       }
     }
+  };
+  auto compute = [&](int k0, int buf) {  // a stage's groups in k order
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      group(k0 + g * GK, smem + Cfg::IMG + buf * Cfg::STAGE_B + g * Cfg::GROUP_B + z * PB::BYTES);
   };
   auto iter = [&](auto S_, int kt) {
     constexpr int set = decltype(S_)::value;
@@ -192,14 +193,14 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
   C::epilogue(pz, smem, m0, 0, wave, half, 0, lane, 0, acc, false);
 }
 
-template <class G, int FPB = 1>
+template <class G, int FPB = 1, int BK_ = 32>
 inline hipError_t launch_gemm_p3s(const conv::P3ConvDgradSubZ<G>& p, int frames, hipStream_t st) {
-  using Cfg = P3SCfg<G, FPB>;
+  using Cfg = P3SCfg<G, FPB, BK_>;
   static_assert(Cfg::LDS <= 160 * 1024, "dZ images + two four-class B stages must fit the LDS");
-  static hipError_t attr = p3_set_lds(&gemm_p3s_kernel<G, FPB>, Cfg::LDS);
+  static hipError_t attr = p3_set_lds(&gemm_p3s_kernel<G, FPB, BK_>, Cfg::LDS);
   if (attr != hipSuccess) return attr;
   if (p.N > Cfg::BN || p.batch != frames || frames < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((gemm_p3s_kernel<G, FPB>), dim3((frames + FPB - 1) / FPB), dim3(Cfg::NT),
+  hipLaunchKernelGGL((gemm_p3s_kernel<G, FPB, BK_>), dim3((frames + FPB - 1) / FPB), dim3(Cfg::NT),
                      Cfg::LDS, st, p, frames);
   return hipGetLastError();
 }

@@ -811,7 +811,7 @@ __device__ __forceinline__ void store_shared_level(double* p, double v) {
 }
 // R: updates per thread the launch holds (n <= 256 R).  The small form (R = 2, up to 512
 // updates: a DQN batch) takes 21 KB of LDS and few registers, so its workgroups fit beside
-// the next step's target forward (gemm_p3c12_kernel, 121 KB of LDS per CU), which the
+// the next step's target forward (gemm_p3c12_kernel, 117 KB of LDS per CU), which the
 // early start runs at the same time on the side stream; at R = 16 (49 KB, 200 VGPRs) they
 // waited for its blocks to retire (24 us in the two-stream trace against 12 us alone,
 // profiles/r06/schedule/).

@@ -88,8 +88,10 @@ struct Frames {
 // keep_x1: frames [0, keep_x1) get their conv1 output x1 in HBM (the backward reads it);
 // -1: all.  With the fused conv1 -> conv2 kernel (gemm_p3c12.h, used when
 // keep_x1 == 0) x1 only lives in LDS.
+// bk32: the image-resident kernels at a stage depth of 32 k instead of each kernel's own
+// (the same bits; tests, ACME_V_BK32=1 at the learner's creation).
 int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a,
-               hipStream_t st, int keep_x1 = -1);
+               hipStream_t st, int keep_x1 = -1, bool bk32 = false);
 // Optional second stream for the weight gradients: conv3 / conv2 weight gradients run on
 // `side` (with their own split-K slab) beside the input gradients on the main stream;
 // events e[0..2] are scratch (hipEventDisableTiming).  side == nullptr: one stream.
@@ -117,6 +119,7 @@ struct Side {
   // (the same bits; tests, ACME_V_WSN=1 at the learner's creation).
   bool single_role = false;
   bool conv1_single = false;  // conv1's weight gradient on the single-role kernel (the DQN step)
+  bool bk32 = false;          // the image-resident input gradients at a stage depth of 32 k
 };
 // dz3: conv3's dZ planes [rows][kFlat] (masked); dz2 / dz1 plane scratch.
 int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int rows,

@@ -126,14 +126,28 @@ constexpr int kP3Conv1WgradSplits = 512, kP3Conv2WgradSplits = 128, kP3Conv3Wgra
 constexpr int kP3MaxWgradSplits = 512;
 
 // Image-resident convolution (gemm_p3i.h): FPB frames per block, WM x WN waves of 32*MT
-// rows; `frames` images.
+// rows, stage depth BK; `frames` images.
 using I1F = gemm::ImgGeomPairs<G1>;
 using I2F = gemm::ImgGeom<G2, false>;
 using I3F = gemm::ImgGeom<G3, false>;
 using I3D = gemm::ImgGeom<G3, true>;
-#define P3I_GEMM(name, GI, FPB, BN, WM, WN, MT, prob, frames)                                 \
+#define P3I_GEMM(name, GI, FPB, BN, WM, WN, MT, BK, prob, frames)                             \
   ACME_LAUNCH_GEMM(name, ACME_MNK_FLOPS(prob), gemm::p3_peak_tflops<decltype(prob)>(),        \
-                   (gemm::launch_gemm_p3i<GI, FPB, BN, WM, WN, MT>(prob, frames, st)))
+                   (gemm::launch_gemm_p3i<GI, FPB, BN, WM, WN, MT, BK>(prob, frames, st)))
+// The same launch at the kernel's own stage depth, or at 32 k (bk32: the same bits).
+#define P3I_GEMM_BK(name, GI, FPB, BN, WM, WN, MT, BK, bk32, prob, frames) \
+  do {                                                                     \
+    if (bk32) P3I_GEMM(name, GI, FPB, BN, WM, WN, MT, 32, prob, frames);   \
+    else P3I_GEMM(name, GI, FPB, BN, WM, WN, MT, BK, prob, frames);        \
+  } while (0)
+
+// Stage depths (k per barrier and ring hand-off) of the image-resident kernels, chosen by
+// alternating runs of the step within each kernel's LDS budget (conv1_fwd <= 80 KB and
+// conv3_fwd two blocks per CU, the others one; DESIGN 4.1, profiles/r07/p3i): conv3_fwd and
+// conv2_dgrad leave 128 VGPRs or spill at 64, the fused kernel's conv1 half gains nothing.
+constexpr int kBkConv1 = 64, kBkConv2 = 64, kBkConv3 = 32;
+constexpr int kBkConv3Dgrad = 128, kBkConv2Dgrad = 32;
+constexpr int kBkFused1 = 32, kBkFused2 = 64;  // conv12_fwd's two halves
 
 inline PlaneSrc frames_src(const Frames& f, int rows) {
   return PlaneSrc{static_cast<const uint16_t*>(f.p), 0,
@@ -143,7 +157,7 @@ inline PlaneSrc frames_src(const Frames& f, int rows) {
 // conv1 forward (image-resident) over `rows` frames into y, f16 or uint8 frames.
 template <bool U8>
 int conv1_fwd_p3(const PWeights& w, const Frames& frames, int rows, const Planes& y,
-                 hipStream_t st, uint64_t* stamps = nullptr) {
+                 hipStream_t st, bool bk32, uint64_t* stamps = nullptr) {
   P3ConvFwd<G1, 1, U8> p;
   p.stamps = stamps;
   p.M = rows * G1::OPIX; p.N = G1::CO; p.K = G1::K; p.k_chunk = G1::K;
@@ -156,14 +170,14 @@ int conv1_fwd_p3(const PWeights& w, const Frames& frames, int rows, const Planes
   p.bias = w.b1; p.y = y;
   // Image-resident frames (gemm_p3i.h pixel pairs): 39.6 -> 33.7 us vs the best im2col
   // tiling.
-  P3I_GEMM("conv1_fwd", I1F, 1, 32, 7, 1, 2, p, rows);
+  P3I_GEMM_BK("conv1_fwd", I1F, 1, 32, 7, 1, 2, kBkConv1, bk32, p, rows);
   return ACME_OK;
 }
 
 // The fused conv1 -> conv2 forward (gemm_p3c12.h) over frames [nsep, rows).
 template <bool U8>
 int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, const PActs& a,
-                  hipStream_t st) {
+                  hipStream_t st, bool bk32) {
   const int nf = rows - nsep;
   const Frames fr = frames.rows_from(nsep);
   if (U8 && fr.split < nf)
@@ -181,7 +195,8 @@ int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, c
   p2.y = Planes{a.x2.p + (int64_t)nsep * kFlat, a.x2.stride, a.x2.sc};
   const double fl = 2.0 * p1.M * p1.N * (double)p1.K + 2.0 * p2.M * p2.N * (double)p2.K;
   ACME_PROF_PEAK("conv12_fwd", st, fl, 0.0, gemm::p3_peak_tflops<decltype(p2)>());
-  hipError_t e = gemm::launch_gemm_p3c12(p1, p2, nf, 0, st);
+  hipError_t e = bk32 ? gemm::launch_gemm_p3c12<32, 32>(p1, p2, nf, 0, st)
+                      : gemm::launch_gemm_p3c12<kBkFused1, kBkFused2>(p1, p2, nf, 0, st);
   if (e != hipSuccess) return (set_error("gemm launch failed: %s", hipGetErrorString(e)), ACME_ERR_HIP);
   return ACME_OK;
 }
@@ -224,7 +239,7 @@ int64_t wgrad_slab_floats_p3() {
 }
 
 int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a,
-               hipStream_t st, int keep_x1) {
+               hipStream_t st, int keep_x1, bool bk32) {
   // Frames [0, nsep) run conv1 then conv2 with x1 in HBM (the backward reads it); frames
   // [nsep, rows) the fused conv1 -> conv2 kernel (gemm_p3c12.h), whose x1 stays in LDS.
   // The target forward (keep_x1 == 0, on the side stream) is fused throughout: 0.716 ->
@@ -234,11 +249,11 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
   const int nsep = keep_x1 == 0 ? 0 : rows;
   int rc;
   if (nsep < rows &&
-      (rc = frames.u8 ? conv12_fwd_p3<true>(w, frames, rows, nsep, a, st)
-                      : conv12_fwd_p3<false>(w, frames, rows, nsep, a, st)) != ACME_OK)
+      (rc = frames.u8 ? conv12_fwd_p3<true>(w, frames, rows, nsep, a, st, bk32)
+                      : conv12_fwd_p3<false>(w, frames, rows, nsep, a, st, bk32)) != ACME_OK)
     return rc;
-  if (nsep > 0 && (rc = frames.u8 ? conv1_fwd_p3<true>(w, frames, nsep, PP(a.x1), st, g_stamps_conv[0])
-                                  : conv1_fwd_p3<false>(w, frames, nsep, PP(a.x1), st, g_stamps_conv[0])) != ACME_OK)
+  if (nsep > 0 && (rc = frames.u8 ? conv1_fwd_p3<true>(w, frames, nsep, PP(a.x1), st, bk32, g_stamps_conv[0])
+                                  : conv1_fwd_p3<false>(w, frames, nsep, PP(a.x1), st, bk32, g_stamps_conv[0])) != ACME_OK)
     return rc;
   if (nsep > 0) {
     P3ConvFwd<G2, gemm::kPlanes> p;
@@ -250,7 +265,7 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
     // planes a frame's x1 image is 56 KB, so two frames and the weight ring fit one CU.
     // Step 0.573 -> 0.551 ms against the producer / consumer im2col kernel (two alternating
     // runs each, one box; one frame per block: 0.571).
-    P3I_GEMM("conv2_fwd", I2F, 2, 64, 8, 2, 1, p, nsep);
+    P3I_GEMM_BK("conv2_fwd", I2F, 2, 64, 8, 2, 1, kBkConv2, bk32, p, nsep);
   }
   {
     P3ConvFwd<G3, gemm::kPlanes> p;
@@ -260,7 +275,7 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
     if (keep_x1 != 0) p.stamps = g_stamps_conv[2];  // the online forward's
     // Image-resident, 4 x 2 waves (measured 50.1 -> 43.5 us vs the 128x64 im2col engine;
     // two frames per block measured slower on the step, 0.550 -> 0.568-0.618 ms).
-    P3I_GEMM("conv3_fwd", I3F, 1, 64, 4, 2, 1, p, rows);
+    P3I_GEMM_BK("conv3_fwd", I3F, 1, 64, 4, 2, 1, kBkConv3, bk32, p, rows);
   }
   return ACME_OK;
 }
@@ -302,7 +317,7 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     p.a_src = SRC(dz3, (int64_t)rows * kFlat); p.b_src = SRC(w.w3, G3::K * G3::CO);
     p.xprev = CP(a.x2); p.dx = PP(dz2);
     // Image-resident dZ, two frames x 8 x 2 waves: 37.4 us (128x64 im2col) -> 31.2 us.
-    P3I_GEMM("conv3_dgrad", I3D, 2, 64, 8, 2, 1, p, rows);
+    P3I_GEMM_BK("conv3_dgrad", I3D, 2, 64, 8, 2, 1, kBkConv3Dgrad, sd.bk32, p, rows);
   }
   if (fork) {
     ACME_HIP_TRY(hipEventRecord(sd.e[1], st_main));
@@ -334,7 +349,8 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     // 57.7 us (128x32 im2col) -> 38.0 (one frame per block) -> 34.7 us.
     const double fl = 2.0 * rows * G2::IPIX * G2::CI * (double)p.K;
     ACME_PROF_PEAK("conv2_dgrad", st, fl, 0.0, gemm::p3_peak_tflops<decltype(p)>());
-    hipError_t e = gemm::launch_gemm_p3s<G2, 2>(p, rows, st);
+    hipError_t e = sd.bk32 ? gemm::launch_gemm_p3s<G2, 2, 32>(p, rows, st)
+                           : gemm::launch_gemm_p3s<G2, 2, kBkConv2Dgrad>(p, rows, st);
     if (e != hipSuccess) return (set_error("gemm launch failed: %s", hipGetErrorString(e)), ACME_ERR_HIP);
   }
   {  // conv1 (no input gradient)
