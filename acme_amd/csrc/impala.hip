@@ -61,6 +61,11 @@ struct acme_impala : RecurrentNet {
   // Policy steps of an actor-side network on the plane engine (acme_impala_set_policy_planes):
   // the torso and W_i on f16 planes, the records rescaled after every call.
   bool policy_planes = false;
+  // The forward records are calibrated for policy steps (their three T = 1 passes, or a
+  // learner step's calibration: scales_ok).  Not scales_ok itself: a policy step measures no
+  // backward record, and a learner step that found scales_ok set would run its backward at
+  // the initial scales and be skipped.
+  bool policy_scales_ok = false;
   // Plane path of the Atari learner step (RecurrentNet; the DQN kernels): the f16 frames.
   bool p3_capable = false;
   uint16_t* frames = nullptr;
@@ -604,13 +609,13 @@ int acme_impala_bind(acme_impala* l, float* params, float* grads, float* adam_m,
   l->grads = grads;
   l->m = adam_m;
   l->v = adam_v;
-  l->scales_ok = false;
+  l->scales_ok = l->policy_scales_ok = false;
   return ACME_OK;
 }
 
 int acme_impala_params_changed(acme_impala* l) {
   ACME_CHECK_ARG(l, "null learner");
-  l->scales_ok = false;
+  l->scales_ok = l->policy_scales_ok = false;
   return ACME_OK;
 }
 
@@ -662,13 +667,14 @@ int acme_impala_policy_step(acme_impala* l, const void* obs, const int32_t* prev
                                 -1, -1, rg);
   };
   int rc;
-  if (p3 && !l->scales_ok) {
+  if (p3 && !l->scales_ok && !l->policy_scales_ok) {
     // First call (or new parameters): three passes set the chain frames -> x1 -> x2 -> x3
-    // (and the parameter planes) from real maxima before the call whose outputs count.
+    // (and the parameter planes) from real maxima before the call whose outputs count.  The
+    // backward's records stay uncalibrated: a learner step still runs its own calibration.
     for (int pass = 0; pass < 3; ++pass)
       if ((rc = forward()) != ACME_OK) return rc;
     ACME_HIP_TRY(hipMemsetAsync(l->overflow, 0, sizeof(int), st));
-    l->scales_ok = true;
+    l->policy_scales_ok = true;
   }
   if ((rc = forward()) != ACME_OK) return rc;
   // Outputs are rows of the T = 1 unroll.
@@ -688,7 +694,7 @@ int acme_impala_policy_step(acme_impala* l, const void* obs, const int32_t* prev
 int acme_impala_set_policy_planes(acme_impala* l, int32_t on) {
   ACME_CHECK_ARG(l, "null learner");
   l->policy_planes = on != 0;
-  l->scales_ok = false;
+  l->scales_ok = l->policy_scales_ok = false;
   return ACME_OK;
 }
 

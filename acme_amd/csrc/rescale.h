@@ -10,7 +10,9 @@
 // scale.  A record whose maximum is not finite (planes computed from overflowed planes) takes
 // the largest scale reduction of the group's overflowed records with a finite maximum (its
 // inputs shrink by that factor at their new scale), else 2^-16.  overflow |= 1 when a write
-// exceeded f16's range (amax w >= 65520) or was not finite.
+// exceeded f16's range (amax w >= 65520) or was not finite.  In q_values' job (kRgQValues: a
+// forward chain in record order) every record after the first overflowed one takes that
+// record's reduction, whatever maximum it measured (see rescale_block).
 //
 // defer_r: the transient records' read scale r is NOT moved (w, wi and rl are): consumers
 // still running on another stream read the planes stored now at r; the step's Adam launch
@@ -137,7 +139,23 @@ __device__ __forceinline__ void rescale_block(const RescaleJob& j) {
     const bool persistent = i >= j.nt;
     const float stored = persistent ? wi0 : r0;  // the read scale of the planes stored now
     gemm::PScale* rec = s + i;
-    if (a == 0.f) {  // no maximum taken: the scale stays
+    // q_values' records are a forward chain (T1 -> T2 -> T3), and its caller repeats an
+    // overflowed call once.  A record after the first overflowed one was computed from
+    // overflowed planes: the conv epilogues' ReLU turns those NaNs into zeros, so its maximum
+    // is that of garbage (0, or too small) and says nothing.  It takes the overflowed
+    // record's reduction instead (its inputs shrink by that factor at their new scale), so
+    // the repeated call finds every record of the chain at a scale that fits.
+    int up = 0;
+    if (rg.mode == kRgQValues)
+      for (int k = 0; k < i && up == 0; ++k) up = min(up, s_shift[k]);
+    if (up < 0) {
+      rec->w = ldexpf(w0, up);
+      const float wi = ldexpf(wi0, -up);
+      rec->wi = wi;
+      rec->rl = stored;
+      if (persistent) rec->r = stored;
+      else if (!j.defer_r) rec->r = wi;
+    } else if (a == 0.f) {  // no maximum taken: the scale stays
       if (persistent) rec->r = rec->rl = stored;
       else rec->rl = stored;
     } else {

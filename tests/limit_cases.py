@@ -116,6 +116,27 @@ def swap_columns(params, names, j, k):
     return out
 
 
+# ------------------------------------------------------------------ DQN acting (q_values)
+
+# Frames an actor really sends (tests/test_acting_gpu.py; shown to produce their edge, or not,
+# on the oracle alone by tests/test_acting_cpu.py).  id -> (frames, value, biased):
+# black frames under net.init's zero biases (every torso activation and the hidden layer are
+# identically zero, so the target activations' scale records see a maximum of 0), the same
+# frames under dqn_params' non-zero biases (no activation tensor is zero), and one saturated
+# frame.
+DQN_ACTING_EDGES = {"black_zero_bias": (3, 0, False), "black_biased": (3, 0, True),
+                    "saturated": (1, 255, True)}
+
+
+def dqn_acting_edge(name):
+    """-> net, params, target, frames (uint8 [n, 84, 84, 4])."""
+    from acme_amd.networks import DQNAtariNetwork
+    n, value, biased = DQN_ACTING_EDGES[name]
+    net = DQNAtariNetwork(18)
+    draw = dqn_params if biased else (lambda net_, seed: net_.init(seed))
+    return net, draw(net, 1), draw(net, 2), np.full((n,) + net.obs_shape, value, np.uint8)
+
+
 # ------------------------------------------------------------------ IMPALA
 
 # Flat torso, obs_dim 12.  B, T, H (lstm_size), A; head: head_size (default 16); kw: learner
