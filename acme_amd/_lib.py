@@ -233,6 +233,8 @@ _SIGS = {
     "acme_replay_capacity": (c_i64, [c_vp]),
     "acme_replay_debug_leaves": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                          ctypes.POINTER(c_vp)]),
+    "acme_replay_debug_level": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_vp),
+                                        ctypes.POINTER(c_i64), ctypes.POINTER(c_i32)]),
     "acme_replay_storage": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
     "acme_replay_inserted": (c_i64, [c_vp]),
     "acme_replay_restore": (c_i32, [c_vp, c_i64, c_vp]),
@@ -250,6 +252,7 @@ _SIGS = {
     "acme_dqn_skipped_steps": (c_i64, [c_vp]),
     "acme_dqn_guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_dqn_verdict_timeouts": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
+    "acme_dqn_update_rider_launches": (c_i64, [c_vp]),
     "acme_dqn_set_applied_steps": (c_i32, [c_vp, c_i64]),
     "acme_dqn_skip_word": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
     "acme_dqn_set_reissue": (c_i32, [c_vp, c_i32]),

@@ -20,8 +20,8 @@ namespace acme {
 void set_error(const char* fmt, ...);
 
 // Tile / schedule variant for tuning runs: ACME_V_<KEY>=<n> in the environment (read once
-// per key); 0 is the shipped default.
-int tune_variant(const char* key);
+// per key); 0 is the shipped default, or `unset` for a key whose 0 switches something off.
+int tune_variant(const char* key, int unset = 0);
 void tune_set(const char* key, int value);
 // Incremented by every tune_set: cached launch plans (captured graphs) keyed on it.
 int tune_generation();

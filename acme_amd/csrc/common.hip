@@ -29,12 +29,12 @@ int tune_generation() {
   return g_tune_gen;
 }
 
-int tune_variant(const char* key) {
+int tune_variant(const char* key, int unset) {
   std::lock_guard<std::mutex> lock(g_tune_mu);
   for (auto& kv : g_tune)
     if (kv.first == key) return kv.second;
   const char* v = getenv((std::string("ACME_V_") + key).c_str());
-  const int x = v ? atoi(v) : 0;
+  const int x = v ? atoi(v) : unset;
   g_tune.emplace_back(key, x);
   return x;
 }

@@ -33,6 +33,7 @@
 #include "launch.h"
 #include "learner_common.h"
 #include "plane_guard.h"
+#include "prio_update.h"
 #include "profiler.h"
 #include "rccl_dyn.h"
 #include "torso.h"
@@ -154,6 +155,13 @@ struct acme_dqn : PlaneGuard {
   bool single_stream = false;
   bool single_role = false;
   bool bk32 = false;
+  // The fused step's priority write-back as the leading workgroups of conv1's weight-gradient
+  // launch (prio_update.h UpdateRider) instead of a launch of its own after it
+  // (ACME_V_UPDATE_RIDER=0 at creation: the separate launch; the same bits).
+  bool update_rider = true;
+  int rider_groups = kUpdateRiderBlocks;  // its update workgroups (ACME_V_RIDER_GROUPS: A/B runs)
+  acme_replay* rider_replay = nullptr;  // locked between the rider's prepare and its launch
+  int64_t rider_launches = 0;
   // conv1 reads the batch's uint8 frames (unless the batch carries the f16 copy, obs_f16, or
   // the frames are not 16-byte aligned: then the step makes the f16 copy, the round-4 path)
   bool frames_u8 = true;
@@ -444,6 +452,34 @@ int priority_update_tail(void* ctx, hipStream_t st) {
   return rc;
 }
 
+// The same write-back as a rider of conv1's weight-gradient launch (torso::Side::tail_rider):
+// the waits and the arguments now, before that launch; the update's workgroups then lead its
+// grid.  Armed for the fused step's batches of at most kUpdateRiderMax updates; otherwise
+// nothing is consumed and priority_update_tail runs after the launch as before.
+int priority_update_rider(void* ctx, hipStream_t st, FusedUpdateArgs* out, bool* armed) {
+  acme_dqn* l = static_cast<acme_dqn*>(ctx);
+  acme_replay* r = l->upd_replay;
+  *armed = false;
+  if (!r || !l->upd_prio || l->upd_n < 1 || l->upd_n > kUpdateRiderMax) return ACME_OK;
+  if (l->upd_after) ACME_HIP_TRY(hipStreamWaitEvent(st, l->upd_after, 0));
+  const RescaleJob job = step_rescale_job(l, true);
+  const int rc = replay_update_prepare(r, l->upd_keys, l->upd_prio, l->upd_n, step_gate(l), st,
+                                       &job, l->rider_groups, out);
+  if (rc != ACME_OK) return rc;
+  l->upd_replay = nullptr;
+  l->rider_replay = r;
+  l->rider_launches += 1;
+  l->step_rescaled = true;
+  *armed = true;
+  return ACME_OK;
+}
+
+void priority_update_rider_done(void* ctx) {
+  acme_dqn* l = static_cast<acme_dqn*>(ctx);
+  if (l->rider_replay) replay_update_release(l->rider_replay);
+  l->rider_replay = nullptr;
+}
+
 // join_dense: the caller's stream waits for the side stream's dense weight gradients
 // before returning (stage 0 of a data-parallel step all-reduces them next); otherwise the
 // torso backward's final join covers them.
@@ -666,6 +702,8 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
   l->single_stream = tune_variant("SIDE") == 1;
   l->single_role = tune_variant("WSN") == 1;
   l->bk32 = tune_variant("BK32") == 1;
+  l->update_rider = tune_variant("UPDATE_RIDER", kUpdateRiderDefault) != 0;
+  l->rider_groups = std::clamp(tune_variant("RIDER_GROUPS", kUpdateRiderBlocks), 1, 1024);
   l->stamps_on = tune_variant("STAMPS") == 1;
   const int A = cfg->num_actions;
   const int B = cfg->max_batch;
@@ -895,6 +933,8 @@ int acme_dqn_verdict_timeouts(acme_dqn* l, int64_t* out) {
   return ACME_OK;
 }
 
+int64_t acme_dqn_update_rider_launches(const acme_dqn* l) { return l ? l->rider_launches : 0; }
+
 int acme_dqn_set_reissue(acme_dqn* l, int32_t enable) {
   ACME_CHECK_ARG(l, "null learner");
   l->sticky = enable != 0 && l->p3_capable;
@@ -1111,6 +1151,10 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
       if (l->upd_replay && l->upd_prio && !l->calibrating) {
         sd.tail = priority_update_tail;
         sd.tail_ctx = l;
+        if (l->update_rider && l->fused_step && !l->dp_gate) {
+          sd.tail_rider = priority_update_rider;
+          sd.tail_rider_done = priority_update_rider_done;
+        }
       }
       if (l->fused_step && !l->calibrating && l->slab2) {
         sd.slab = l->side_slab;

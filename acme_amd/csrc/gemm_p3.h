@@ -67,11 +67,11 @@ namespace gemm {
 struct BlockPlace {
   int m0, n0, z;
 };
+// orig: the block's flat index in dispatch order among `total` = tiles x splits blocks (its
+// XCD is orig & 7 when the launch's blocks before the first of them are a multiple of 8).
 template <int BM, int BN>
-__device__ __forceinline__ BlockPlace place_block(int M, int N, int n_major) {
-  const int tiles = gridDim.x;
-  const int total = tiles * gridDim.z;
-  const int orig = blockIdx.x + tiles * blockIdx.z;
+__device__ __forceinline__ BlockPlace place_block_at(int orig, int tiles, int total, int M, int N,
+                                                     int n_major) {
   const int xcd = orig & 7, q = total >> 3, r = total & 7;
   const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   const int z = L / tiles, t = L - z * tiles;
@@ -85,6 +85,12 @@ __device__ __forceinline__ BlockPlace place_block(int M, int N, int n_major) {
     nt = t - mt * tiles_n;
   }
   return BlockPlace{mt * BM, nt * BN, z};
+}
+template <int BM, int BN>
+__device__ __forceinline__ BlockPlace place_block(int M, int N, int n_major) {
+  const int tiles = gridDim.x;
+  return place_block_at<BM, BN>(blockIdx.x + tiles * blockIdx.z, tiles, tiles * gridDim.z, M, N,
+                                n_major);
 }
 template <class P>
 __device__ __forceinline__ P z_select_at(const P& p, int z) {
@@ -663,15 +669,16 @@ struct P3Core {
 
 // Register-staged kernel: global -> VGPR -> LDS, two LDS stages; with DEEP two register
 // sets so a stage's loads are issued two stages before its compute.
+// (The block's work as a function of its placement, shared by gemm_p3_kernel and
+// gemm_p3r_kernel below.)
 template <int BM, int BN, int WM, int WN, int BK, bool DEEP, class P>
-__global__ void __launch_bounds__(64 * WM * WN) gemm_p3_kernel(const P p_in, int n_major) {
+__device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& bp,
+                                              uint8_t* smem) {
   using C = P3Core<BM, BN, WM, WN, BK, P>;
   using PA = typename C::PA;
   using PB = typename C::PB;
   constexpr int NT = C::NT, NPA = C::NPA, NPB = C::NPB, STAGE = C::STAGE;
-  const BlockPlace bp = place_block<BM, BN>(p_in.M, p_in.N, n_major);
   const P p = z_select_at(p_in, bp.z);
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -812,6 +819,36 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3_kernel(const P p_in, int
     }
   }
   C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, split, acc, do_colsum);
+}
+
+template <int BM, int BN, int WM, int WN, int BK, bool DEEP, class P>
+__global__ void __launch_bounds__(64 * WM * WN) gemm_p3_kernel(const P p_in, int n_major) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  gemm_p3_block<BM, BN, WM, WN, BK, DEEP, P>(
+      p_in, place_block<BM, BN>(p_in.M, p_in.N, n_major), smem);
+}
+
+// The same GEMM behind a leading rider: work of another kind that takes the launch's first
+// R::blocks(ra) workgroups in dispatch order (a multiple of 8, so the GEMM's blocks keep the
+// XCDs place_block_at assumes) and runs in the launch's dynamic LDS, before any stage is
+// written there by that workgroup's threads (a rider workgroup does no GEMM work).  The GEMM's
+// blocks are placed by their index minus the rider's count and never wait for a rider
+// workgroup.  R: Args, kThreads (= the GEMM's), kLdsBytes (<= the GEMM's), blocks(Args),
+// run(Args, lds, workgroup).  A 1-D grid: rider blocks, then tiles x splits.
+template <int BM, int BN, int WM, int WN, int BK, bool DEEP, class P, class R>
+__global__ void __launch_bounds__(64 * WM * WN)
+    gemm_p3r_kernel(const P p_in, int n_major, int tiles, const typename R::Args ra) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int nr = R::blocks(ra);
+  if ((int)blockIdx.x < nr) {
+    R::run(ra, smem, (int)blockIdx.x);
+    return;
+  }
+  gemm_p3_block<BM, BN, WM, WN, BK, DEEP, P>(
+      p_in,
+      place_block_at<BM, BN>((int)blockIdx.x - nr, tiles, (int)gridDim.x - nr, p_in.M, p_in.N,
+                             n_major),
+      smem);
 }
 
 // LDS-DMA kernel: every operand unit goes HBM -> LDS by buffer_load ... lds (no VGPR
@@ -1158,6 +1195,25 @@ inline hipError_t launch_gemm_p3(const P& p, int splits, hipStream_t st) {
   const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
   hipLaunchKernelGGL((gemm_p3_kernel<BM, BN, WM, WN, BK, DEEP, P>), dim3(tiles, 1, splits),
                      dim3(C::NT), LDS, st, p, p3_n_major(p));
+  return hipGetLastError();
+}
+
+// launch_gemm_p3 with a leading rider (gemm_p3r_kernel): the grid grows by R::blocks(ra).
+template <int BM, int BN, int WM, int WN, int BK, class R, bool DEEP = true, class P>
+inline hipError_t launch_gemm_p3_rider(const P& p, int splits, const typename R::Args& ra,
+                                       hipStream_t st) {
+  using C = P3Core<BM, BN, WM, WN, BK, P>;
+  constexpr int STAGES_BYTES = 2 * C::STAGE;
+  constexpr int LDS = STAGES_BYTES > C::EPI_BYTES ? STAGES_BYTES : C::EPI_BYTES;
+  static_assert(LDS <= 160 * 1024, "two stages must fit the 160-KiB LDS of a CU");
+  static_assert(R::kLdsBytes <= LDS, "the rider runs in the GEMM's LDS");
+  static_assert(R::kThreads == C::NT, "the rider's workgroup size is the GEMM's");
+  static hipError_t attr = p3_set_lds(&gemm_p3r_kernel<BM, BN, WM, WN, BK, DEEP, P, R>, LDS);
+  if (attr != hipSuccess) return attr;
+  const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
+  hipLaunchKernelGGL((gemm_p3r_kernel<BM, BN, WM, WN, BK, DEEP, P, R>),
+                     dim3(R::blocks(ra) + tiles * splits), dim3(C::NT), LDS, st, p,
+                     p3_n_major(p), tiles, ra);
   return hipGetLastError();
 }
 

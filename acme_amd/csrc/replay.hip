@@ -37,6 +37,7 @@
 #include "common.h"
 #include "detmath.h"
 #include "kernels.h"
+#include "prio_update.h"
 #include "profiler.h"
 #include "rescale.h"
 
@@ -134,37 +135,6 @@ __device__ __forceinline__ double wave_scan64(double x) {
     if (lane >= d) x = y + x;
   }
   return x;
-}
-
-// The scan's total (its lane-63 value) in every lane, with the same bits: lane 63 of the
-// scan adds aligned blocks pairwise (round d: the block of d lanes ending at 63 - d to the one
-// ending at 63), and so does this butterfly (each round adds the aligned neighbour block of
-// the same size; f64 addition is commutative).  DPP moves for blocks of 1..8 lanes, a swizzle
-// for 16 and two lane reads for 32 replace six rounds of LDS permutes.  The whole wave must
-// be active (as for wave_scan64).
-template <int Ctrl>
-__device__ __forceinline__ double dpp_f64(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, Ctrl, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), Ctrl, 0xf, 0xf, false);
-  return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-__device__ __forceinline__ double wave_total64(double x) {
-  x = x + dpp_f64<0xB1>(x);   // quad_perm [1,0,3,2]: pairs
-  x = x + dpp_f64<0x4E>(x);   // quad_perm [2,3,0,1]: quads
-  x = x + dpp_f64<0x141>(x);  // row_half_mirror: blocks of 8
-  x = x + dpp_f64<0x140>(x);  // row_mirror: blocks of 16
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_ds_swizzle((int)(uint32_t)u, 0x401F);  // lane ^ 16
-  const int hi = __builtin_amdgcn_ds_swizzle((int)(uint32_t)(u >> 32), 0x401F);
-  x = x + __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  const uint64_t v = __builtin_bit_cast(uint64_t, x);
-  const uint32_t a0 = __builtin_amdgcn_readlane((int)(uint32_t)v, 31);
-  const uint32_t a1 = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 31);
-  const uint32_t b0 = __builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-  const uint32_t b1 = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-  return __builtin_bit_cast(double, ((uint64_t)a1 << 32) | a0) +
-         __builtin_bit_cast(double, ((uint64_t)b1 << 32) | b0);
 }
 
 __device__ __forceinline__ int select_child(double v, double s, double t) {
@@ -736,340 +706,14 @@ __global__ void prio_reset_kernel(const int64_t* __restrict__ slots,
   winner[slots[j]] = -1;
 }
 
-// update_priorities in ONE launch.  Updates are partitioned over the workgroups by their
-// ancestor at level h = nlevels - 2 (owner = slot >> 6h, workgroup owner % G), so every
-// update of a slot, and every touched node of levels 1..h, belongs to exactly one workgroup:
-// it elects the last valid update per slot in LDS (largest j wins, Reverb's in-order
-// application) and computes its leaves p^alpha and its nodes of levels 1..h.  The children
-// of those nodes are loaded up front (one round of loads issued together right after the
-// keys are resolved), the new values substituted in LDS and each node rescanned from LDS, so
-// no store has to be read back.  The top level (whose children many workgroups write) is
-// rescanned by the LAST workgroup to finish: the level-h values are stored write-through
-// (agent-scope atomic stores, drained before the workgroup counts itself) and read back by
-// agent-scope atomic loads, the hand-off form that needs no L2 writeback or invalidate
-// (cdna_hip_programming.md G16), so the update is one launch instead of two (round 4: a
-// 10.2 us kernel + a 5.2 us one-workgroup launch for the top level).
-constexpr int kFusedUpdateMax = 4096;
-constexpr int kFusedUpdateBlocks = 256;
-constexpr int kUpdPairs = 32;  // (level, node) pairs a workgroup prefetches; else read back
-struct FusedUpdateArgs {
-  const uint64_t* upd_keys;
-  const double* prios;
-  int n;
-  int64_t capacity;
-  const uint64_t* keys;
-  double alpha;
-  double* raw_prio;
-  double* level[8];
-  int64_t top_nodes;  // nodes of level nlevels - 2 (the top level's entries that have children)
-  int top_computed;   // readers compute the top level (computed_top_nodes > 0): not stored
-  int nlevels;
-  uint32_t* done;     // workgroups finished (the last one rescans the top; it resets the count)
-  Gate gate;  // a learner step that was skipped writes no priority
-  // job.s: the learner step's rescale, run by workgroup 0 (the update workgroups are 1..G).
-  // With a step verdict (kRgStep) the update workgroups wait for it (StepGuard::vseq) and
-  // write nothing when the step was skipped, for every reason the rescale decides
-  // (overflow, underflow, a timed-out unroll, the sticky hold, another rank's skip).
-  RescaleJob job;
-  // Timing experiment (ACME_V_STAMPS=1 in the DQN learner, tools/update_stamps.py): thread 0 of
-  // each workgroup stores s_memrealtime (100 MHz) at its phase boundaries, 8 slots per
-  // workgroup: entry, keys resolved (workgroup 0: rescale done), node list, verdict, leaves,
-  // levels, exit.
-  uint64_t* stamps = nullptr;
-};
-// Waits (bounded) for the verdict with sequence number seq; true when that step is skipped
-// (or the wait timed out: no priority is written, and the timeout is counted in
-// g->vtimeout, which the host reads: acme_dqn_verdict_timeouts).  Workgroup 0 of the same
-// launch publishes it and was dispatched first, so it is resident or done.
-// `first`: thread 0's load of g->vseq issued earlier (its latency overlapped the caller's LDS
-// work); polled again only when it did not yet hold this step's verdict.
-__device__ __forceinline__ bool wait_verdict_skip(StepGuard* g, uint32_t seq, uint32_t first) {
-  __shared__ uint32_t s_v;
-  if (threadIdx.x == 0) {
-    uint32_t v = first;
-    for (int it = 0; it < (1 << 22) && (v >> 1) != (seq & 0x7fffffffu); ++it) {
-      __builtin_amdgcn_s_sleep(2);
-      v = __hip_atomic_load(&g->vseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const bool got = (v >> 1) == (seq & 0x7fffffffu);
-    if (!got) atomicAdd(&g->vtimeout, 1u);
-    s_v = got ? (v & 1u) : 1u;
-  }
-  __syncthreads();
-  return s_v != 0u;
-}
-// A workgroup barrier that orders LDS only: outstanding global loads stay in flight across it
-// (__syncthreads also waits for every vector memory operation of the wave).
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-// A level-h value other workgroups' top rescan reads: write-through.
-__device__ __forceinline__ void store_shared_level(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// R: updates per thread the launch holds (n <= 256 R).  The small form (R = 2, up to 512
-// updates: a DQN batch) takes 21 KB of LDS and few registers, so its workgroups fit beside
-// the next step's target forward (gemm_p3c12_kernel, 117 KB of LDS per CU), which the
-// early start runs at the same time on the side stream; at R = 16 (49 KB, 200 VGPRs) they
-// waited for its blocks to retire (24 us in the two-stream trace against 12 us alone,
-// profiles/r06/schedule/).
+// update_priorities in ONE launch: the body lives in prio_update.h (shared with the DQN step's
+// rider form); here its own kernel, a.groups update workgroups after the optional rescale
+// workgroup, its LDS one static array of the size of the arrays it replaces.
 template <int R>
 __global__ void __launch_bounds__(256) prio_update_fused_kernel(FusedUpdateArgs a) {
-  static_assert(R * 256 <= kFusedUpdateMax, "update capacity");
-  __shared__ int64_t s_slot[R * 256];
-  __shared__ int s_len, s_np, s_ovf, s_last;
-  __shared__ double s_ch[kUpdPairs][64];  // children of each prefetched node
-  __shared__ int64_t s_node[kUpdPairs];
-  __shared__ int s_lvl[kUpdPairs];
-  __shared__ int64_t s_nk[kUpdPairs];  // node << 3 | level: one LDS read per match test
-  __shared__ double s_val[kUpdPairs];
-  const int first = a.job.s ? 1 : 0;
-  auto stamp = [&](int ph) {
-    if (a.stamps && threadIdx.x == 0)
-      a.stamps[8 * (int64_t)blockIdx.x + ph] = __builtin_amdgcn_s_memrealtime();
-  };
-  stamp(0);
-  if (a.job.s && blockIdx.x == 0) {
-    rescale_block(a.job);
-    stamp(1);
-    return;
-  }
-  const bool verdict = a.job.s && a.job.rg.g && a.job.rg.mode == kRgStep;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-  const int G = kFusedUpdateBlocks, bid = (int)blockIdx.x - first;
-  const int h = a.nlevels >= 2 ? a.nlevels - 2 : 0;
-  bool skip = !verdict && gate_skip(a.gate);
-  if (tid == 0) s_len = 0;
-  __syncthreads();
-  // Round 1: every update's key and priority (all workgroups read all of them; L2-resident
-  // after the first), its slot and owner; this workgroup's updates join the list in atomic
-  // order, and the thread that read an update keeps it (key, priority, list entry) in
-  // registers.  Its stale-key check shares round 2 with the children rows, and its leaf
-  // p^alpha is computed while those loads are in flight (round 6: three dependent rounds of
-  // global loads became two, and the f64 power left the critical path).
-  uint64_t kv[R];
-  double pr[R];
-  int64_t sl[R];
-  int my_e[R];
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    my_e[i] = -1;
-    kv[i] = 0;
-    pr[i] = 0.0;
-    sl[i] = 0;
-  }
-  if (!skip) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;  // workgroup-uniform
-      const int j = tid + i * nt;
-      const int jc = j < a.n ? j : a.n - 1;
-      kv[i] = a.upd_keys[jc];
-      pr[i] = a.prios[jc];
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;
-      const int j = tid + i * nt;
-      const int64_t slot = (int64_t)(kv[i] % (uint64_t)a.capacity);
-      if (j < a.n && (int)((slot >> (6 * h)) % G) == bid) {
-        const int e = atomicAdd(&s_len, 1);
-        s_slot[e] = slot;
-        my_e[i] = e;
-        sl[i] = slot;
-      }
-    }
-  }
-  __syncthreads();
-  stamp(1);
-  const int len = s_len;
-  if (len > 0) {
-    // The distinct nodes of levels 1..h this workgroup recomputes: a thread per (level,
-    // update) keeps the node if no earlier update of the list has the same ancestor at that
-    // level (a serial scan by one thread took up to 7 us on the workgroup with the most
-    // updates, profiles/r05/update_stamps/).  The list's order is the threads' (atomic slot
-    // order); every use below matches nodes by (level, node), so the result does not depend
-    // on it.  A node whose updates all turn out stale is rescanned from unchanged children:
-    // the same value it holds.
-    if (tid == 0) {
-      s_np = 0;
-      s_ovf = 0;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < h * len; idx += nt) {
-      const int l = 1 + idx / len, e = idx - (l - 1) * len;
-      const int64_t node = s_slot[e] >> (6 * l);
-      bool first = true;
-      for (int f = 0; f < e && first; ++f) first = (s_slot[f] >> (6 * l)) != node;
-      if (!first) continue;
-      const int q = atomicAdd(&s_np, 1);
-      if (q < kUpdPairs) {
-        s_lvl[q] = l;
-        s_node[q] = node;
-        s_nk[q] = (node << 3) | l;
-      } else {
-        s_ovf = 1;
-      }
-    }
-    __syncthreads();
-    if (tid == 0 && s_np > kUpdPairs) s_np = kUpdPairs;  // (with s_ovf: the read-back path)
-    __syncthreads();
-    stamp(2);
-    const int np = s_np;
-    const bool pre = !s_ovf;
-    // Round 2, one batch of loads: the stored key of each of this thread's updates (the stale
-    // check) and each node's 64 children (a wave per node); the leaves computed meanwhile.
-    // (Loops over a thread's updates stop at the workgroup-uniform count, so nothing is
-    // evaluated for the unused register slots: the f64 power below for all 16 measured
-    // 17 us.)
-    uint64_t kt[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;
-      kt[i] = my_e[i] >= 0 ? a.keys[sl[i]] : 0;
-    }
-    if (pre) {
-      for (int q = wave; q < np; q += nw)
-        s_ch[q][lane] = a.level[s_lvl[q] - 1][s_node[q] * 64 + lane];
-    }
-    double leafv[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;
-      leafv[i] = 0.0;
-      if (my_e[i] >= 0) leafv[i] = det_pow_priority(pr[i], a.alpha);
-    }
-    // Each entry repacked in place as slot << 13 | valid << 12 | j (the node list is built,
-    // so s_slot's plain form is no longer read): the election below reads one word per entry.
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;
-      if (my_e[i] >= 0)  // valid: the key still lives in its slot (evicted since sampled: ignored)
-        s_slot[my_e[i]] = (sl[i] << 13) | ((kt[i] == kv[i] ? 1 : 0) << 12) | (tid + i * nt);
-    }
-    __syncthreads();
-    stamp(4);
-    // The verdict's first poll now (thread 0), landing while the LDS work below runs: the
-    // barriers below order LDS only, so they do not wait for it.
-    uint32_t vfirst = 0;
-    if (verdict && tid == 0)
-      vfirst = __hip_atomic_load(&a.job.rg.g->vseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // Everything but the stores before the verdict: the last valid update of each slot wins
-    // (substituted into its level-1 node's children) and, on the prefetched path, every
-    // node's new value rescanned level by level in LDS.
-    bool winv[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) winv[i] = false;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      if (i * nt >= a.n) break;
-      const int e = my_e[i];
-      bool win = e >= 0 && kt[i] == kv[i];
-      const int j = tid + i * nt;
-      const int64_t me = (sl[i] << 1) | 1;  // same slot, valid
-#pragma unroll 4
-      for (int f = 0; f < len; ++f) {
-        const int64_t x = s_slot[f];
-        if ((x >> 12) == me && (int)(x & 4095) > j) win = false;
-      }
-      winv[i] = win;
-    }
-    // (The children rows were filled by wave q % nw before the barrier above, so the
-    // substitutions below by any wave follow them: ADVICE r5's race.)
-    if (pre) {
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        if (i * nt >= a.n) break;
-        if (!winv[i]) continue;
-        const int64_t k1 = ((sl[i] >> 6) << 3) | 1;
-#pragma unroll 4
-        for (int q = 0; q < np; ++q)
-          if (s_nk[q] == k1) s_ch[q][sl[i] & 63] = leafv[i];
-      }
-    }
-    lds_barrier();
-    if (pre) {
-      for (int l = 1; l <= h; ++l) {
-        for (int q = wave; q < np; q += nw) {
-          if (s_lvl[q] != l) continue;
-          const double v = wave_total64(s_ch[q][lane]);
-          if (lane == 63) s_val[q] = v;
-        }
-        lds_barrier();
-        if (tid < np && s_lvl[tid] == l) {  // into the parent's children
-          const int64_t kp = ((s_node[tid] >> 6) << 3) | (l + 1);
-#pragma unroll 4
-          for (int q = 0; q < np; ++q)
-            if (s_nk[q] == kp) s_ch[q][s_node[tid] & 63] = s_val[tid];
-        }
-        lds_barrier();
-      }
-    }
-    // The step's verdict (published by workgroup 0's rescale while this workgroup resolved
-    // its keys, loaded and computed), before the first store.
-    stamp(7);
-    if (verdict) skip = wait_verdict_skip(a.job.rg.g, a.job.rg.seq, vfirst);
-    stamp(3);
-    if (!skip) {
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        if (i * nt >= a.n) break;
-        if (!winv[i]) continue;
-        a.raw_prio[sl[i]] = pr[i];
-        if (h == 0 && !a.top_computed) store_shared_level(a.level[0] + sl[i], leafv[i]);
-        else a.level[0][sl[i]] = leafv[i];
-      }
-      if (pre) {
-        for (int q = tid; q < np; q += nt) {
-          const int l = s_lvl[q];
-          if (l == h && !a.top_computed) store_shared_level(a.level[l] + s_node[q], s_val[q]);
-          else a.level[l][s_node[q]] = s_val[q];
-        }
-      } else {
-        __syncthreads();
-        for (int l = 1; l <= h; ++l) {  // read back what this workgroup stored (levels below are its own)
-          for (int e = wave; e < len; e += nw) {
-            const int64_t node = (s_slot[e] >> 13) >> (6 * l);
-            const double v = wave_total64(a.level[l - 1][node * 64 + lane]);
-            if (lane == 63) {
-              if (l == h && !a.top_computed) store_shared_level(a.level[l] + node, v);
-              else a.level[l][node] = v;
-            }
-          }
-          __syncthreads();
-        }
-      }
-      stamp(5);
-    }
-  }
-  stamp(6);
-  if (a.nlevels < 2 || a.top_computed) return;  // readers compute the top (TreeView)
-  // Count this workgroup finished once its level-h stores are released at agent scope (every
-  // thread's own release fence, then the workgroup barrier, then a release increment), and
-  // the last one acquires them (the increment's acquire side and an agent-scope acquire fence
-  // in every thread) before it rescans the top level (a waitcnt is no fence).
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (tid == 0)
-    s_last = __hip_atomic_fetch_add(a.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-             (uint32_t)(G - 1);
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  const int top = a.nlevels - 1;
-  for (int64_t node = wave; node < a.top_nodes; node += nw) {
-    const double c = __hip_atomic_load(a.level[top - 1] + node * 64 + lane, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-    const double v = wave_total64(c);
-    if (lane == 63) a.level[top][node] = v;
-  }
-  if (tid == 0) __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __shared__ __attribute__((aligned(16))) uint8_t s_mem[UpdLds<R>::kBytes];
+  prio_update_body<R>(a, s_mem, (int)blockIdx.x, a.groups);
 }
-
-
 
 __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1578,6 +1222,16 @@ int acme_replay_debug_leaves(const acme_replay* r, const double** leaf_values,
   if (leaf_values) *leaf_values = r->levels[0];
   if (raw_priorities) *raw_priorities = r->raw_prio;
   if (keys) *keys = r->keys;
+  return ACME_OK;
+}
+
+int acme_replay_debug_level(const acme_replay* r, int32_t level, const double** values,
+                            int64_t* count, int32_t* nlevels) {
+  ACME_CHECK_ARG(r, "null replay");
+  if (nlevels) *nlevels = r->nlevels;
+  ACME_CHECK_ARG(level >= 0 && level < r->nlevels, "level %d out of range", level);
+  if (values) *values = r->levels[level];
+  if (count) *count = r->level_size[level];
   return ACME_OK;
 }
 
@@ -2195,6 +1849,52 @@ int acme_replay_sample_gather_pipe(acme_replay* r, int32_t pipe, int64_t batch,
 
 }  // extern "C"
 
+namespace {
+// Scratch for resolved slots / validity (grown on demand; growth drains the device).  The
+// caller holds r->mu.
+int update_scratch(acme_replay* r, int64_t n) {
+  if (n > r->upd_cap) {
+    if (r->upd_slots) {
+      ACME_HIP_TRY(hipDeviceSynchronize());
+      (void)hipFree(r->upd_slots);
+      (void)hipFree(r->upd_valid);
+    }
+    r->upd_cap = std::max<int64_t>(n, 4096);
+    ACME_HIP_TRY(hipMalloc(&r->upd_slots, r->upd_cap * sizeof(int64_t)));
+    ACME_HIP_TRY(hipMalloc(&r->upd_valid, r->upd_cap * sizeof(int32_t)));
+  }
+  return ACME_OK;
+}
+}  // namespace
+
+int acme::replay_update_prepare(acme_replay* r, const uint64_t* keys, const double* prios,
+                                int64_t n, const Gate& gate, hipStream_t st,
+                                const RescaleJob* job, int groups, FusedUpdateArgs* out) {
+  ACME_CHECK_ARG(r && keys && prios && out, "null argument");
+  ACME_CHECK_ARG(n >= 1 && n <= kFusedUpdateMax && groups >= 1, "bad update or workgroup count");
+  std::unique_lock<std::mutex> lock(r->mu);
+  int rc = order_after_inserts(r, st);
+  if (rc != ACME_OK) return rc;
+  if ((rc = update_scratch(r, n)) != ACME_OK) return rc;
+  FusedUpdateArgs a;
+  a.upd_keys = keys; a.prios = prios; a.n = (int)n; a.capacity = r->cfg.capacity;
+  a.keys = r->keys; a.raw_prio = r->raw_prio; a.nlevels = r->nlevels;
+  a.alpha = r->cfg.sampler == ACME_SAMPLER_PRIORITIZED ? r->cfg.priority_exponent : 0.0;
+  a.gate = gate;
+  if (job) a.job = *job;
+  for (int l = 0; l < 8; ++l) a.level[l] = r->levels[l];
+  a.top_nodes = r->nlevels >= 2 ? r->level_size[r->nlevels - 2] / 64 : 0;
+  a.top_computed = computed_top_nodes(r) > 0 ? 1 : 0;
+  a.groups = groups;
+  a.done = r->upd_done;
+  a.stamps = g_update_stamps;
+  *out = a;
+  lock.release();  // held until replay_update_release
+  return ACME_OK;
+}
+
+void acme::replay_update_release(acme_replay* r) { r->mu.unlock(); }
+
 int acme::replay_update_priorities_gated(acme_replay* r, const uint64_t* keys,
                                          const double* prios, int64_t n, const Gate& gate,
                                          hipStream_t st, const RescaleJob* job) {
@@ -2213,43 +1913,32 @@ int acme::replay_update_priorities_gated(acme_replay* r, const uint64_t* keys,
     }
     if (n == 0) return ACME_OK;
   }
+  if (n <= kFusedUpdateMax) {
+    // ACME_V_UPD_GROUPS (tests): the update workgroups of this launch; the result does not
+    // depend on the count.
+    const int tg = tune_variant("UPD_GROUPS");
+    FusedUpdateArgs a;
+    const int rc = replay_update_prepare(r, keys, prios, n, gate, st, job,
+                                         tg >= 1 && tg <= 1024 ? tg : kFusedUpdateBlocks, &a);
+    if (rc != ACME_OK) return rc;
+    std::lock_guard<std::mutex> lock(r->mu, std::adopt_lock);
+    ACME_PROF("replay_update", st, 0.0, (double)n * (16.0 + 8.0 * 3 + 512.0 * (r->nlevels - 1)));
+    const unsigned blocks = a.groups + (a.job.s ? 1 : 0);
+    if (n <= 2 * 256) prio_update_fused_kernel<2><<<blocks, 256, 0, st>>>(a);
+    else prio_update_fused_kernel<kFusedUpdateMax / 256><<<blocks, 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+    return ACME_OK;
+  }
   std::lock_guard<std::mutex> lock(r->mu);
   int rc = order_after_inserts(r, st);
   if (rc != ACME_OK) return rc;
-  // Scratch for resolved slots / validity (grown on demand; growth drains the device).
-  if (n > r->upd_cap) {
-    if (r->upd_slots) {
-      ACME_HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(r->upd_slots);
-      (void)hipFree(r->upd_valid);
-    }
-    r->upd_cap = std::max<int64_t>(n, 4096);
-    ACME_HIP_TRY(hipMalloc(&r->upd_slots, r->upd_cap * sizeof(int64_t)));
-    ACME_HIP_TRY(hipMalloc(&r->upd_valid, r->upd_cap * sizeof(int32_t)));
-  }
+  if ((rc = update_scratch(r, n)) != ACME_OK) return rc;
   int64_t* t_slots = r->upd_slots;
   int32_t* t_valid = r->upd_valid;
   const unsigned g = (unsigned)ceil_div(n, 256);
   const double alpha =
       r->cfg.sampler == ACME_SAMPLER_PRIORITIZED ? r->cfg.priority_exponent : 0.0;
   ACME_PROF("replay_update", st, 0.0, (double)n * (16.0 + 8.0 * 3 + 512.0 * (r->nlevels - 1)));
-  if (n <= kFusedUpdateMax) {
-    FusedUpdateArgs a;
-    a.upd_keys = keys; a.prios = prios; a.n = (int)n; a.capacity = r->cfg.capacity;
-    a.keys = r->keys; a.alpha = alpha; a.raw_prio = r->raw_prio; a.nlevels = r->nlevels;
-    a.gate = gate;
-    if (job) a.job = *job;
-    for (int l = 0; l < 8; ++l) a.level[l] = r->levels[l];
-    a.top_nodes = r->nlevels >= 2 ? r->level_size[r->nlevels - 2] / 64 : 0;
-    a.top_computed = computed_top_nodes(r) > 0 ? 1 : 0;
-    a.done = r->upd_done;
-    a.stamps = g_update_stamps;
-    const unsigned blocks = kFusedUpdateBlocks + (a.job.s ? 1 : 0);
-    if (n <= 2 * 256) prio_update_fused_kernel<2><<<blocks, 256, 0, st>>>(a);
-    else prio_update_fused_kernel<kFusedUpdateMax / 256><<<blocks, 256, 0, st>>>(a);
-    ACME_LAUNCH_CHECK();
-    return ACME_OK;
-  }
   prio_resolve_kernel<<<g, 256, 0, st>>>(keys, n, r->keys, r->cfg.capacity, t_slots, t_valid,
                                          r->winner);
   ACME_LAUNCH_CHECK();

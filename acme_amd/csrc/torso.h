@@ -11,6 +11,7 @@
 #include "conv.h"
 
 namespace acme {
+struct FusedUpdateArgs;  // prio_update.h
 namespace gemm {
 struct PScale;  // gemm_p3.h
 }
@@ -115,6 +116,13 @@ struct Side {
   // step's priority write-back, which balances the two streams' backward).
   int (*tail)(void* ctx, hipStream_t st) = nullptr;
   void* tail_ctx = nullptr;
+  // Optional: the tail as a rider of conv1's weight-gradient launch (the replay table's
+  // priority update in that launch's leading workgroups, prio_update.h UpdateRider; needs
+  // conv1_single).  Called before the launch: it issues the tail's stream waits and, when it
+  // sets *armed, fills the rider's arguments; tail_rider_done is then called right after the
+  // launch and `tail` is not.  Not armed (a tail of another shape): `tail` runs as usual.
+  int (*tail_rider)(void* ctx, hipStream_t st, FusedUpdateArgs* out, bool* armed) = nullptr;
+  void (*tail_rider_done)(void* ctx) = nullptr;
   // conv1's weight gradient on the single-role kernel instead of the producer / consumer one
   // (the same bits; tests, ACME_V_WSN=1 at the learner's creation).
   bool single_role = false;

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "launch.h"
 #include "plane_guard.h"
+#include "prio_update.h"
 #include "profiler.h"
 
 namespace acme {
@@ -204,7 +205,8 @@ int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, c
 // conv1's weight + bias gradient (split-K slabs) from the frames of rows [0, rows).
 template <bool U8>
 int conv1_wgrad_p3(const Frames& frames, int rows, const Plane& dz1, float* slab, int splits,
-                   bool single_role, P3ConvWgrad<G1, 1, U8>& p, hipStream_t st) {
+                   bool single_role, P3ConvWgrad<G1, 1, U8>& p, hipStream_t st,
+                   const FusedUpdateArgs* rider = nullptr) {
   if (U8 && frames.split < rows)
     return (set_error("conv1's weight gradient reads its frames from one buffer"),
             ACME_ERR_INVALID);
@@ -214,7 +216,16 @@ int conv1_wgrad_p3(const Frames& frames, int rows, const Plane& dz1, float* slab
   q.a_src = frames_src(frames, rows); q.b_src = SRC(dz1, (int64_t)rows * kX1);
   q.slab = slab;
   // Producer / consumer waves (gemm_p3ws_kernel): 28.5 -> 25.0 us, the same bits.
-  if (single_role) ACME_P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
+  // With a rider (single-role only): the priority write-back in the launch's first
+  // workgroups, in the same 40 KB of LDS, so the launch still fits beside the side stream's
+  // fused target convolution (117 KB).
+  if (rider && !single_role)
+    return (set_error("the update rider needs conv1's single-role kernel"), ACME_ERR_INVALID);
+  if (rider)
+    ACME_LAUNCH_GEMM("conv1_wgrad", ACME_MNK_FLOPS(q), gemm::p3_peak_tflops<decltype(q)>(),
+                     (gemm::launch_gemm_p3_rider<256, 32, 4, 1, 32, UpdateRider>(q, splits, *rider,
+                                                                                 st)));
+  else if (single_role) ACME_P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
   else ACME_P3WS_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
   p = q;
   return ACME_OK;
@@ -353,21 +364,32 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
                            : gemm::launch_gemm_p3s<G2, 2, kBkConv2Dgrad>(p, rows, st);
     if (e != hipSuccess) return (set_error("gemm launch failed: %s", hipGetErrorString(e)), ACME_ERR_HIP);
   }
+  // The tail as conv1_wgrad's rider: everything it reads is written by now (the priorities
+  // by the loss launch, the last amax record by conv2's input gradient above), and the
+  // weight gradient writes only f32 slabs.
+  FusedUpdateArgs upd;
+  bool rider = false;
+  if (sd.tail && sd.tail_rider && sd.tail_rider_done && sd.conv1_single &&
+      (rc = sd.tail_rider(sd.tail_ctx, st_main, &upd, &rider)) != ACME_OK)
+    return rc;
+  const FusedUpdateArgs* ride = rider ? &upd : nullptr;
   {  // conv1 (no input gradient)
     const int splits = kP3Conv1WgradSplits;
     int64_t wcount;
     int M1, N1;
     if (frames.u8) {
       P3ConvWgrad<G1, 1, true> p;
-      if ((rc = conv1_wgrad_p3<true>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st)))
-        return rc;
+      rc = conv1_wgrad_p3<true>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st, ride);
+      if (rider) sd.tail_rider_done(sd.tail_ctx);
+      if (rc) return rc;
       M1 = p.M, N1 = p.N;
       if (!defer && (rc = p3_wgrad_reduce(p, splits, slab, g.w1, g.b1, "conv1_wgrad_reduce", st)))
         return rc;
     } else {
       P3ConvWgrad<G1, 1> p;
-      if ((rc = conv1_wgrad_p3<false>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st)))
-        return rc;
+      rc = conv1_wgrad_p3<false>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st, ride);
+      if (rider) sd.tail_rider_done(sd.tail_ctx);
+      if (rc) return rc;
       M1 = p.M, N1 = p.N;
       if (!defer && (rc = p3_wgrad_reduce(p, splits, slab, g.w1, g.b1, "conv1_wgrad_reduce", st)))
         return rc;
@@ -375,7 +397,7 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
     wcount = (int64_t)M1 * N1;
     if (defer) sd.defer[0] = WgradSlab{slab, splits, wcount, N1};
   }
-  if (sd.tail && (rc = sd.tail(sd.tail_ctx, st_main)) != ACME_OK) return rc;
+  if (sd.tail && !rider && (rc = sd.tail(sd.tail_ctx, st_main)) != ACME_OK) return rc;
   if (fork) ACME_HIP_TRY(hipStreamWaitEvent(st_main, sd.e[2], 0));  // join
   return ACME_OK;
 }

@@ -229,6 +229,22 @@ class NativeReplay:
             out[name] = _device_array(p.value, cnt, dt, self.device).cpu().numpy().view(dt).copy()
         return out
 
+    def debug_levels(self) -> list:
+        """Host copies of every stored sum-tree level, leaves first (tests)."""
+        n = ctypes.c_int32()
+        p, cnt = ctypes.c_void_p(), ctypes.c_int64()
+        check(lib().acme_replay_debug_level(self._h, 0, ctypes.byref(p), ctypes.byref(cnt),
+                                            ctypes.byref(n)))
+        torch.cuda.synchronize(self.device)
+        out = []
+        for l in range(n.value):
+            check(lib().acme_replay_debug_level(self._h, l, ctypes.byref(p), ctypes.byref(cnt),
+                                                None))
+            out.append(_device_array(p.value, cnt.value, np.float64, self.device)
+                       .cpu().numpy().view(np.float64).copy())
+        return out
+
+
 
 class NativeNStepWriter:
     """acme_nstep_writer: the native side of NStepTransitionAdder (rows formed and packed in
@@ -563,6 +579,10 @@ class NativeDQN(_PlaneState, _NativeLearner):
         check(lib().acme_dqn_verdict_timeouts(self._h, ctypes.byref(t)), "dqn verdict_timeouts")
         return dict(applied=int(a[0]), skipped=int(a[1]), last_skipped=int(a[2]),
                     q_values_overflowed=int(a[3]), verdict_timeouts=int(t.value))
+
+    def update_rider_launches(self) -> int:
+        """Steps whose priority write-back rode conv1's weight-gradient launch."""
+        return int(lib().acme_dqn_update_rider_launches(self._h))
 
     @property
     def applied_steps(self) -> int:

@@ -285,6 +285,10 @@ int64_t acme_replay_capacity(const acme_replay* r);
 /* Device pointer to the sum-tree total (f64) — test/diagnostic use. */
 int acme_replay_debug_leaves(const acme_replay* r, const double** leaf_values,
                              const double** raw_priorities, const uint64_t** keys);
+/* Device pointer and entry count of sum-tree level `level` (0: the leaves); *nlevels (optional)
+ * the number of levels.  Tests: the stored tree after priority updates. */
+int acme_replay_debug_level(const acme_replay* r, int32_t level, const double** values,
+                            int64_t* count, int32_t* nlevels);
 
 /* Table state for checkpoints (optional replay state of acme/tf/savers.py's Checkpointer,
  * SURVEY §8(f) row 2).  acme_replay_storage: device pointer of field f's [capacity, bytes]
@@ -396,6 +400,10 @@ int acme_dqn_set_reissue(acme_dqn* l, int32_t enable);
  * applied; synchronises.  Never expected; DQNLearner raises RuntimeError when it is non-zero. */
 int acme_dqn_verdict_timeouts(acme_dqn* l, int64_t* out);
 int64_t acme_dqn_verdicts_issued(const acme_dqn* l);
+/* Steps whose priority write-back (acme_dqn_step_update) ran as the leading workgroups of
+ * conv1's weight-gradient launch instead of a launch of its own (the fused plane step with
+ * at most 512 updates, unless the learner was created with ACME_V_UPDATE_RIDER=0). */
+int64_t acme_dqn_update_rider_launches(const acme_dqn* l);
 int acme_dqn_step_verdict(const acme_dqn* l, int64_t seq, int32_t* state);
 /* The plane scales (powers of two) as learner state for checkpoints: acme_dqn_scale_state
  * writes *count floats to out (when out is non-NULL and capacity suffices);

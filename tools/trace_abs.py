@@ -5,8 +5,13 @@ Usage: tools/trace_abs.py <kernel_trace.csv> [steps] [marker]"""
 import csv, re, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-mark = sys.argv[3] if len(sys.argv) > 3 else "prio_update_fused"
-idx = [i for i, r in enumerate(rows) if mark in r["Kernel_Name"]]
+# The step's last main-stream kernel: the priority write-back, or conv1's weight gradient that
+# carries it as a rider (gemm_p3r_kernel) when there is no separate launch.
+marks = [sys.argv[3]] if len(sys.argv) > 3 else ["prio_update_fused", "gemm_p3r_kernel"]
+for mark in marks:
+    idx = [i for i, r in enumerate(rows) if mark in r["Kernel_Name"]]
+    if idx:
+        break
 acc = collections.OrderedDict()
 for s in range(steps):
     a, b = idx[-steps - 1 + s], idx[-steps + s]

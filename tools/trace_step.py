@@ -8,8 +8,12 @@ import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-mark = sys.argv[3] if len(sys.argv) > 3 else "prio_update_fused"
-adam = [i for i, r in enumerate(rows) if mark in r["Kernel_Name"]]
+# Default marker: the priority update, or conv1's weight gradient carrying it as a rider.
+marks = [sys.argv[3]] if len(sys.argv) > 3 else ["prio_update_fused", "gemm_p3r_kernel"]
+for mark in marks:
+    adam = [i for i, r in enumerate(rows) if mark in r["Kernel_Name"]]
+    if adam:
+        break
 a, b = adam[-steps - 1], adam[-1]
 iv = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows[a + 1:b + 1])
 union, gaps, (cs, ce) = 0, 0, iv[0]
