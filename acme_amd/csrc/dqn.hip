@@ -56,6 +56,59 @@ struct Layer {  // dense layer of the MLP network
   bool relu = true;
 };
 
+// What kind of step a call issues.  The entry point decides it once and passes it down the
+// stage functions; nothing on the learner says which step is in flight.
+struct StepPlan {
+  // A calibration pass (calibrate_scales): outputs to scratch, no write-back, no gate word.
+  bool calibrating = false;
+  // acme_dqn_step / acme_dqn_step_update: stage 1 leaves the conv weight gradients as
+  // split-K slabs for Adam (launch_adam_slabs: three reduction launches fewer).
+  bool fused = false;
+  // The caller's stream waits for the side stream's dense weight gradients before stage 0 / 3
+  // returns (a staged caller all-reduces them next); otherwise the torso backward's final
+  // join covers them.
+  bool join_dense = false;
+  // acme_dqn_step_update: the replay's priority write-back issued inside the step (keys of
+  // the step's batch; `after`: the table's last device read, which the update waits for).
+  // replay == nullptr: none.
+  acme_replay* replay = nullptr;
+  const uint64_t* keys = nullptr;
+  hipEvent_t after = nullptr;
+};
+
+// What one step leaves for its later stages (stage 2 -> 3 / 4 -> 1 -> apply may be separate
+// C-ABI calls).  Value-initialised where a step's forwards begin (forward_backward_stage)
+// and nowhere else, so no call can read what an earlier, abandoned or failed step left.
+struct StepState {
+  int64_t fwd_batch = 0;  // rows of the stage-2 forward awaiting its stage 3 / 4
+  bool last_p3 = false;   // the forward ran the plane path
+  torso::Frames cur_frames{nullptr};  // conv1's input (the batch's uint8 frames or an f16 copy)
+  // Plane path: the loss is launched together with the head dZ (launch_dqn_loss_head_dz)
+  // by the backward; loss_and_dense_backward leaves its arguments here.
+  LossArgs pending_la{};
+  bool loss_pending = false;
+  // The online forward left its duelling head (the fc split-K slab's reduction, hid, q_on) to
+  // the loss launch (launch_dqn_head_loss_dz, head_splits splits); loss_nparts: the loss
+  // partials the launch writes.
+  bool head_deferred = false;
+  int head_splits = 0;
+  int64_t loss_nparts = 0;
+  // The dense layers' gradients (grads[grad_split:]) of stage 3 / 4 are complete at
+  // dense_ev: the side stream's event when their launches ran there, else ev_dense,
+  // recorded on the caller's stream.
+  hipEvent_t dense_ev = nullptr;
+  // Stage 1 of a fused step left the conv weight gradients as these slabs.
+  bool slabs_pending = false;
+  torso::WgradSlab wslabs[3];
+  // The step's transient rescale is launched (take_step_rescale): with the priority
+  // write-back's launch it has deferred read scales, committed by Adam.
+  bool rescaled = false;
+  // The write-back of StepPlan::replay: the loss's priorities, and whether it was issued.
+  const double* upd_prio = nullptr;
+  int upd_n = 0;
+  bool update_issued = false;
+};
+
 }  // namespace
 
 struct acme_dqn : PlaneGuard {
@@ -88,14 +141,10 @@ struct acme_dqn : PlaneGuard {
   // the parameters / target parameters ([2][flat]) and of every GEMM operand.
   bool p3_capable = false;
   bool planes_stale = true;  // parameter planes need a refresh from the f32 buffers
-  bool last_p3 = false;      // the last forward/backward ran the plane path
   uint16_t *wpl = nullptr, *tpl = nullptr;
   // (PlaneGuard: the scale records of the plane tensors, kSc* below.)
-  bool calibrating = false;
-  int64_t fwd_batch = 0;  // rows of the last stage-2 forward awaiting its stage 3
   uint16_t* frames = nullptr;  // f16 copies of [o_tm1; o_t] (2B frames)
-  // conv1's input of the current step (l->frames, the f16 copy).
-  torso::Frames cur_frames{nullptr};
+  StepState step;              // the step in flight
   // Second stream of the plane path: the target forward runs beside the online forward,
   // and weight gradients beside input gradients (fork / join by events on the caller's
   // stream; side_slab is its split-K scratch).
@@ -104,16 +153,6 @@ struct acme_dqn : PlaneGuard {
   // Fused step (acme_dqn_step): the conv weight gradients stay split-K slabs and Adam
   // reduces them on its read (launch_adam_slabs): three reduction launches fewer.
   float* slab2 = nullptr;    // conv2's slab (conv3's is side_slab, conv1's slab)
-  bool fused_step = false;   // set by step_impl
-  // acme_dqn_step_update: the replay's priority write-back issued inside the step (on the
-  // second stream right after the loss), keys of the step's batch.
-  acme_replay* upd_replay = nullptr;
-  const uint64_t* upd_keys = nullptr;
-  hipEvent_t upd_after = nullptr;  // the table's last device read (the update waits for it)
-  const double* upd_prio = nullptr;
-  int upd_n = 0;
-  bool slabs_pending = false;
-  torso::WgradSlab wslabs[3];
   float* side_slab = nullptr;
   // The target forward's split-K slab (its own: the fused step's Adam reads side_slab while
   // the side stream may already run the next step's target forward).
@@ -124,22 +163,7 @@ struct acme_dqn : PlaneGuard {
   // activation scale records (kScT1..kScT3) are rescaled on the side stream after it.
   bool target_dirty = true;
   torso::Plane x1p{}, x2p{}, x3p{}, t1p{}, t2p{}, t3p{}, dzhp{}, dz3p{}, dz2p{}, dz1p{};
-  // Plane path: the loss is launched together with the head dZ (launch_dqn_loss_head_dz)
-  // by the backward; forward_backward_stage leaves its arguments here.
-  LossArgs pending_la{};
-  bool loss_pending = false;
-  // The online forward left its duelling head (the fc split-K slab's reduction, hid, q_on) to
-  // the loss launch (launch_dqn_head_loss_dz, head_splits splits); loss_nparts: the loss
-  // partials the launch writes.
-  bool head_deferred = false;
-  int head_splits = 0;
-  int64_t loss_nparts = 0;
-  // The dense layers' gradients (grads[grad_split:]) of the last stage 3 / 4 are complete
-  // at dense_ev: the side stream's event when their launches ran there, else ev_dense,
-  // recorded on the caller's stream.
-  hipEvent_t ev_dense = nullptr;
-  hipEvent_t dense_ev = nullptr;
-  bool dense_on_side = false;
+  hipEvent_t ev_dense = nullptr;  // StepState::dense_ev without the side stream
   // Data parallelism over a caller-owned RCCL communicator (acme_dqn_dp_*): the collective
   // stream, its events, the global IS normaliser's minimum probability.
   void* dp_comm = nullptr;
@@ -159,8 +183,6 @@ struct acme_dqn : PlaneGuard {
   // launch (prio_update.h UpdateRider) instead of a launch of its own after it
   // (ACME_V_UPDATE_RIDER=0 at creation: the separate launch; the same bits).
   bool update_rider = true;
-  int rider_groups = kUpdateRiderBlocks;  // its update workgroups (ACME_V_RIDER_GROUPS: A/B runs)
-  acme_replay* rider_replay = nullptr;  // locked between the rider's prepare and its launch
   int64_t rider_launches = 0;
   // conv1 reads the batch's uint8 frames (unless the batch carries the f16 copy, obs_f16, or
   // the frames are not 16-byte aligned: then the step makes the f16 copy, the round-4 path)
@@ -182,9 +204,6 @@ struct acme_dqn : PlaneGuard {
   // torso gradient bucket (stage 1 publishes the local one; the all-reduce combines them).
   bool dp_gate = false;
   int64_t dp_gate_index = -1;
-  // The step's transient rescale ran inside the priority write-back's launch (deferred read
-  // scales, committed by Adam): apply_impl launches none of its own.
-  bool step_rescaled = false;
 };
 
 namespace {
@@ -271,6 +290,16 @@ torso::Weights torso_weights(const acme_dqn* l, const float* prm) {
   return torso::Weights{P(l, prm, l->t_c1w), P(l, prm, l->t_c1b), P(l, prm, l->t_c2w),
                         P(l, prm, l->t_c2b), P(l, prm, l->t_c3w), P(l, prm, l->t_c3b)};
 }
+torso::Grads torso_grads(const acme_dqn* l) {
+  float* gr = l->grads;
+  return torso::Grads{Pm(l, gr, l->t_c1w), Pm(l, gr, l->t_c1b), Pm(l, gr, l->t_c2w),
+                      Pm(l, gr, l->t_c2b), Pm(l, gr, l->t_c3w), Pm(l, gr, l->t_c3b)};
+}
+// The plane path's: `wpl` are the planes of `prm` (the biases stay f32).
+torso::PWeights torso_pweights(const acme_dqn* l, const float* prm, uint16_t* wpl) {
+  return torso::PWeights{WP(l, wpl, l->t_c1w), WP(l, wpl, l->t_c2w), WP(l, wpl, l->t_c3w),
+                         P(l, prm, l->t_c1b), P(l, prm, l->t_c2b), P(l, prm, l->t_c3b)};
+}
 
 // Duelling value/advantage outputs as one skinny split-K GEMM + epilogue kernel.
 int head_forward(acme_dqn* l, const float* prm, int rows, const float* hid, float* q,
@@ -311,6 +340,19 @@ int nature_forward(acme_dqn* l, const float* prm, const void* obs_a, const void*
   return head_forward(l, prm, rows, hid, q, st);
 }
 
+// The fused hidden layer's GEMM on BM x 128 tiles: producer / consumer waves with fragment
+// reads one k16 step ahead (gemm_p3ws_kernel): 65.2 -> 60.5 us against the single-role
+// kernel, the same bits.
+// (Two f16 planes, measured on the step: 256x128 / 128x256 WS tiles, 256x128 single-role
+// tiles with split-K 8, and the LDS-DMA ring (3 or 4 stages) all slower or equal.)
+template <int BM>
+int fc_fwd_gemm(const acme_dqn* l, const char* name, P3DenseFwd p, int splits,
+                hipStream_t st) {
+  if (l->single_role) ACME_P3_GEMM(name, BM, 128, 2, 2, 32, p, splits);  // tests
+  else ACME_P3WS_GEMM(name, BM, 128, 2, 2, 32, p, splits);
+  return ACME_OK;
+}
+
 // Nature forward on the plane path: torso and the fused hidden layer read f16 planes
 // (gemm_p3.h); `wpl` are the planes of `prm`.
 int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso::Frames& frames,
@@ -318,9 +360,7 @@ int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso:
                       const torso::Plane& x3, float* hid, float* q, hipStream_t st,
                       float* slab = nullptr, int keep_x1 = -1, bool defer_head = false) {
   if (!slab) slab = l->slab;
-  torso::PWeights w{WP(l, wpl, l->t_c1w), WP(l, wpl, l->t_c2w), WP(l, wpl, l->t_c3w),
-                    P(l, prm, l->t_c1b), P(l, prm, l->t_c2b), P(l, prm, l->t_c3b)};
-  int rc = torso::forward_p3(w, frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1, l->bk32);
+  int rc = torso::forward_p3(torso_pweights(l, prm, wpl), frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1, l->bk32);
   if (rc != ACME_OK) return rc;
   {
     P3DenseFwd p;
@@ -344,24 +384,17 @@ int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso:
     p.a_src = SRC(x3, (int64_t)rows * kFlat); p.ldx = kFlat;
     p.b_src = SRC(WP(l, wpl, l->t_fcw), (int64_t)kFlat * 2 * kHidden); p.slab = slab;
     if (tall) p.stamps = l->stamps;
-    // Producer / consumer waves with fragment reads one k16 step ahead (gemm_p3ws_kernel):
-    // 65.2 -> 60.5 us against the single-role kernel, the same bits.
-    // (Two f16 planes, measured on the step: 256x128 / 128x256 WS tiles, 256x128 single-role
-    // tiles with split-K 8, and the LDS-DMA ring (3 or 4 stages) all slower or equal.)
     // (The target launch is its own profiler section: bench.py reports both launches as
     // fc_fwd and each one apart.)
-    if (ttall && l->single_role) ACME_P3_GEMM("fc_fwd_target", 256, 128, 2, 2, 32, p, splits);  // tests
-    else if (ttall) ACME_P3WS_GEMM("fc_fwd_target", 256, 128, 2, 2, 32, p, splits);
-    else if (tall && l->single_role) ACME_P3_GEMM("fc_fwd", 256, 128, 2, 2, 32, p, splits);  // tests
-    else if (tall) ACME_P3WS_GEMM("fc_fwd", 256, 128, 2, 2, 32, p, splits);
-    else if (l->single_role) ACME_P3_GEMM("fc_fwd", 128, 128, 2, 2, 32, p, splits);  // tests
-    else ACME_P3WS_GEMM("fc_fwd", 128, 128, 2, 2, 32, p, splits);
+    rc = tall || ttall ? fc_fwd_gemm<256>(l, ttall ? "fc_fwd_target" : "fc_fwd", p, splits, st)
+                       : fc_fwd_gemm<128>(l, "fc_fwd", p, splits, st);
+    if (rc != ACME_OK) return rc;
     // The online forward of a step: the head runs inside the loss launch (nature_backward).
     if (defer_head &&
         dqn_head_loss_dz_fusable(kHidden, l->cfg.num_actions, splits, P(l, prm, l->t_vw),
                                  P(l, prm, l->t_aw), P(l, prm, l->t_fcb))) {
-      l->head_deferred = true;
-      l->head_splits = splits;
+      l->step.head_deferred = true;
+      l->step.head_splits = splits;
       return ACME_OK;
     }
     ACME_PROF("fc_head_fwd", st, 0.0, 4.0 * (double)rows * 2 * kHidden * (splits + 1));
@@ -413,10 +446,12 @@ int mlp_forward(acme_dqn* l, const float* prm, const void* obs_a, const void* ob
   return ACME_OK;
 }
 
-// The step's transient rescale and skip decision (the guard's kRgStep): every plane of the
-// online forward and the backward is written by now; the target forward's records have their
-// own rescale.  defer_r: consumers may still read the planes on the second stream.
-RescaleJob step_rescale_job(acme_dqn* l, bool defer_r) {
+// The step's transient rescale and skip decision (the guard's kRgStep), taken exactly once per
+// step: by the priority write-back's launch (defer_r: consumers may still read the planes on
+// the second stream, so Adam commits the read scales), else by apply_impl.  Every plane of
+// the online forward and the backward is written by then; the target forward's records have
+// their own rescale.  Taking it issues the step's verdict number.
+RescaleJob take_step_rescale(acme_dqn* l, bool defer_r) {
   RescaleJob j;
   j.s = l->scales;
   j.nt = j.n = kScTransient;
@@ -431,60 +466,78 @@ RescaleJob step_rescale_job(acme_dqn* l, bool defer_r) {
   j.rg.host_verdicts = l->host_verdicts;
   j.rg.seq = l->verdict_seq++;
   j.rg.sticky = l->sticky ? 1 : 0;
+  l->step.rescaled = true;
   return j;
 }
 
-// The step's priority write-back (acme_dqn_step_update), once, on `st`, with the step's
-// rescale in an extra workgroup of its launch (one kernel boundary fewer on the step's
-// critical path; the read scales are committed by Adam, after the second stream's weight
-// gradients that still read the planes).
-int priority_update_tail(void* ctx, hipStream_t st) {
-  acme_dqn* l = static_cast<acme_dqn*>(ctx);
-  acme_replay* r = l->upd_replay;
-  if (!r || !l->upd_prio) return ACME_OK;
-  l->upd_replay = nullptr;
-  if (l->upd_after) ACME_HIP_TRY(hipStreamWaitEvent(st, l->upd_after, 0));
-  // Gated: a step that overflowed writes no priority.
-  const RescaleJob job = step_rescale_job(l, true);
-  const int rc =
-      replay_update_priorities_gated(r, l->upd_keys, l->upd_prio, l->upd_n, step_gate(l), st, &job);
-  if (rc == ACME_OK) l->step_rescaled = true;
-  return rc;
-}
-
-// The same write-back as a rider of conv1's weight-gradient launch (torso::Side::tail_rider):
-// the waits and the arguments now, before that launch; the update's workgroups then lead its
-// grid.  Armed for the fused step's batches of at most kUpdateRiderMax updates; otherwise
-// nothing is consumed and priority_update_tail runs after the launch as before.
-int priority_update_rider(void* ctx, hipStream_t st, FusedUpdateArgs* out, bool* armed) {
-  acme_dqn* l = static_cast<acme_dqn*>(ctx);
-  acme_replay* r = l->upd_replay;
-  *armed = false;
-  if (!r || !l->upd_prio || l->upd_n < 1 || l->upd_n > kUpdateRiderMax) return ACME_OK;
-  if (l->upd_after) ACME_HIP_TRY(hipStreamWaitEvent(st, l->upd_after, 0));
-  const RescaleJob job = step_rescale_job(l, true);
-  const int rc = replay_update_prepare(r, l->upd_keys, l->upd_prio, l->upd_n, step_gate(l), st,
-                                       &job, l->rider_groups, out);
+// The torso backward of the plane path (stage 1), with the step's priority write-back
+// (plan.replay) on the main stream around conv1's weight gradient: issued there, before the
+// join, it balances the two streams' backward (on the second stream right after the loss its
+// backward ended ~20 us after the main stream's).  The write-back's launch carries the step's
+// rescale in an extra workgroup (one kernel boundary fewer on the step's critical path) and
+// is gated: a step that overflowed writes no priority.
+int torso_backward_p3(acme_dqn* l, const StepPlan& plan, int B, hipStream_t st) {
+  const torso::Grads g = torso_grads(l);
+  StepState& s = l->step;
+  torso::Side sd;
+  sd.bk32 = l->bk32;
+  // conv1's weight gradient on the single-role kernel: its two 20-KB stages (40 KB of
+  // LDS) fit beside the next step's fused target convolution (117 KB) that runs on the
+  // side stream at the same time; the producer / consumer kernel's three stages (60 KB)
+  // do not.  Step 0.4957 -> 0.4920 ms (three alternating 300-step pairs, round 6,
+  // profiles/r06/schedule/ab_conv1_wgrad_single_role.log).
+  sd.conv1_single = true;
+  if (side_stream(l)) {
+    sd.side = l->side;
+    sd.slab = l->side_slab;
+    for (int i = 0; i < 3; ++i) sd.e[i] = l->ev[i];
+  }
+  if (plan.fused && !plan.calibrating && l->slab2) {
+    sd.slab = l->side_slab;
+    sd.slab2 = l->slab2;
+    sd.defer = s.wslabs;
+    s.slabs_pending = true;
+  }
+  int rc = torso::backward_p3_convs(torso_pweights(l, l->params, l->wpl), g, B,
+                                    torso::PActs{l->x1p, l->x2p, l->x3p}, l->dz3p, l->dz2p,
+                                    l->dz1p, l->slab, st, sd);
   if (rc != ACME_OK) return rc;
-  l->upd_replay = nullptr;
-  l->rider_replay = r;
-  l->rider_launches += 1;
-  l->step_rescaled = true;
-  *armed = true;
-  return ACME_OK;
+  const bool write_back = plan.replay && s.upd_prio;
+  // The write-back as a rider of conv1's weight-gradient launch (its workgroups lead that
+  // grid): the fused step's batches of at most kUpdateRiderMax updates.  Everything it reads
+  // is written by now (the priorities by the loss launch, the last amax record by conv2's
+  // input gradient), and the weight gradient writes only f32 slabs.  The table stays locked
+  // from the prepare to the launch.
+  FusedUpdateArgs upd;
+  const bool rider = write_back && l->update_rider && plan.fused && !l->dp_gate &&
+                     s.upd_n >= 1 && s.upd_n <= kUpdateRiderMax;
+  if (rider) {
+    if (plan.after) ACME_HIP_TRY(hipStreamWaitEvent(st, plan.after, 0));
+    const RescaleJob job = take_step_rescale(l, true);
+    if ((rc = replay_update_prepare(plan.replay, plan.keys, s.upd_prio, s.upd_n, step_gate(l), st,
+                                    &job, kUpdateRiderBlocks, &upd)) != ACME_OK)
+      return rc;
+    l->rider_launches += 1;
+    s.update_issued = true;
+  }
+  rc = torso::backward_p3_conv1(g, s.cur_frames, B, l->dz1p, l->slab, st, sd,
+                                rider ? &upd : nullptr);
+  if (rider) replay_update_release(plan.replay);
+  if (rc != ACME_OK) return rc;
+  if (write_back && !rider) {  // a launch of its own after conv1's weight gradient
+    s.update_issued = true;
+    if (plan.after) ACME_HIP_TRY(hipStreamWaitEvent(st, plan.after, 0));
+    const RescaleJob job = take_step_rescale(l, true);
+    if ((rc = replay_update_priorities_gated(plan.replay, plan.keys, s.upd_prio, s.upd_n,
+                                             step_gate(l), st, &job)) != ACME_OK)
+      return rc;
+  }
+  return torso::backward_p3_join(st, sd);
 }
 
-void priority_update_rider_done(void* ctx) {
-  acme_dqn* l = static_cast<acme_dqn*>(ctx);
-  if (l->rider_replay) replay_update_release(l->rider_replay);
-  l->rider_replay = nullptr;
-}
-
-// join_dense: the caller's stream waits for the side stream's dense weight gradients
-// before returning (stage 0 of a data-parallel step all-reduces them next); otherwise the
-// torso backward's final join covers them.
-int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
-                    bool join_dense) {
+int nature_backward(acme_dqn* l, const StepPlan& plan, const void* o_tm1, int B,
+                    hipStream_t st_main, bool join_dense) {
+  StepState& s = l->step;
   hipStream_t st = st_main;
   const float* prm = l->params;
   float* gr = l->grads;
@@ -495,21 +548,21 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
   // stream's first launch (off the critical path: folding it into the fused kernel's last
   // block to finish measured 14.6 -> 20.5 us on the critical path).
   bool loss_sum = false;
-  const LossArgs la = l->pending_la;
-  if (p3 && l->loss_pending && l->head_deferred) {  // online head + loss + head dZ, one launch
-    l->loss_pending = l->head_deferred = false;
+  const LossArgs la = s.pending_la;
+  if (p3 && s.loss_pending && s.head_deferred) {  // online head + loss + head dZ, one launch
+    s.loss_pending = s.head_deferred = false;
     loss_sum = true;
-    l->loss_nparts = B;
-    ACME_PROF("head_loss_dz", st, 0.0, 4.0 * (double)2 * B * 2 * kHidden * (l->head_splits + 1));
-    rc = launch_dqn_head_loss_dz(la, l->slab, l->head_splits, kHidden, P(l, prm, l->t_fcb),
+    s.loss_nparts = B;
+    ACME_PROF("head_loss_dz", st, 0.0, 4.0 * (double)2 * B * 2 * kHidden * (s.head_splits + 1));
+    rc = launch_dqn_head_loss_dz(la, l->slab, s.head_splits, kHidden, P(l, prm, l->t_fcb),
                                  P(l, prm, l->t_vw), P(l, prm, l->t_vb), P(l, prm, l->t_aw),
                                  P(l, prm, l->t_ab), l->hid, l->dzhp.p, l->dzhp.stride,
                                  l->dzhp.sc, st);
     if (rc != ACME_OK) return rc;
-  } else if (p3 && l->loss_pending) {  // the loss and the head dZ planes, one launch
-    l->loss_pending = false;
+  } else if (p3 && s.loss_pending) {  // the loss and the head dZ planes, one launch
+    s.loss_pending = false;
     loss_sum = la.loss_part != nullptr;
-    l->loss_nparts = dqn_loss_head_dz_blocks(B, kHidden);
+    s.loss_nparts = dqn_loss_head_dz_blocks(B, kHidden);
     ACME_PROF("loss_head_dz", st, 0.0, 0.0);
     rc = launch_dqn_loss_head_dz(la, l->hid, kHidden, P(l, prm, l->t_vw),
                                  P(l, prm, l->t_aw), l->dzhp.p, l->dzhp.stride, l->dzhp.sc, st);
@@ -530,12 +583,9 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
     ACME_HIP_TRY(hipStreamWaitEvent(l->side, l->ev[2], 0));
     st = l->side;
   }
-  if (p3 && l->upd_replay && !l->calibrating) {
-    l->upd_prio = la.prio;
-    l->upd_n = B;
-    // Issued at the end of the main stream's torso backward, before the join
-    // (priority_update_tail); on the second stream right after the loss its backward ended
-    // ~20 us after the main stream's.
+  if (p3 && plan.replay) {  // the write-back: issued by the torso backward (torso_backward_p3)
+    s.upd_prio = la.prio;
+    s.upd_n = B;
   }
   // The batch loss is summed by the head-gradient scatter's extra block (below): a launch of
   // its own on the second stream measured 0.5107 -> 0.5235 ms per step.
@@ -551,7 +601,7 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
     rc = launch_duel_head_grad_scatter(
         hslab, kHeadBwdSplits, kHidden, A, Pm(l, gr, l->t_vw), Pm(l, gr, l->t_vb),
         Pm(l, gr, l->t_aw), Pm(l, gr, l->t_ab), st, sum_in_scatter ? la.loss_part : nullptr,
-        l->loss_nparts, la.mean_over, la.loss);
+        s.loss_nparts, la.mean_over, la.loss);
     if (rc != ACME_OK) return rc;
   }
   if (p3) {
@@ -582,7 +632,7 @@ int nature_backward(acme_dqn* l, const void* o_tm1, int B, hipStream_t st_main,
       else ACME_P3WS_GEMM("fc_dgrad", 128, 128, 2, 2, 32, p, 1);
     }
     if (fork && join_dense) ACME_HIP_TRY(hipStreamWaitEvent(st_main, l->ev[3], 0));
-    l->dense_on_side = fork;
+    if (fork) s.dense_ev = l->ev[3];
     return ACME_OK;
   }
   {  // FC weight + bias grad: [7744, 1024] = x3^T dZh (reduction over the batch).
@@ -703,7 +753,6 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
   l->single_role = tune_variant("WSN") == 1;
   l->bk32 = tune_variant("BK32") == 1;
   l->update_rider = tune_variant("UPDATE_RIDER", kUpdateRiderDefault) != 0;
-  l->rider_groups = std::clamp(tune_variant("RIDER_GROUPS", kUpdateRiderBlocks), 1, 1024);
   l->stamps_on = tune_variant("STAMPS") == 1;
   const int A = cfg->num_actions;
   const int B = cfg->max_batch;
@@ -1006,7 +1055,7 @@ int acme_dqn_debug_buffer(const acme_dqn* l, const char* name, const float** out
              {"q_tg", l->q_tg, B * l->cfg.num_actions}, {"g", l->g, B}};
   for (auto& e : tab)
     if (e.p && std::strcmp(e.n, name) == 0) {
-      if (l->last_p3) {  // the plane path keeps these tensors as planes: join into f32
+      if (l->step.last_p3) {  // the plane path keeps these tensors as planes: join into f32
         struct {
           const char* n;
           torso::Plane pl;
@@ -1067,17 +1116,70 @@ int acme_dqn_q_values(acme_dqn* l, const void* obs, int64_t batch, int32_t use_t
   return mlp_forward(l, prm, obs, obs, B, B, l->mlp_tact, q_out, st);
 }
 
-static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batch,
-                                  const acme_dqn_outputs* out, int32_t stage, void* stream,
-                                  bool join_dense);
+static int forward_backward_stage(acme_dqn* l, const StepPlan& plan,
+                                  const acme_transition_batch* batch,
+                                  const acme_dqn_outputs* out, int32_t stage, void* stream);
 
 int acme_dqn_forward_backward_stage(acme_dqn* l, const acme_transition_batch* batch,
                                     const acme_dqn_outputs* out, int32_t stage, void* stream) {
-  return forward_backward_stage(l, batch, out, stage, stream, true);
+  StepPlan plan;
+  plan.join_dense = true;
+  return forward_backward_stage(l, plan, batch, out, stage, stream);
 }
 
-static int loss_and_dense_backward(acme_dqn* l, const acme_transition_batch* batch,
-                                   const acme_dqn_outputs* out, hipStream_t st, bool join_dense);
+// Loss (fused into the head dZ on the plane path) and the dense layers' backward, after
+// the forwards of the same batch.
+static int loss_and_dense_backward(acme_dqn* l, const StepPlan& plan,
+                                   const acme_transition_batch* batch,
+                                   const acme_dqn_outputs* out, hipStream_t st, bool join_dense) {
+  const int B = (int)batch->batch, A = l->cfg.num_actions;
+  const bool nature = l->cfg.network == ACME_NET_NATURE_DQN;
+  int rc;
+  float* loss = out && out->loss ? out->loss : l->loss_tmp;
+  float* td = out && out->td_error ? out->td_error : l->td_tmp;
+  double* prio = out && out->priorities ? out->priorities : l->prio_tmp;
+  LossArgs la;
+  la.q_on = l->q_on;
+  la.q_tg = l->q_tg;
+  la.a = batch->a_tm1;
+  la.r = batch->r_t;
+  la.d = batch->d_t;
+  la.probs = batch->probabilities;
+  la.global_min_prob = batch->global_min_probability;
+  la.B = B;
+  la.A = A;
+  la.mean_over = batch->mean_over > 0 ? (int)batch->mean_over : B;
+  la.discount = l->cfg.discount;
+  la.beta = l->cfg.importance_sampling_exponent;
+  la.delta = l->cfg.huber_loss_parameter;
+  la.max_abs_reward = l->cfg.max_abs_reward;
+  la.jax = l->cfg.semantics == ACME_SEMANTICS_JAX;
+  la.loss = loss;
+  la.td = td;
+  la.prio = prio;
+  la.g = l->g;
+  la.a_cache = l->a_cache;
+  if (l->step.last_p3) {  // fused with the head dZ (nature_backward)
+    la.loss_part = l->loss_part;
+    l->step.pending_la = la;
+    l->step.loss_pending = true;
+  } else {
+    ACME_PROF("loss", st, 0.0, 0.0);
+    if ((rc = launch_dqn_loss(la, st)) != ACME_OK) return rc;
+  }
+  rc = nature ? nature_backward(l, plan, batch->o_tm1, B, st, join_dense)
+              : mlp_backward(l, batch->o_tm1, B, st);
+  if (rc != ACME_OK) return rc;
+  // After the backward: on the plane path its first launch forms q_on (the online head).
+  if (out && out->q_tm1)
+    ACME_HIP_TRY(hipMemcpyAsync(out->q_tm1, l->q_on, (size_t)B * A * sizeof(float),
+                                hipMemcpyDeviceToDevice, st));
+  if (!l->step.dense_ev) {  // not on the side stream
+    ACME_HIP_TRY(hipEventRecord(l->ev_dense, st));
+    l->step.dense_ev = l->ev_dense;
+  }
+  return ACME_OK;
+}
 
 // Activation / gradient scales for new parameters (gemm_p3.h): kCalibrationPasses passes of
 // the step's forward, loss and backward on this batch (local IS normaliser, outputs to
@@ -1089,29 +1191,31 @@ static int loss_and_dense_backward(acme_dqn* l, const acme_transition_batch* bat
 // dz2 -> dz1) is four tensors deep, so four passes calibrate every record whatever the
 // gradients' magnitude (two left dz2 / dz1 at scale 1 when |TD| was ~1e-4: their planes
 // read as zeros, tests/test_step_guard_gpu.py).  Writes nothing the real step does not
-// overwrite.
+// overwrite; the passes run on a step state of their own, and the caller's is put back.
 constexpr int kCalibrationPasses = 4;
 static int calibrate_scales(acme_dqn* l, const acme_transition_batch* batch, hipStream_t st) {
   acme_transition_batch cb = *batch;
   cb.global_min_probability = nullptr;
-  l->calibrating = true;
+  StepPlan plan;  // whatever the caller's: not fused, no write-back, no join
+  plan.calibrating = true;
+  const StepState outer = l->step;
   int rc = ACME_OK;
   for (int pass = 0; pass < kCalibrationPasses && rc == ACME_OK; ++pass) {
-    rc = forward_backward_stage(l, &cb, nullptr, 2, st, false);
-    if (rc == ACME_OK) rc = forward_backward_stage(l, &cb, nullptr, 3, st, false);
-    if (rc == ACME_OK) rc = forward_backward_stage(l, &cb, nullptr, 1, st, false);
+    rc = forward_backward_stage(l, plan, &cb, nullptr, 2, st);
+    if (rc == ACME_OK) rc = forward_backward_stage(l, plan, &cb, nullptr, 3, st);
+    if (rc == ACME_OK) rc = forward_backward_stage(l, plan, &cb, nullptr, 1, st);
     if (rc == ACME_OK)
       rc = launch_plane_rescale(l->scales, kScTransient, kScTransient, -1, -1, l->overflow, st);
   }
-  l->calibrating = false;
+  l->step = outer;
   if (rc != ACME_OK) return rc;
   // Overflows at the initial scales are expected and corrected by the passes.
   return calibration_done(l, st);
 }
 
-static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batch,
-                                  const acme_dqn_outputs* out, int32_t stage, void* stream,
-                                  bool join_dense) {
+static int forward_backward_stage(acme_dqn* l, const StepPlan& plan,
+                                  const acme_transition_batch* batch,
+                                  const acme_dqn_outputs* out, int32_t stage, void* stream) {
   ACME_CHECK_ARG(l && batch && l->params, "null argument or unbound learner");
   ACME_CHECK_ARG(stage >= 0 && stage <= 4, "stage must be 0, 1, 2, 3 or 4");
   ACME_CHECK_ARG(batch->o_tm1 && batch->a_tm1 && batch->r_t && batch->d_t && batch->o_t &&
@@ -1127,47 +1231,10 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
     // element is written by its kernel (no accumulation), so nothing is cleared.
     if (!nature) return ACME_OK;
     if (use_p3(l)) {
-      torso::Grads g{Pm(l, l->grads, l->t_c1w), Pm(l, l->grads, l->t_c1b),
-                     Pm(l, l->grads, l->t_c2w), Pm(l, l->grads, l->t_c2b),
-                     Pm(l, l->grads, l->t_c3w), Pm(l, l->grads, l->t_c3b)};
-      torso::PWeights w{WP(l, l->wpl, l->t_c1w), WP(l, l->wpl, l->t_c2w),
-                        WP(l, l->wpl, l->t_c3w), P(l, l->params, l->t_c1b),
-                        P(l, l->params, l->t_c2b), P(l, l->params, l->t_c3b)};
-      torso::Side sd;
-      sd.single_role = l->single_role;
-      sd.bk32 = l->bk32;
-      // conv1's weight gradient on the single-role kernel: its two 20-KB stages (40 KB of
-      // LDS) fit beside the next step's fused target convolution (117 KB) that runs on the
-      // side stream at the same time; the producer / consumer kernel's three stages (60 KB)
-      // do not.  Step 0.4957 -> 0.4920 ms (three alternating 300-step pairs, round 6,
-      // profiles/r06/schedule/ab_conv1_wgrad_single_role.log).
-      sd.conv1_single = true;
-      if (side_stream(l)) {
-        sd.side = l->side;
-        sd.slab = l->side_slab;
-        for (int i = 0; i < 3; ++i) sd.e[i] = l->ev[i];
-      }
-      l->slabs_pending = false;
-      if (l->upd_replay && l->upd_prio && !l->calibrating) {
-        sd.tail = priority_update_tail;
-        sd.tail_ctx = l;
-        if (l->update_rider && l->fused_step && !l->dp_gate) {
-          sd.tail_rider = priority_update_rider;
-          sd.tail_rider_done = priority_update_rider_done;
-        }
-      }
-      if (l->fused_step && !l->calibrating && l->slab2) {
-        sd.slab = l->side_slab;
-        sd.slab2 = l->slab2;
-        sd.defer = l->wslabs;
-        l->slabs_pending = true;
-      }
-      int rc = torso::backward_p3(w, g, l->cur_frames, B,
-                                  torso::PActs{l->x1p, l->x2p, l->x3p}, l->dz3p, l->dz2p, l->dz1p,
-                                  l->slab, st, sd);
+      int rc = torso_backward_p3(l, plan, B, st);
       // Data parallelism: this rank's skip decision into the torso bucket's padding word,
       // which the ranks' all-reduce combines before Adam reads it (step_gate).
-      if (rc == ACME_OK && l->dp_gate && !l->calibrating) {
+      if (rc == ACME_OK && l->dp_gate && !plan.calibrating) {
         Gate local = step_gate(l);
         local.dp = nullptr;
         rc = launch_gate_publish(local, l->grads + l->dp_gate_index, st, l->scales,
@@ -1175,26 +1242,24 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
       }
       return rc;
     }
-    torso::Grads g{Pm(l, l->grads, l->t_c1w), Pm(l, l->grads, l->t_c1b), Pm(l, l->grads, l->t_c2w),
-                   Pm(l, l->grads, l->t_c2b), Pm(l, l->grads, l->t_c3w), Pm(l, l->grads, l->t_c3b)};
-    return torso::backward(torso_weights(l, l->params), g,
+    return torso::backward(torso_weights(l, l->params), torso_grads(l),
                            l->cfg.obs_dtype == ACME_OBS_U8_SCALED, batch->o_tm1, B,
                            torso::Acts{l->x1, l->x2, l->x3}, l->dz3, l->dz2, l->dz1, l->slab, st);
   }
-  const int A = l->cfg.num_actions;
   int rc;
   // Stage 0 = stage 2 (the forwards) + stage 3 (loss and the dense backward); a
   // data-parallel rank splits them to run the IS-normaliser all-reduce beside the forwards.
   if (stage == 3 || stage == 4) {
-    ACME_CHECK_ARG(l->fwd_batch == (int64_t)B, "stage %d needs the stage-2 forward of this batch",
-                   stage);
-    l->fwd_batch = 0;
-    return loss_and_dense_backward(l, batch, out, st, join_dense && stage == 3);
+    ACME_CHECK_ARG(l->step.fwd_batch == (int64_t)B,
+                   "stage %d needs the stage-2 forward of this batch", stage);
+    l->step.fwd_batch = 0;
+    return loss_and_dense_backward(l, plan, batch, out, st, plan.join_dense && stage == 3);
   }
   // Forward: online on [o_tm1; o_t] (q_tm1 rows 0..B-1, q_t_selector rows B..2B-1),
-  // target on o_t (q_t_value).
-  l->last_p3 = nature && use_p3(l);
-  if (l->last_p3) {
+  // target on o_t (q_t_value).  A step begins here: nothing of an earlier one is kept.
+  l->step = StepState{};
+  l->step.last_p3 = nature && use_p3(l);
+  if (l->step.last_p3) {
     // conv1's input: the batch's uint8 frames themselves (conv1's kernels widen them exactly
     // as they stage them: half the bytes of an f16 copy, and no copy), or an f16 copy (the
     // dataset's obs_f16, else our own).
@@ -1203,11 +1268,10 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
                       reinterpret_cast<uintptr_t>(batch->o_t)) & 15) == 0;
     // The caller's inputs event can stand for the fork only if nothing is enqueued here first.
     const bool quiet =
-        !l->planes_stale && l->scales_ok && (batch->obs_f16 || u8) && !l->calibrating;
+        !l->planes_stale && l->scales_ok && (batch->obs_f16 || u8) && !plan.calibrating;
     if ((rc = sync_planes(l, st)) != ACME_OK) return rc;
-    if (!l->scales_ok && !l->calibrating && (rc = calibrate_scales(l, batch, st)) != ACME_OK)
+    if (!l->scales_ok && !plan.calibrating && (rc = calibrate_scales(l, batch, st)) != ACME_OK)
       return rc;
-    l->last_p3 = true;
     hipStream_t tst = st;
     hipStream_t side = side_stream(l);
     // conv1's input: an f16 copy of [o_tm1; o_t] on the main stream for everything.  (Reading
@@ -1221,7 +1285,7 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
         u8 ? torso::Frames{batch->o_tm1, true, batch->o_t, B}
            : torso::Frames{batch->obs_f16 ? static_cast<const void*>(batch->obs_f16)
                                           : static_cast<const void*>(l->frames)};
-    l->cur_frames = fwd_frames;
+    l->step.cur_frames = fwd_frames;
     // Target forward (q_t_value) on the side stream, beside the online forward.
     if (side) {
       // Early start: the side stream's own order covers the previous step's target work
@@ -1232,7 +1296,7 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
         ACME_HIP_TRY(hipEventRecord(l->ev[0], st));
         ACME_HIP_TRY(hipStreamWaitEvent(side, l->ev[0], 0));
       }
-      l->target_dirty = l->calibrating;
+      l->target_dirty = plan.calibrating;
       tst = side;
     } else {
       l->target_dirty = true;  // the target forward runs on the caller's stream
@@ -1242,7 +1306,6 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
     // windows 0.5208 -> 0.5181 ms, three alternating runs each).  Either order gives the
     // same bits.
     const bool online_first = side != nullptr;
-    l->head_deferred = false;
     if (online_first &&
         (rc = nature_forward_p3(l, l->params, l->wpl, fwd_frames, 2 * B, l->x1p, l->x2p, l->x3p,
                                 l->hid, l->q_on, st, nullptr, B, true)) != ACME_OK)
@@ -1282,73 +1345,18 @@ static int forward_backward_stage(acme_dqn* l, const acme_transition_batch* batc
       return rc;
   }
   if (stage == 2) {
-    l->fwd_batch = B;
+    l->step.fwd_batch = B;
     return ACME_OK;
   }
-  return loss_and_dense_backward(l, batch, out, st, join_dense);
-}
-
-// Loss (fused into the head dZ on the plane path) and the dense layers' backward, after
-// the forwards of the same batch.
-static int loss_and_dense_backward(acme_dqn* l, const acme_transition_batch* batch,
-                                   const acme_dqn_outputs* out, hipStream_t st, bool join_dense) {
-  const int B = (int)batch->batch, A = l->cfg.num_actions;
-  const bool nature = l->cfg.network == ACME_NET_NATURE_DQN;
-  int rc;
-  float* loss = out && out->loss ? out->loss : l->loss_tmp;
-  float* td = out && out->td_error ? out->td_error : l->td_tmp;
-  double* prio = out && out->priorities ? out->priorities : l->prio_tmp;
-  LossArgs la;
-  la.q_on = l->q_on;
-  la.q_tg = l->q_tg;
-  la.a = batch->a_tm1;
-  la.r = batch->r_t;
-  la.d = batch->d_t;
-  la.probs = batch->probabilities;
-  la.global_min_prob = batch->global_min_probability;
-  la.B = B;
-  la.A = A;
-  la.mean_over = batch->mean_over > 0 ? (int)batch->mean_over : B;
-  la.discount = l->cfg.discount;
-  la.beta = l->cfg.importance_sampling_exponent;
-  la.delta = l->cfg.huber_loss_parameter;
-  la.max_abs_reward = l->cfg.max_abs_reward;
-  la.jax = l->cfg.semantics == ACME_SEMANTICS_JAX;
-  la.loss = loss;
-  la.td = td;
-  la.prio = prio;
-  la.g = l->g;
-  la.a_cache = l->a_cache;
-  if (l->last_p3) {  // fused with the head dZ (nature_backward)
-    la.loss_part = l->loss_part;
-    l->pending_la = la;
-    l->loss_pending = true;
-  } else {
-    ACME_PROF("loss", st, 0.0, 0.0);
-    if ((rc = launch_dqn_loss(la, st)) != ACME_OK) return rc;
-  }
-  l->dense_on_side = false;
-  rc = nature ? nature_backward(l, batch->o_tm1, B, st, join_dense)
-              : mlp_backward(l, batch->o_tm1, B, st);
-  if (rc != ACME_OK) return rc;
-  // After the backward: on the plane path its first launch forms q_on (the online head).
-  if (out && out->q_tm1)
-    ACME_HIP_TRY(hipMemcpyAsync(out->q_tm1, l->q_on, (size_t)B * A * sizeof(float),
-                                hipMemcpyDeviceToDevice, st));
-  if (l->dense_on_side) {
-    l->dense_ev = l->ev[3];
-  } else {
-    ACME_HIP_TRY(hipEventRecord(l->ev_dense, st));
-    l->dense_ev = l->ev_dense;
-  }
-  return ACME_OK;
+  return loss_and_dense_backward(l, plan, batch, out, st, plan.join_dense);
 }
 
 int acme_dqn_forward_backward(acme_dqn* l, const acme_transition_batch* batch,
                               const acme_dqn_outputs* out, void* stream) {
-  int rc = forward_backward_stage(l, batch, out, 0, stream, false);
+  const StepPlan plan;
+  int rc = forward_backward_stage(l, plan, batch, out, 0, stream);
   if (rc != ACME_OK) return rc;
-  return forward_backward_stage(l, batch, out, 1, stream, false);
+  return forward_backward_stage(l, plan, batch, out, 1, stream);
 }
 
 int acme_dqn_grad_split(const acme_dqn* l, int64_t* split) {
@@ -1357,8 +1365,16 @@ int acme_dqn_grad_split(const acme_dqn* l, int64_t* split) {
   return ACME_OK;
 }
 
-// Adam (+ the parameter planes) and the periodic target copy; `copy` decided by the host.
-static int apply_impl(acme_dqn* l, bool copy, hipStream_t st) {
+// TF: copy when num_steps % period == 0, then num_steps += 1 (tf/dqn/learning.py:157-161);
+// JAX: steps + 1 first, copy when that is a multiple of the period (jax/dqn/learning.py:114-119).
+static bool copies_target(const acme_dqn* l) {
+  const int64_t at = l->cfg.semantics == ACME_SEMANTICS_JAX ? l->num_steps + 1 : l->num_steps;
+  return at % l->cfg.target_update_period == 0;
+}
+
+// Adam (+ the parameter planes), the periodic target copy, and the step counted.
+static int apply_impl(acme_dqn* l, hipStream_t st) {
+  const bool copy = copies_target(l);
   int rc = ACME_OK;
   Gate gate;  // Adam reads the step's skip decision, made by the step's rescale
   AdamTail tail;
@@ -1370,16 +1386,16 @@ static int apply_impl(acme_dqn* l, bool copy, hipStream_t st) {
     // (the fused step's priority write-back already ran it, with deferred read scales); the
     // target forward's records were rescaled after it (on the side stream, which may
     // already run the next step's target forward).
-    if (!l->step_rescaled) {
+    if (!l->step.rescaled) {
       ACME_PROF("plane_rescale", st, 0.0, 0.0);
-      if ((rc = launch_rescale_job(step_rescale_job(l, false), st)) != ACME_OK) return rc;
+      if ((rc = launch_rescale_job(take_step_rescale(l, false), st)) != ACME_OK) return rc;
     } else {
       tail.commit = l->scales;
       tail.ncommit = kScTransient;
       tail.skip_lo = kScT1;
       tail.skip_hi = kScT3 + 1;
     }
-    l->step_rescaled = false;
+    l->step.rescaled = false;
     gate.g = l->guard;
     gate.use_last = 1;
     tail.clear = l->guard;
@@ -1390,18 +1406,18 @@ static int apply_impl(acme_dqn* l, bool copy, hipStream_t st) {
   // parameter planes it writes for the next forward (2 x 2 B), and on the fused step the conv
   // weight gradients' split-K slabs it reduces on its read (and their reduced gradients).
   const double adam_bytes = 28.0 * (double)l->logical + (l->p3_capable ? 4.0 * (double)l->flat : 0.0);
-  if (l->slabs_pending) {  // the conv weight gradients reduced on Adam's read
-    l->slabs_pending = false;
+  if (l->step.slabs_pending) {  // the conv weight gradients reduced on Adam's read
+    l->step.slabs_pending = false;
     double slab_bytes = 0.0;
     for (int k = 0; k < 3; ++k) {
-      const double count4 = (double)((l->wslabs[k].wcount + l->wslabs[k].bcount) / 4);
-      slab_bytes += 16.0 * count4 * (double)(l->wslabs[k].splits + 1);
+      const double count4 = (double)((l->step.wslabs[k].wcount + l->step.wslabs[k].bcount) / 4);
+      slab_bytes += 16.0 * count4 * (double)(l->step.wslabs[k].splits + 1);
     }
     ACME_PROF("adam", st, 0.0, adam_bytes + slab_bytes);
     const int ten[3][2] = {{l->t_c1w, l->t_c1b}, {l->t_c2w, l->t_c2b}, {l->t_c3w, l->t_c3b}};
     AdamSlabs a;
     for (int k = 0; k < 3; ++k) {
-      const torso::WgradSlab& w = l->wslabs[k];
+      const torso::WgradSlab& w = l->step.wslabs[k];
       const int64_t count4 = (w.wcount + w.bcount) / 4;
       for (int j = 0; j < 2; ++j) {
         const Tensor& t = l->tensors[ten[k][j]];
@@ -1443,40 +1459,32 @@ static int apply_impl(acme_dqn* l, bool copy, hipStream_t st) {
         return rc;
     }
     ACME_PROF("param_rescale", st, 0.0, 0.0);
-    rc = launch_plane_rescale(l->scales + kScParams, 0, 1, -1, -1, l->overflow, st);
+    if ((rc = launch_plane_rescale(l->scales + kScParams, 0, 1, -1, -1, l->overflow, st)))
+      return rc;
   }
-  return rc;
-}
-
-// TF: copy when num_steps % period == 0, then num_steps += 1 (tf/dqn/learning.py:157-161);
-// JAX: steps + 1 first, copy when that is a multiple of the period (jax/dqn/learning.py:114-119).
-static bool copies_target(const acme_dqn* l) {
-  const int64_t at = l->cfg.semantics == ACME_SEMANTICS_JAX ? l->num_steps + 1 : l->num_steps;
-  return at % l->cfg.target_update_period == 0;
-}
-
-int acme_dqn_apply(acme_dqn* l, void* stream) {
-  ACME_CHECK_ARG(l && l->params, "unbound learner");
-  int rc = apply_impl(l, copies_target(l), as_stream(stream));
-  if (rc != ACME_OK) return rc;
   l->num_steps += 1;
   l->seq += 1;
   return ACME_OK;
 }
 
-static int step_impl(acme_dqn* l, const acme_transition_batch* batch, const acme_dqn_outputs* out,
-                     bool copy, hipStream_t st) {
-  int rc = forward_backward_stage(l, batch, out, 0, st, false);
-  l->fused_step = true;
-  if (rc == ACME_OK) rc = forward_backward_stage(l, batch, out, 1, st, false);
-  l->fused_step = false;
-  if (rc == ACME_OK) rc = apply_impl(l, copy, st);
+int acme_dqn_apply(acme_dqn* l, void* stream) {
+  ACME_CHECK_ARG(l && l->params, "unbound learner");
+  return apply_impl(l, as_stream(stream));
+}
+
+// The fused step: plan.fused changes stage 1 (and through the state it leaves, Adam); stage 0
+// runs as a staged caller's.
+static int step_impl(acme_dqn* l, const StepPlan& plan, const acme_transition_batch* batch,
+                     const acme_dqn_outputs* out, hipStream_t st) {
+  int rc = forward_backward_stage(l, plan, batch, out, 0, st);
+  if (rc == ACME_OK) rc = forward_backward_stage(l, plan, batch, out, 1, st);
+  if (rc == ACME_OK) rc = apply_impl(l, st);
   return rc;
 }
 
 int acme_dqn_dense_grads_ready(acme_dqn* l, void* stream) {
-  ACME_CHECK_ARG(l && l->dense_ev, "no stage 3 / 4 has run");
-  ACME_HIP_TRY(hipStreamWaitEvent(as_stream(stream), l->dense_ev, 0));
+  ACME_CHECK_ARG(l && l->step.dense_ev, "no stage 3 / 4 has run");
+  ACME_HIP_TRY(hipStreamWaitEvent(as_stream(stream), l->step.dense_ev, 0));
   return ACME_OK;
 }
 
@@ -1524,18 +1532,19 @@ int acme_dqn_dp_step(acme_dqn* l, const acme_transition_batch* batch, const acme
   ACME_HIP_TRY(hipEventRecord(l->dp_ev[1], cs));
   acme_transition_batch b = *batch;
   b.global_min_probability = l->dp_gmin;
-  if ((rc = forward_backward_stage(l, &b, out, 2, st, false))) return rc;
+  const StepPlan plan;
+  if ((rc = forward_backward_stage(l, plan, &b, out, 2, st))) return rc;
   ACME_HIP_TRY(hipStreamWaitEvent(st, l->dp_ev[1], 0));
-  if ((rc = forward_backward_stage(l, &b, out, 4, st, false))) return rc;
+  if ((rc = forward_backward_stage(l, plan, &b, out, 4, st))) return rc;
   int64_t split = 0;
   if ((rc = acme_dqn_grad_split(l, &split))) return rc;
-  ACME_HIP_TRY(hipStreamWaitEvent(cs, l->dense_ev, 0));
+  ACME_HIP_TRY(hipStreamWaitEvent(cs, l->step.dense_ev, 0));
   const ncclRedOp_t avg = static_cast<ncclRedOp_t>(ncclAvg);
   if ((rc = nccl(r->AllReduce(l->grads + split, l->grads + split, (size_t)(l->flat - split),
                               ncclFloat32, avg, comm, cs),
                  "all-reduce (dense gradients)")))
     return rc;
-  if ((rc = forward_backward_stage(l, &b, out, 1, st, false))) return rc;
+  if ((rc = forward_backward_stage(l, plan, &b, out, 1, st))) return rc;
   if (split > 0) {
     ACME_HIP_TRY(hipEventRecord(l->dp_ev[2], st));
     ACME_HIP_TRY(hipStreamWaitEvent(cs, l->dp_ev[2], 0));
@@ -1545,10 +1554,7 @@ int acme_dqn_dp_step(acme_dqn* l, const acme_transition_batch* batch, const acme
   }
   ACME_HIP_TRY(hipEventRecord(l->dp_ev[3], cs));
   ACME_HIP_TRY(hipStreamWaitEvent(st, l->dp_ev[3], 0));
-  if ((rc = apply_impl(l, copies_target(l), st))) return rc;
-  l->num_steps += 1;
-  l->seq += 1;
-  return ACME_OK;
+  return apply_impl(l, st);
 }
 
 int acme_dqn_step_update(acme_dqn* l, const acme_transition_batch* batch,
@@ -1556,40 +1562,33 @@ int acme_dqn_step_update(acme_dqn* l, const acme_transition_batch* batch,
                          void* after_event, void* stream) {
   ACME_CHECK_ARG(l && batch && l->params, "null argument or unbound learner");
   ACME_CHECK_ARG(replay && keys, "null replay or keys");
-  const bool inside = use_p3(l) && l->cfg.network == ACME_NET_NATURE_DQN && !l->calibrating;
-  l->upd_replay = inside ? replay : nullptr;
-  l->upd_keys = keys;
-  l->upd_prio = nullptr;
-  l->upd_after = static_cast<hipEvent_t>(after_event);
-  int rc = step_impl(l, batch, out, copies_target(l), as_stream(stream));
-  const bool pending = l->upd_replay != nullptr || !inside;
-  l->upd_replay = nullptr;
-  if (rc != ACME_OK) return rc;
-  l->num_steps += 1;
-  l->seq += 1;
-  if (pending) {  // not issued inside the step (other paths): after it, on the stream
-    const double* prio = out && out->priorities ? out->priorities : l->prio_tmp;
-    if (after_event)
-      ACME_HIP_TRY(hipStreamWaitEvent(as_stream(stream), static_cast<hipEvent_t>(after_event), 0));
-    Gate q;  // the plane path's step has ended: its skip decision is `last`
-    if (l->p3_capable) {
-      q.g = l->guard;
-      q.use_last = 1;
-    }
-    return replay_update_priorities_gated(replay, keys, prio, batch->batch, q,
-                                          as_stream(stream));
+  StepPlan plan;
+  plan.fused = true;
+  if (use_p3(l) && l->cfg.network == ACME_NET_NATURE_DQN) {  // inside the step
+    plan.replay = replay;
+    plan.keys = keys;
+    plan.after = static_cast<hipEvent_t>(after_event);
   }
-  return ACME_OK;
+  const int rc = step_impl(l, plan, batch, out, as_stream(stream));
+  if (rc != ACME_OK || l->step.update_issued) return rc;
+  // Not issued inside the step (other paths): after it, on the stream.
+  const double* prio = out && out->priorities ? out->priorities : l->prio_tmp;
+  if (after_event)
+    ACME_HIP_TRY(hipStreamWaitEvent(as_stream(stream), static_cast<hipEvent_t>(after_event), 0));
+  Gate q;  // the plane path's step has ended: its skip decision is `last`
+  if (l->p3_capable) {
+    q.g = l->guard;
+    q.use_last = 1;
+  }
+  return replay_update_priorities_gated(replay, keys, prio, batch->batch, q, as_stream(stream));
 }
 
 int acme_dqn_step(acme_dqn* l, const acme_transition_batch* batch, const acme_dqn_outputs* out,
                   void* stream) {
   ACME_CHECK_ARG(l && batch && l->params, "null argument or unbound learner");
-  const int rc = step_impl(l, batch, out, copies_target(l), as_stream(stream));
-  if (rc != ACME_OK) return rc;
-  l->num_steps += 1;
-  l->seq += 1;
-  return ACME_OK;
+  StepPlan plan;
+  plan.fused = true;
+  return step_impl(l, plan, batch, out, as_stream(stream));
 }
 
 }  // extern "C"

@@ -112,20 +112,6 @@ struct Side {
   // conv2 then use `slab` and `slab2` (both needed, with or without the side stream).
   float* slab2 = nullptr;
   WgradSlab* defer = nullptr;
-  // Optional work for the main stream after its last kernel, before the join (the DQN
-  // step's priority write-back, which balances the two streams' backward).
-  int (*tail)(void* ctx, hipStream_t st) = nullptr;
-  void* tail_ctx = nullptr;
-  // Optional: the tail as a rider of conv1's weight-gradient launch (the replay table's
-  // priority update in that launch's leading workgroups, prio_update.h UpdateRider; needs
-  // conv1_single).  Called before the launch: it issues the tail's stream waits and, when it
-  // sets *armed, fills the rider's arguments; tail_rider_done is then called right after the
-  // launch and `tail` is not.  Not armed (a tail of another shape): `tail` runs as usual.
-  int (*tail_rider)(void* ctx, hipStream_t st, FusedUpdateArgs* out, bool* armed) = nullptr;
-  void (*tail_rider_done)(void* ctx) = nullptr;
-  // conv1's weight gradient on the single-role kernel instead of the producer / consumer one
-  // (the same bits; tests, ACME_V_WSN=1 at the learner's creation).
-  bool single_role = false;
   bool conv1_single = false;  // conv1's weight gradient on the single-role kernel (the DQN step)
   bool bk32 = false;          // the image-resident input gradients at a stage depth of 32 k
 };
@@ -133,6 +119,20 @@ struct Side {
 int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int rows,
                 const PActs& a, const Plane& dz3, const Plane& dz2, const Plane& dz1, float* slab,
                 hipStream_t st, const Side& side = Side());
+// backward_p3 is these three in order; a caller with work of its own for the main stream
+// around conv1's weight gradient (the DQN step's priority write-back) issues them itself:
+//   _convs: conv3's and conv2's weight and input gradients, with their forks;
+//   _conv1: conv1's weight gradient and its reduction (or sd.defer[0]); with `rider`, the
+//           replay table's priority update in that launch's leading workgroups
+//           (prio_update.h UpdateRider; needs sd.conv1_single);
+//   _join:  the main stream waits for the side stream's weight gradients.
+int backward_p3_convs(const PWeights& w, const Grads& g, int rows, const PActs& a,
+                      const Plane& dz3, const Plane& dz2, const Plane& dz1, float* slab,
+                      hipStream_t st, const Side& side);
+int backward_p3_conv1(const Grads& g, const Frames& frames, int rows, const Plane& dz1,
+                      float* slab, hipStream_t st, const Side& side,
+                      const FusedUpdateArgs* rider = nullptr);
+int backward_p3_join(hipStream_t st, const Side& side);
 
 }  // namespace torso
 }  // namespace acme

@@ -202,41 +202,45 @@ int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, c
   return ACME_OK;
 }
 
-// conv1's weight + bias gradient (split-K slabs) from the frames of rows [0, rows).
-template <bool U8>
-int conv1_wgrad_p3(const Frames& frames, int rows, const Plane& dz1, float* slab, int splits,
-                   bool single_role, P3ConvWgrad<G1, 1, U8>& p, hipStream_t st,
-                   const FusedUpdateArgs* rider = nullptr) {
-  if (U8 && frames.split < rows)
-    return (set_error("conv1's weight gradient reads its frames from one buffer"),
-            ACME_ERR_INVALID);
-  P3ConvWgrad<G1, 1, U8> q;
-  q.M = G1::K; q.N = G1::CO; q.K = rows * G1::OPIX;
-  q.k_chunk = chunk_for(q.K, splits);
-  q.a_src = frames_src(frames, rows); q.b_src = SRC(dz1, (int64_t)rows * kX1);
-  q.slab = slab;
-  // Producer / consumer waves (gemm_p3ws_kernel): 28.5 -> 25.0 us, the same bits.
-  // With a rider (single-role only): the priority write-back in the launch's first
-  // workgroups, in the same 40 KB of LDS, so the launch still fits beside the side stream's
-  // fused target convolution (117 KB).
-  if (rider && !single_role)
-    return (set_error("the update rider needs conv1's single-role kernel"), ACME_ERR_INVALID);
-  if (rider)
-    ACME_LAUNCH_GEMM("conv1_wgrad", ACME_MNK_FLOPS(q), gemm::p3_peak_tflops<decltype(q)>(),
-                     (gemm::launch_gemm_p3_rider<256, 32, 4, 1, 32, UpdateRider>(q, splits, *rider,
-                                                                                 st)));
-  else if (single_role) ACME_P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
-  else ACME_P3WS_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, q, splits);
-  p = q;
-  return ACME_OK;
-}
-
 template <class P>
 int p3_wgrad_reduce(const P& p, int splits, float* slab, float* dw, float* db, const char* rname,
                     hipStream_t st) {
   const int64_t count = (int64_t)(p.M + 1) * p.N;
   ACME_PROF(rname, st, 0.0, 4.0 * (double)(splits + 1) * (double)count);
   return launch_slab_reduce(slab, splits, count, dw, (int64_t)p.M * p.N, db, nullptr, 0, 0, st);
+}
+
+// conv1's weight + bias gradient from the frames of rows [0, rows), f16 or uint8 frames: its
+// split-K slabs, then their reduction or (sd.defer) their description for the consumer.
+template <bool U8>
+int conv1_wgrad_p3(const Grads& g, const Frames& frames, int rows, const Plane& dz1, float* slab,
+                   hipStream_t st, const Side& sd, const FusedUpdateArgs* rider) {
+  if (U8 && frames.split < rows)
+    return (set_error("conv1's weight gradient reads its frames from one buffer"),
+            ACME_ERR_INVALID);
+  const int splits = kP3Conv1WgradSplits;
+  P3ConvWgrad<G1, 1, U8> p;
+  p.M = G1::K; p.N = G1::CO; p.K = rows * G1::OPIX;
+  p.k_chunk = chunk_for(p.K, splits);
+  p.a_src = frames_src(frames, rows); p.b_src = SRC(dz1, (int64_t)rows * kX1);
+  p.slab = slab;
+  // Producer / consumer waves (gemm_p3ws_kernel): 28.5 -> 25.0 us, the same bits.
+  // With a rider (single-role only): the priority write-back in the launch's first
+  // workgroups, in the same 40 KB of LDS, so the launch still fits beside the side stream's
+  // fused target convolution (117 KB).
+  if (rider && !sd.conv1_single)
+    return (set_error("the update rider needs conv1's single-role kernel"), ACME_ERR_INVALID);
+  if (rider)
+    ACME_LAUNCH_GEMM("conv1_wgrad", ACME_MNK_FLOPS(p), gemm::p3_peak_tflops<decltype(p)>(),
+                     (gemm::launch_gemm_p3_rider<256, 32, 4, 1, 32, UpdateRider>(p, splits, *rider,
+                                                                                 st)));
+  else if (sd.conv1_single) ACME_P3_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, p, splits);
+  else ACME_P3WS_GEMM("conv1_wgrad", 256, 32, 4, 1, 32, p, splits);
+  if (sd.defer) {
+    sd.defer[0] = WgradSlab{slab, splits, (int64_t)p.M * p.N, p.N};
+    return ACME_OK;
+  }
+  return p3_wgrad_reduce(p, splits, slab, g.w1, g.b1, "conv1_wgrad_reduce", st);
 }
 
 }  // namespace
@@ -291,9 +295,9 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
   return ACME_OK;
 }
 
-int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int rows,
-                const PActs& a, const Plane& dz3, const Plane& dz2, const Plane& dz1, float* slab,
-                hipStream_t st_main, const Side& sd) {
+int backward_p3_convs(const PWeights& w, const Grads& g, int rows, const PActs& a,
+                      const Plane& dz3, const Plane& dz2, const Plane& dz1, float* slab,
+                      hipStream_t st_main, const Side& sd) {
   int rc;
   // Weight gradients of conv3 and conv2 go to the side stream (when given): each only
   // waits for its layer's dZ, and runs beside the next input gradient on the main stream
@@ -364,42 +368,27 @@ int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int row
                            : gemm::launch_gemm_p3s<G2, 2, kBkConv2Dgrad>(p, rows, st);
     if (e != hipSuccess) return (set_error("gemm launch failed: %s", hipGetErrorString(e)), ACME_ERR_HIP);
   }
-  // The tail as conv1_wgrad's rider: everything it reads is written by now (the priorities
-  // by the loss launch, the last amax record by conv2's input gradient above), and the
-  // weight gradient writes only f32 slabs.
-  FusedUpdateArgs upd;
-  bool rider = false;
-  if (sd.tail && sd.tail_rider && sd.tail_rider_done && sd.conv1_single &&
-      (rc = sd.tail_rider(sd.tail_ctx, st_main, &upd, &rider)) != ACME_OK)
-    return rc;
-  const FusedUpdateArgs* ride = rider ? &upd : nullptr;
-  {  // conv1 (no input gradient)
-    const int splits = kP3Conv1WgradSplits;
-    int64_t wcount;
-    int M1, N1;
-    if (frames.u8) {
-      P3ConvWgrad<G1, 1, true> p;
-      rc = conv1_wgrad_p3<true>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st, ride);
-      if (rider) sd.tail_rider_done(sd.tail_ctx);
-      if (rc) return rc;
-      M1 = p.M, N1 = p.N;
-      if (!defer && (rc = p3_wgrad_reduce(p, splits, slab, g.w1, g.b1, "conv1_wgrad_reduce", st)))
-        return rc;
-    } else {
-      P3ConvWgrad<G1, 1> p;
-      rc = conv1_wgrad_p3<false>(frames, rows, dz1, slab, splits, sd.conv1_single, p, st, ride);
-      if (rider) sd.tail_rider_done(sd.tail_ctx);
-      if (rc) return rc;
-      M1 = p.M, N1 = p.N;
-      if (!defer && (rc = p3_wgrad_reduce(p, splits, slab, g.w1, g.b1, "conv1_wgrad_reduce", st)))
-        return rc;
-    }
-    wcount = (int64_t)M1 * N1;
-    if (defer) sd.defer[0] = WgradSlab{slab, splits, wcount, N1};
-  }
-  if (sd.tail && !rider && (rc = sd.tail(sd.tail_ctx, st_main)) != ACME_OK) return rc;
-  if (fork) ACME_HIP_TRY(hipStreamWaitEvent(st_main, sd.e[2], 0));  // join
   return ACME_OK;
+}
+
+int backward_p3_conv1(const Grads& g, const Frames& frames, int rows, const Plane& dz1,
+                      float* slab, hipStream_t st, const Side& sd, const FusedUpdateArgs* rider) {
+  return frames.u8 ? conv1_wgrad_p3<true>(g, frames, rows, dz1, slab, st, sd, rider)
+                   : conv1_wgrad_p3<false>(g, frames, rows, dz1, slab, st, sd, rider);
+}
+
+int backward_p3_join(hipStream_t st_main, const Side& sd) {
+  if (sd.side) ACME_HIP_TRY(hipStreamWaitEvent(st_main, sd.e[2], 0));
+  return ACME_OK;
+}
+
+int backward_p3(const PWeights& w, const Grads& g, const Frames& frames, int rows,
+                const PActs& a, const Plane& dz3, const Plane& dz2, const Plane& dz1, float* slab,
+                hipStream_t st, const Side& sd) {
+  int rc = backward_p3_convs(w, g, rows, a, dz3, dz2, dz1, slab, st, sd);
+  if (rc == ACME_OK) rc = backward_p3_conv1(g, frames, rows, dz1, slab, st, sd);
+  if (rc == ACME_OK) rc = backward_p3_join(st, sd);
+  return rc;
 }
 
 }  // namespace torso

@@ -385,6 +385,97 @@ def test_split_forward_stages_bitwise(kind):
         n.forward_backward_stage(3, *dev, global_min_probability=gmin)
 
 
+def _assert_same_learner(a, b):
+    assert a.loss.item() == b.loss.item()
+    for buf in ("params", "target", "m", "v"):
+        ga, gb = a.get_params(buf), b.get_params(buf)
+        for k in ga:
+            np.testing.assert_array_equal(ga[k], gb[k], err_msg=f"{buf}/{k}")
+
+
+def test_abandoned_staged_forward_cannot_feed_a_later_stage():
+    """A stage-2 forward that a whole step follows is gone: the step's forward begins a new
+    step state, so stage 3 of the first batch is refused instead of computing its loss from the
+    step's activations.  The refusal leaves nothing: the next step equals, bit for bit, that
+    step on a twin that ran only the two steps.
+
+    The step's batch holds the abandoned forward's transitions again, in buffers of its own.
+    The plane scales are powers of two from each tensor's maximum over the forwards since the
+    record's last rescale, on the device: with the same transitions the abandoned forward (and
+    the calibration that the learner's first forward runs, here on the abandoned batch, on the
+    twin on the step's) measures the maxima the twin measures, so the comparison is exact by
+    construction and not by two batches' maxima sharing a binade."""
+    from acme_amd.networks import DQNAtariNetwork
+    net = DQNAtariNetwork(18)
+    B = 32
+    p0, t0 = net.init(1), net.init(2)
+    a = _learner(net, B, target_update_period=2)
+    b = _learner(net, B, target_update_period=2)
+    a.set_params(p0, t0)
+    b.set_params(p0, t0)
+    rng = np.random.default_rng(17)
+    batch, batch3 = (_dev(_batch(rng, B, (84, 84, 4), 18)) for _ in range(2))
+    batch2 = [t.clone() for t in batch]
+    a.forward_backward_stage(2, *batch)
+    a.step(*batch2)
+    b.step(*batch2)
+    with pytest.raises(ValueError, match="needs the stage-2 forward of this batch"):
+        a.forward_backward_stage(3, *batch)
+    a.step(*batch3)
+    b.step(*batch3)
+    torch.cuda.synchronize()
+    assert a.num_steps == b.num_steps == 2
+    _assert_same_learner(a, b)
+
+
+def test_refused_call_leaves_no_state():
+    """A step refused for its batch size (by the wrapper, and by the library itself), between
+    a step with the in-step priority write-back and one without, changes nothing: learner and
+    table stay bit-identical to twins that never saw the refused calls."""
+    import ctypes
+    from acme_amd import _lib
+    from acme_amd.native import NativeReplay, ptr
+    from acme_amd.networks import DQNAtariNetwork
+    net = DQNAtariNetwork(18)
+    B = 32
+    p0, t0 = net.init(3), net.init(4)
+    learners = [_learner(net, B, target_update_period=2) for _ in range(2)]
+    tables = [NativeReplay(4096, [4], prioritized=True, priority_exponent=0.6, seed=5)
+              for _ in range(2)]
+    rows = np.arange(3000, dtype=np.uint32).view(np.uint8).reshape(3000, 4)
+    for d, t in zip(learners, tables):
+        d.set_params(p0, t0)
+        t.insert([rows], np.linspace(0.5, 2.0, 3000))
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(19)
+    first, second = (_dev(_batch(rng, B, (84, 84, 4), 18)) for _ in range(2))
+    big = _dev(_batch(rng, B + 1, (84, 84, 4), 18))
+    for refuse, (d, t) in zip((True, False), zip(learners, tables)):
+        keys = t.sample(B, 0)["keys"]
+        d.step(*first, priority_update=(t.handle, keys))
+        if refuse:
+            big_keys = torch.zeros(B + 1, dtype=torch.int64, device="cuda")  # never read
+            with pytest.raises(ValueError):
+                d.step(*big, priority_update=(t.handle, big_keys))
+            # The same refusal by the library: the wrapper's check of the batch size bypassed.
+            tb, out = d._batch(*first), d._outputs()
+            tb.batch = B + 1
+            for call in (lambda: _lib.lib().acme_dqn_step(d._h, ctypes.byref(tb),
+                                                          ctypes.byref(out), None),
+                         lambda: _lib.lib().acme_dqn_step_update(
+                             d._h, ctypes.byref(tb), ctypes.byref(out), t.handle, ptr(big_keys),
+                             None, None)):
+                assert call() == _lib.ACME_ERR_INVALID
+        d.step(*second)
+    torch.cuda.synchronize()
+    assert learners[0].num_steps == learners[1].num_steps == 2
+    _assert_same_learner(*learners)
+    sa, sb = tables[0].debug_state(), tables[1].debug_state()
+    for k in ("leaves", "raw", "keys"):
+        np.testing.assert_array_equal(sa[k], sb[k], err_msg=k)
+    assert not np.array_equal(sa["raw"][:3000], np.linspace(0.5, 2.0, 3000))  # written back
+
+
 @pytest.mark.parametrize("kind", ["nature", "mlp"])
 def test_step_with_priority_update_equals_step_then_update(kind):
     """acme_dqn_step_update (the write-back issued inside the step, on the second stream on
