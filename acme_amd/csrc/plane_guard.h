@@ -40,12 +40,16 @@ struct PlaneGuard {
   int n_scales = 0;
 };
 
-// The zeroed guard and its pinned host mirror.
+// The zeroed guard and its pinned host mirror.  vseq starts at "no verdict" (all ones, as the
+// host ring's entries): zero reads as "verdict 0: applied", and the first step's priority
+// write-back, which waits for verdict 0, would take it for its own before the rescale
+// workgroup has decided.
 template <class L>
 int guard_create(L* l) {
   int rc = dev_alloc(l, &l->guard, 1);
   if (rc != ACME_OK) return rc;
   if (hipMemset(l->guard, 0, sizeof(StepGuard)) != hipSuccess ||
+      hipMemset(&l->guard->vseq, 0xFF, sizeof(uint32_t)) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&l->host_skipped), sizeof(int64_t),
                     hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
     return (set_error("step guard allocation failed"), ACME_ERR_HIP);

@@ -23,6 +23,7 @@ from tests import test_d4pg_gpu as d4pg_t
 from tests import test_dqn_gpu as dqn_t
 from tests import test_impala_gpu as impala_t
 from tests import test_r2d2_learner_gpu as r2d2_t
+from tests import test_step_guard_gpu as guard_t
 
 # ------------------------------------------------------------------ DQN
 
@@ -135,6 +136,163 @@ def dqn_acting_edge(name):
     net = DQNAtariNetwork(18)
     draw = dqn_params if biased else (lambda net_, seed: net_.init(seed))
     return net, draw(net, 1), draw(net, 2), np.full((n,) + net.obs_shape, value, np.uint8)
+
+
+# ------------------------------------------------------------------ DQN plane-engine inputs
+
+# Batch schedules of the learner step on frames that i.i.d. uniform bytes never produce
+# (tests/test_plane_inputs_gpu.py; shown to produce their edge on the oracle alone by
+# tests/test_plane_inputs_cpu.py).  id -> (biased, the frames of each batch in turn, the
+# learner's learning rate).  Every batch is test_step_guard_gpu._batch's draw (actions,
+# N(0, 1.5) rewards, discounts, probabilities) with its frames replaced, B = 5: conv2_fwd's
+# last two-frame block half empty, the fc tile partial.
+#   black   every byte 0 (under net.init's zero biases every activation, every input
+#           gradient below the head and every weight gradient is identically zero);
+#   random  _batch's own uniform bytes;
+#   dark    bytes drawn from {0, 1};  saturated  every byte 255 (x1's maximum moves about
+#           255-fold between the two);
+#   sparse  an Atari-like stack: black background and a few rectangles of bytes in
+#           128..255, o_t the stack of o_tm1 one position on (plane_sparse_frames).
+DQN_PLANE_B = 5
+# learning rate 0 where the schedule needs the biases to stay zero past the first update;
+# black_after_update is black_between at the default rate: the update of the first batch
+# leaves biases of about the learning rate, so the black batch's activations are those
+# biases alone, about 2^-10 of the first batch's, and the third batch's 2^10 above them.
+DQN_PLANE_SCHEDULES = {
+    "black_first": (False, ("black", "random", "random"), 1e-3),
+    "black_between": (False, ("random", "black", "random"), 0.0),
+    "black_after_update": (False, ("random", "black", "random"), 1e-3),
+    "black_biased": (True, ("black", "random", "random"), 1e-3),
+    "dark_then_saturated": (False, ("dark", "saturated", "dark"), 1e-3),
+    "sparse": (False, ("sparse", "sparse", "sparse"), 1e-3),
+}
+
+
+def plane_sparse_frames(rng, B):
+    """-> o_tm1, o_t (uint8 [B, 84, 84, 4]).  Five 84 x 84 screens per row, each black but
+    for three rectangles (3..10 pixels a side, bytes in 128..255, redrawn per screen as a
+    sprite that moves); o_tm1 stacks screens 0..3 and o_t screens 1..4."""
+    screens = np.zeros((B, 5, 84, 84), np.uint8)
+    for b in range(B):
+        for s in range(5):
+            for _ in range(3):
+                h, w = rng.integers(3, 11, 2)
+                y, x = rng.integers(0, 84 - h), rng.integers(0, 84 - w)
+                screens[b, s, y:y + h, x:x + w] = rng.integers(128, 256, (h, w), dtype=np.uint8)
+    stack = lambda lo: np.ascontiguousarray(np.moveaxis(screens[:, lo:lo + 4], 1, -1))  # noqa: E731
+    return stack(0), stack(1)
+
+
+def _plane_frames(kind, rng, b):
+    shape = b["o_tm1"].shape
+    if kind == "random":
+        return b["o_tm1"], b["o_t"]
+    if kind == "sparse":
+        return plane_sparse_frames(rng, shape[0])
+    if kind == "dark":
+        return (rng.integers(0, 2, shape, dtype=np.uint8), rng.integers(0, 2, shape, dtype=np.uint8))
+    value = {"black": 0, "saturated": 255}[kind]
+    return np.full(shape, value, np.uint8), np.full(shape, value, np.uint8)
+
+
+def dqn_plane_schedule(name):
+    """-> net, params, target, batches (a list of transition batches), learning rate."""
+    from acme_amd.networks import DQNAtariNetwork
+    biased, kinds, lr = DQN_PLANE_SCHEDULES[name]
+    net = DQNAtariNetwork(18)
+    draw = dqn_params if biased else (lambda net_, seed: net_.init(seed))
+    rng = np.random.default_rng(list(name.encode()))
+    batches = []
+    for kind in kinds:
+        b = guard_t._batch(rng, DQN_PLANE_B, 18)
+        b["o_tm1"], b["o_t"] = _plane_frames(kind, rng, b)
+        batches.append(b)
+    return net, draw(net, 1), draw(net, 2), batches, lr
+
+
+# The step guard's window (rescale.h): a rescale leaves a tensor's maximum times its write
+# scale in [2^7, 2^8), and the next step is applied while that product stays in [1, 65520).
+# A g-fold jump of the tensor therefore must apply when [2^7 g, 2^8 g) lies inside
+# [1, 65520) (2^-7 <= g <= 2^7) and must skip when it lies outside whatever the mantissa
+# (g >= 2^9: overflow; g <= 2^-8: underflow).  id -> (log2 g, log2 r0, log2 r1 = log2 g r0,
+# skips, overflow): the innermost power of two that must apply and, with a binade to spare,
+# one that must skip, on either side.
+DQN_WINDOW_JUMPS = {
+    "up7_applies": (7, -8, -1, 0, False),
+    "down6_applies": (-6, -1, -7, 0, False),
+    "up10_skips": (10, -11, -1, 1, True),
+    "down9_skips": (-9, -1, -10, 1, False),
+}
+# The parameter planes share one scale record (the largest parameter, 0.125, at 2^7), so a
+# tensor far below it loses its low plane: test_step_guard_gpu's head scale 1e-4 is kept,
+# and the remaining factor (q must be below 2^-7 of the smaller reward, 2^-18) comes from
+# the hidden layer's weights, an exact power of two 2^-4.  With zero biases q is linear in
+# each: max |q| falls from 0.14 to 8.6e-7.
+DQN_WINDOW_HEAD_SCALE = 1e-4
+DQN_WINDOW_HIDDEN_SCALE = 2.0 ** -4
+
+
+def dqn_window_case(name):
+    """-> net, params, target, first, second, g: two batches on the same frames, actions,
+    discounts (0) and probabilities whose constant rewards are r0 and g r0.  Every |TD| is
+    below 1 (Huber's quadratic zone) and q is negligible beside either reward, so the head dZ
+    and with it the whole input-gradient chain and every weight gradient scale by g, while
+    the forward activations do not move."""
+    from acme_amd.networks import DQNAtariNetwork
+    lg, l0, l1, _, _ = DQN_WINDOW_JUMPS[name]
+    assert l0 + lg == l1
+    net = DQNAtariNetwork(18)
+    params, target = guard_t._head_scaled_params(net, DQN_WINDOW_HEAD_SCALE)
+    for p in (params, target):
+        k = "duelling_q_network/hidden/w"
+        p[k] = p[k] * np.float32(DQN_WINDOW_HIDDEN_SCALE)
+    first = guard_t._batch(np.random.default_rng(20), DQN_PLANE_B, 18, r=2.0 ** l0, d=0.0)
+    second = dict(first, r_t=np.full(DQN_PLANE_B, 2.0 ** l1, np.float32))
+    return net, params, target, first, second, 2.0 ** lg
+
+
+def dqn_uncalibrated_case():
+    """-> net, params, target, batch: one of _batch's random batches for a learner whose
+    scale records are restored at 1 (the scale state of a checkpoint taken before its first
+    step), so its first step is not calibrated.  x3's maximum is below 1: at scale 1 its
+    planes underflow, and that first step, the learner's verdict 0, must be skipped."""
+    from acme_amd.networks import DQNAtariNetwork
+    net = DQNAtariNetwork(18)
+    batch = guard_t._batch(np.random.default_rng(30), DQN_PLANE_B, 18)
+    return net, net.init(1), net.init(2), batch
+
+
+# ------------------------------------------------------------------ recurrent plane inputs
+
+# The recurrent learners' first (calibrating) plane step on black frames under zero biases
+# (the torso's activations and input gradients all zero), then two steps on the modules' own
+# random batches.  IMPALA at 4 x 16 = 64 frames, the fewest that take the plane path; R2D2's
+# Atari network at 3 x 6.
+
+
+def zero_biases(params):
+    return {k: (np.zeros_like(v) if k.endswith("/b") else v) for k, v in params.items()}
+
+
+def impala_plane_black():
+    """-> cfg, B, T, params, batches."""
+    cfg = IM.IMPALAConfig(num_actions=18, torso="atari", lstm_size=256, head_size=64,
+                          entropy_cost=0.01, baseline_cost=0.5)
+    B, T = 4, 16
+    batches = [impala_t._batch(cfg, B, T, 40 + k) for k in range(3)]
+    batches[0]["obs"] = np.zeros_like(batches[0]["obs"])
+    return cfg, B, T, zero_biases(impala_t._params(cfg, 9)), batches
+
+
+def r2d2_plane_black():
+    """-> cfg, B, T, params, target, batches."""
+    cfg = r2d2_t._cfg(torso="atari", num_actions=18, lstm_size=512, head_size=512, obs_dim=0,
+                      burn_in_length=2, n_step=2)
+    B, T = 3, 6
+    batches = [r2d2_t._batch(cfg, B, T, 50 + k) for k in range(3)]
+    batches[0]["obs"] = np.zeros_like(batches[0]["obs"])
+    return (cfg, B, T, zero_biases(r2d2_t._params(cfg, 14)), zero_biases(r2d2_t._params(cfg, 24)),
+            batches)
 
 
 # ------------------------------------------------------------------ IMPALA

@@ -112,10 +112,14 @@ def _relu_masks(cfg, n, params, b):
     return masks
 
 
-def _compare(cfg, n, params, b, frob_only=()):
+def _compare(cfg, n, params, b, frob_only=(), moments=None):
+    """The step just taken from `params` against the oracle.  moments: (m, v, updates applied
+    before the step), the learner's own pre-step Adam state, for a step that is not the
+    first update (teacher-forced, e.g. after a skipped step); default: a fresh learner's."""
     z = {k: np.zeros_like(v) for k, v in params.items()}
+    m0, v0, t0 = moments if moments is not None else (z, dict(z), 0)
     masks = _relu_masks(cfg, n, params, b)
-    ref, raw, st = O.impala_step(cfg, dict(params=params, m=z, v=dict(z), num_steps=0), b,
+    ref, raw, st = O.impala_step(cfg, dict(params=params, m=m0, v=v0, num_steps=t0), b,
                                  masks=masks)
     B, T = b["action"].shape
     A = cfg.num_actions

@@ -146,11 +146,76 @@ def _relu_masks(cfg, n, params, b):
     return masks
 
 
+def _check_step(cfg, n, state, b, copies, errors_rtol=1e-4, k=0):
+    """The step just taken on batch b against the oracle, teacher-forced from `state`: the
+    learner's own pre-step {params, target, m, v, num_steps} (num_steps: the updates applied
+    before this one, Adam's t - 1).  copies: whether this step's target copy was due.
+    Returns the learner's state after the step, in the same form."""
+    from oracle.dqn_oracle import adam_update
+    B, T = b["action"].shape
+    BI, A = cfg.burn_in_length, cfg.num_actions
+    L = T - BI
+    masks = _relu_masks(cfg, n, state["params"], b)
+    ref, _ = O.loss_and_grads(cfg, state["params"], state["target"], b, masks=masks)
+    # Network forwards against the f64 restatement.
+    q_ref = np.swapaxes(ref["q"][:, BI:], 0, 1).reshape(L * B, A)
+    tq_ref = np.swapaxes(ref["target_q"][:, BI:], 0, 1).reshape(L * B, A)
+    q_k = n.debug_buffer("q")[:L * B * A]
+    tq_k = n.debug_buffer("target_q")[:L * B * A]
+    _close(q_k, q_ref, name=f"q step {k}")
+    _close(tq_k, tq_ref, name=f"target_q step {k}")
+    # The loss kernel bit for bit against TF's f32 loss arithmetic on the kernel's own q
+    # values (teacher-forced): errors, priorities, d loss / d q[a].
+    err_tf, _ = O.transformed_loss(cfg, q_k.reshape(L, B, A), tq_k.reshape(L, B, A), b)
+    np.testing.assert_array_equal(n.errors.cpu().numpy(), err_tf, err_msg=f"errors {k}")
+    np.testing.assert_array_equal(n.priorities.cpu().numpy(),
+                                  O.compute_priority(err_tf, cfg.max_priority_weight),
+                                  err_msg=f"priorities {k}")
+    w32 = O.importance_weights(b["probabilities"], cfg.max_replay_size,
+                               cfg.importance_sampling_exponent)
+    g_tf = (w32[None, :] * err_tf) * np.float32(1.0 / B)
+    g_k = n.debug_buffer("g")[:L * B].reshape(L, B)
+    np.testing.assert_array_equal(g_k[:L - 1], g_tf, err_msg=f"g {k}")
+    assert not g_k[L - 1].any()
+    # End to end against the f64 networks: the f32 value transforms resolve ~6e-5.
+    _close(n.errors.cpu().numpy(), ref["errors"], rtol=errors_rtol, floor=0,
+           name=f"errors {k}")
+    np.testing.assert_allclose(n.errors.cpu().numpy(), ref["errors"], atol=2.5e-4)
+    np.testing.assert_allclose(n.loss.item(), ref["loss"], rtol=2e-4, err_msg=f"loss {k}")
+    # Gradients: the f64 backward from the kernel's d loss / d q (teacher-forced).
+    _, cache = O.forward(cfg, state["params"], b, np.float64)
+    act = b["action"]
+    dq = np.zeros((B, T, A))
+    for t in range(L - 1):
+        dq[np.arange(B), BI + t, act[:, BI + t]] += g_k[t]
+    grads = O.backward(cfg, state["params"], b, cache, dq.reshape(B * T, A), np.float64,
+                       masks)
+    _check_grads(n, grads)
+    got_p = n.get_params("params")
+    new_p = {}
+    for name in state["params"]:
+        new_p[name] = adam_update(state["params"][name], grads[name], state["m"][name],
+                                  state["v"][name], state["num_steps"] + 1, cfg.learning_rate,
+                                  eps=cfg.adam_epsilon)[0]
+    _check_params(got_p, new_p, cfg.learning_rate)
+    # The target copy: identical to the updated parameters on copy steps, else kept.
+    got_t = n.get_params("target")
+    for name in got_t:
+        want = got_p[name] if copies else state["target"][name]
+        np.testing.assert_array_equal(got_t[name], want.reshape(got_t[name].shape), err_msg=name)
+    # Teacher forcing: the next step starts from the kernel's own state.
+    shp = {kk: v.shape for kk, v in state["params"].items()}
+    return dict(params={kk: got_p[kk].reshape(shp[kk]) for kk in shp},
+                target={kk: got_t[kk].reshape(shp[kk]) for kk in shp},
+                m={kk: n.get_params("m")[kk].reshape(shp[kk]) for kk in shp},
+                v={kk: n.get_params("v")[kk].reshape(shp[kk]) for kk in shp},
+                num_steps=state["num_steps"] + 1)
+
+
 def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False, errors_rtol=1e-4):
     """errors_rtol: the relative bar of the end-to-end errors (1e-4 unless a caller derives
     another from the float32 oracle's own error at its shape)."""
     from acme_amd._lib import lib
-    from oracle.dqn_oracle import adam_update
     if f32_engine:
         lib().acme_tune_set(b"R2P3", 1)  # read at the learner's creation
     try:
@@ -162,69 +227,11 @@ def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False, errors_rtol=1e-4):
     n.set_params(p0, t0)
     z = {k: np.zeros_like(v) for k, v in p0.items()}
     state = dict(params=p0, target=t0, m=z, v=dict(z), num_steps=0)
-    BI, A = cfg.burn_in_length, cfg.num_actions
-    L = T - BI
-    prev_t = None
     for k in range(steps):
         b = _batch(cfg, B, T, 100 * seed + k)
         _run(n, b)
-        masks = _relu_masks(cfg, n, state["params"], b)
-        ref, _ = O.loss_and_grads(cfg, state["params"], state["target"], b, masks=masks)
-        # Network forwards against the f64 restatement.
-        q_ref = np.swapaxes(ref["q"][:, BI:], 0, 1).reshape(L * B, A)
-        tq_ref = np.swapaxes(ref["target_q"][:, BI:], 0, 1).reshape(L * B, A)
-        q_k = n.debug_buffer("q")[:L * B * A]
-        tq_k = n.debug_buffer("target_q")[:L * B * A]
-        _close(q_k, q_ref, name=f"q step {k}")
-        _close(tq_k, tq_ref, name=f"target_q step {k}")
-        # The loss kernel bit for bit against TF's f32 loss arithmetic on the kernel's own q
-        # values (teacher-forced): errors, priorities, d loss / d q[a].
-        err_tf, _ = O.transformed_loss(cfg, q_k.reshape(L, B, A), tq_k.reshape(L, B, A), b)
-        np.testing.assert_array_equal(n.errors.cpu().numpy(), err_tf, err_msg=f"errors {k}")
-        np.testing.assert_array_equal(n.priorities.cpu().numpy(),
-                                      O.compute_priority(err_tf, cfg.max_priority_weight),
-                                      err_msg=f"priorities {k}")
-        w32 = O.importance_weights(b["probabilities"], cfg.max_replay_size,
-                                   cfg.importance_sampling_exponent)
-        g_tf = (w32[None, :] * err_tf) * np.float32(1.0 / B)
-        g_k = n.debug_buffer("g")[:L * B].reshape(L, B)
-        np.testing.assert_array_equal(g_k[:L - 1], g_tf, err_msg=f"g {k}")
-        assert not g_k[L - 1].any()
-        # End to end against the f64 networks: the f32 value transforms resolve ~6e-5.
-        _close(n.errors.cpu().numpy(), ref["errors"], rtol=errors_rtol, floor=0,
-               name=f"errors {k}")
-        np.testing.assert_allclose(n.errors.cpu().numpy(), ref["errors"], atol=2.5e-4)
-        np.testing.assert_allclose(n.loss.item(), ref["loss"], rtol=2e-4, err_msg=f"loss {k}")
-        # Gradients: the f64 backward from the kernel's d loss / d q (teacher-forced).
-        _, cache = O.forward(cfg, state["params"], b, np.float64)
-        act = b["action"]
-        dq = np.zeros((B, T, A))
-        for t in range(L - 1):
-            dq[np.arange(B), BI + t, act[:, BI + t]] += g_k[t]
-        grads = O.backward(cfg, state["params"], b, cache, dq.reshape(B * T, A), np.float64,
-                           masks)
-        _check_grads(n, grads)
-        got_p = n.get_params("params")
-        new_p = {}
-        for name in p0:
-            new_p[name] = adam_update(state["params"][name], grads[name], state["m"][name],
-                                      state["v"][name], k + 1, cfg.learning_rate,
-                                      eps=cfg.adam_epsilon)[0]
-        _check_params(got_p, new_p, cfg.learning_rate)
-        # The target copy: identical to the updated parameters on copy steps, else kept.
-        got_t = n.get_params("target")
-        for name in got_t:
-            want = got_p[name] if k % cfg.target_update_period == 0 else prev_t[name]
-            np.testing.assert_array_equal(got_t[name], want, err_msg=name)
-        prev_t = got_t
+        state = _check_step(cfg, n, state, b, k % cfg.target_update_period == 0, errors_rtol, k)
         assert n.num_steps == k + 1
-        # Teacher forcing: the next step starts from the kernel's own state.
-        shp = {kk: v.shape for kk, v in p0.items()}
-        state = dict(params={kk: got_p[kk].reshape(shp[kk]) for kk in p0},
-                     target={kk: got_t[kk].reshape(shp[kk]) for kk in p0},
-                     m={kk: n.get_params("m")[kk].reshape(shp[kk]) for kk in p0},
-                     v={kk: n.get_params("v")[kk].reshape(shp[kk]) for kk in p0},
-                     num_steps=k + 1)
     g = n.guard_state()
     assert g["skipped"] == 0 and g["applied"] == steps, g
     return n
