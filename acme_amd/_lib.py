@@ -253,6 +253,7 @@ _SIGS = {
     "acme_dqn_guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_dqn_verdict_timeouts": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_dqn_update_rider_launches": (c_i64, [c_vp]),
+    "acme_dqn_fused_x2_launches": (c_i64, [c_vp]),
     "acme_dqn_set_applied_steps": (c_i32, [c_vp, c_i64]),
     "acme_dqn_skip_word": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
     "acme_dqn_set_reissue": (c_i32, [c_vp, c_i32]),

@@ -184,6 +184,11 @@ struct acme_dqn : PlaneGuard {
   // (ACME_V_UPDATE_RIDER=0 at creation: the separate launch; the same bits).
   bool update_rider = true;
   int64_t rider_launches = 0;
+  // The step's forwards with conv3 inside conv2's launch, so that x2 stays in LDS wherever the
+  // backward does not read it (torso.h keep_x2; ACME_V_FUSE_X2 at creation: 0 the separate
+  // conv3_fwd launches, 1 the target forward fused, 2 the online forward, 3 both; the same bits).
+  int fuse_x2 = torso::kFuseX2Default;
+  int64_t fused_x2_launches = 0;
   // conv1 reads the batch's uint8 frames (unless the batch carries the f16 copy, obs_f16, or
   // the frames are not 16-byte aligned: then the step makes the f16 copy, the round-4 path)
   bool frames_u8 = true;
@@ -358,9 +363,10 @@ int fc_fwd_gemm(const acme_dqn* l, const char* name, P3DenseFwd p, int splits,
 int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso::Frames& frames,
                       int rows, const torso::Plane& x1, const torso::Plane& x2,
                       const torso::Plane& x3, float* hid, float* q, hipStream_t st,
-                      float* slab = nullptr, int keep_x1 = -1, bool defer_head = false) {
+                      float* slab = nullptr, int keep_x1 = -1, bool defer_head = false,
+                      int keep_x2 = -1) {
   if (!slab) slab = l->slab;
-  int rc = torso::forward_p3(torso_pweights(l, prm, wpl), frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1, l->bk32);
+  int rc = torso::forward_p3(torso_pweights(l, prm, wpl), frames, rows, torso::PActs{x1, x2, x3}, st, keep_x1, l->bk32, keep_x2);
   if (rc != ACME_OK) return rc;
   {
     P3DenseFwd p;
@@ -753,6 +759,7 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
   l->single_role = tune_variant("WSN") == 1;
   l->bk32 = tune_variant("BK32") == 1;
   l->update_rider = tune_variant("UPDATE_RIDER", kUpdateRiderDefault) != 0;
+  l->fuse_x2 = tune_variant("FUSE_X2", torso::kFuseX2Default) & 3;
   l->stamps_on = tune_variant("STAMPS") == 1;
   const int A = cfg->num_actions;
   const int B = cfg->max_batch;
@@ -983,6 +990,7 @@ int acme_dqn_verdict_timeouts(acme_dqn* l, int64_t* out) {
 }
 
 int64_t acme_dqn_update_rider_launches(const acme_dqn* l) { return l ? l->rider_launches : 0; }
+int64_t acme_dqn_fused_x2_launches(const acme_dqn* l) { return l ? l->fused_x2_launches : 0; }
 
 int acme_dqn_set_reissue(acme_dqn* l, int32_t enable) {
   ACME_CHECK_ARG(l, "null learner");
@@ -1306,13 +1314,16 @@ static int forward_backward_stage(acme_dqn* l, const StepPlan& plan,
     // windows 0.5208 -> 0.5181 ms, three alternating runs each).  Either order gives the
     // same bits.
     const bool online_first = side != nullptr;
+    // x2 in HBM: the online o_tm1 rows' (conv3's backward reads it), none of the target's.
+    const int keep_on = (l->fuse_x2 & 2) ? B : -1, keep_tg = (l->fuse_x2 & 1) ? 0 : -1;
+    l->fused_x2_launches += (keep_on >= 0) + (keep_tg >= 0);
     if (online_first &&
         (rc = nature_forward_p3(l, l->params, l->wpl, fwd_frames, 2 * B, l->x1p, l->x2p, l->x3p,
-                                l->hid, l->q_on, st, nullptr, B, true)) != ACME_OK)
+                                l->hid, l->q_on, st, nullptr, B, true, keep_on)) != ACME_OK)
       return rc;
     if ((rc = nature_forward_p3(l, l->target, l->tpl, fwd_frames.rows_from(B), B,
                                 l->t1p, l->t2p, l->t3p, l->thid, l->q_tg, tst,
-                                side ? l->tslab : l->slab, 0)) != ACME_OK)
+                                side ? l->tslab : l->slab, 0, false, keep_tg)) != ACME_OK)
       return rc;
     {  // the target records' scales, and their flag into the step's slot t[seq & 1]
       RescaleGuard rg;
@@ -1326,7 +1337,7 @@ static int forward_backward_stage(acme_dqn* l, const StepPlan& plan,
     if (side) ACME_HIP_TRY(hipEventRecord(l->ev[1], side));
     if (!online_first &&
         (rc = nature_forward_p3(l, l->params, l->wpl, fwd_frames, 2 * B, l->x1p, l->x2p, l->x3p,
-                                l->hid, l->q_on, st, nullptr, B, true)) != ACME_OK)
+                                l->hid, l->q_on, st, nullptr, B, true, keep_on)) != ACME_OK)
       return rc;
     if (side) ACME_HIP_TRY(hipStreamWaitEvent(st, l->ev[1], 0));
   } else if (nature) {

@@ -246,5 +246,84 @@ struct ImgGeomSub {
   }
 };
 
+// ---- Fused forwards (gemm_p3c12.h): a convolution's epilogue writes its output straight
+// into the next layer's LDS image, and the placement of every region in every phase.
+
+// Byte offset, within a plane of the block's ImgGeom<Gto, false> images, of output channels
+// n .. n + 7 (n a multiple of 8) of output pixel pp of the block's frame f of a forward
+// convolution over Gfrom: the unit ImgGeom<Gto, false>::fill places there from HBM.
+template <class Gfrom, class Gto>
+ACME_GEOM_FN int sink_at(int f, int pp, int n) {
+  static_assert(Gfrom::OH == Gto::IH && Gfrom::OW == Gto::IW && Gfrom::CO == Gto::CI,
+                "the output is the next layer's input");
+  const int oh = pp / Gfrom::OW, ow = pp - oh * Gfrom::OW;
+  return ImgGeom<Gto, false>::at(f, oh, ow, n / 8);
+}
+
+// A weight ring of two stages of ng 32-k groups of a [32][bn] two-plane f16 panel, and the
+// epilogue's row-major f32 staging of `waves` 32 x tn tiles (gemm_p3.h P3Core::EPI_BYTES).
+constexpr int p3_ring_bytes(int bn, int ng) { return 2 * ng * (2 * bn * 32 * 2); }
+constexpr int p3_epi_bytes(int waves, int tn) { return waves * 32 * (tn + 4) * 4; }
+
+struct LdsSpan {
+  int lo, hi;  // bytes [lo, hi)
+};
+constexpr bool lds_disjoint(LdsSpan a, LdsSpan b) { return a.hi <= b.lo || b.hi <= a.lo; }
+constexpr int lds_max(int a, int b) { return a > b ? a : b; }
+
+// conv1 -> conv2 (-> conv3), one frame per block, 8 waves (gemm_p3c12_kernel).  Region 0
+// holds the frame image, then conv2's and conv3's weight rings and every epilogue's
+// staging; region 1 the two x1 planes (conv1's ring in the first until conv1's epilogue
+// writes x1), then, once conv2's k loop has read x1 for the last time, the two x2 planes.
+template <class G1, class G2, class G3, int NG1, int NG2, int NG3>
+struct C123Place {
+  using I1 = ImgGeomPairs<G1>;
+  using I2 = ImgGeom<G2, false>;
+  using I3 = ImgGeom<G3, false>;
+  static constexpr int NP = 2, WAVES = 8;
+  static constexpr int ZERO1 = img_zero_base(I1::IMG), FRAME = ZERO1 + kImgZeroBytes;
+  static constexpr int ZERO2 = img_zero_base(I2::IMG), PLANE2 = ZERO2 + kImgZeroBytes;
+  static constexpr int ZERO3 = img_zero_base(I3::IMG), PLANE3 = ZERO3 + kImgZeroBytes;
+  static constexpr int X1 = FRAME, X2 = FRAME;
+  static constexpr int LDS = X1 + NP * PLANE2;
+  static constexpr LdsSpan frame{0, FRAME}, x1{X1, X1 + NP * PLANE2}, x2{X2, X2 + NP * PLANE3};
+  static constexpr LdsSpan ring1{X1, X1 + p3_ring_bytes(32, NG1)};
+  static constexpr LdsSpan ring2{0, p3_ring_bytes(64, NG2)}, ring3{0, p3_ring_bytes(64, NG3)};
+  static constexpr LdsSpan epi1{0, p3_epi_bytes(WAVES, 32)}, epi23{0, p3_epi_bytes(WAVES, 32)};
+  // Phases: conv1's k loop {frame, ring1}; its epilogue {epi1, x1}; conv2's k loop
+  // {ring2, x1}; its epilogue {epi23, x2}; conv3's k loop {ring3, x2}; its epilogue {epi23}.
+  static constexpr bool ok() {
+    return lds_disjoint(frame, ring1) && ring1.hi <= X1 + I2::IMG && lds_disjoint(epi1, x1) &&
+           lds_disjoint(ring2, x1) && lds_disjoint(epi23, x2) && lds_disjoint(ring3, x2) &&
+           x2.hi <= x1.hi && epi1.hi <= FRAME && epi23.hi <= FRAME && ring2.hi <= FRAME &&
+           ring3.hi <= FRAME && LDS <= 160 * 1024;
+  }
+};
+
+// conv2 -> conv3, two frames per block, 16 waves (gemm_p3c23_kernel).  conv2's k loop reads
+// the x1 images (two planes of two frames) beside its weight ring; then x1 is dead: conv2's
+// epilogue stages through the bottom and writes the x2 images above the staging, conv3's
+// ring and its epilogue's staging reuse the bottom.
+template <class G2, class G3, int NG2, int NG3>
+struct C23Place {
+  using I2 = ImgGeom<G2, false>;
+  using I3 = ImgGeom<G3, false>;
+  static constexpr int NP = 2, FPB = 2, WAVES = 16;
+  static constexpr int ZERO2 = img_zero_base(FPB * I2::IMG), PLANE2 = ZERO2 + kImgZeroBytes;
+  static constexpr int ZERO3 = img_zero_base(FPB * I3::IMG), PLANE3 = ZERO3 + kImgZeroBytes;
+  static constexpr int RING2 = NP * PLANE2;
+  static constexpr int EPI = p3_epi_bytes(WAVES, 32);
+  static constexpr int X2 = img_zero_base(lds_max(EPI, p3_ring_bytes(64, NG3)));
+  static constexpr LdsSpan x1{0, NP * PLANE2}, ring2{RING2, RING2 + p3_ring_bytes(64, NG2)};
+  static constexpr LdsSpan epi{0, EPI}, x2{X2, X2 + NP * PLANE3}, ring3{0, p3_ring_bytes(64, NG3)};
+  static constexpr int LDS = lds_max(ring2.hi, x2.hi);
+  // Phases: conv2's k loop {x1, ring2}; its epilogue {epi, x2}; conv3's k loop {ring3, x2};
+  // its epilogue {epi}.
+  static constexpr bool ok() {
+    return lds_disjoint(x1, ring2) && lds_disjoint(epi, x2) && lds_disjoint(ring3, x2) &&
+           LDS <= 160 * 1024;
+  }
+};
+
 }  // namespace gemm
 }  // namespace acme

@@ -91,8 +91,14 @@ struct Frames {
 // keep_x1 == 0) x1 only lives in LDS.
 // bk32: the image-resident kernels at a stage depth of 32 k instead of each kernel's own
 // (the same bits; tests, ACME_V_BK32=1 at the learner's creation).
+// keep_x2: frames [0, keep_x2) get their conv2 output x2 in HBM (the backward reads it);
+// -1: all, from the separate conv3_fwd launch.  With keep_x2 >= 0 conv3 runs inside conv2's
+// launch (gemm_p3c12.h: conv1 -> conv2 -> conv3 when keep_x1 == 0, else conv2 -> conv3 over
+// an even number of frames) and the other frames' x2 only lives in LDS; the same bits.
 int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a,
-               hipStream_t st, int keep_x1 = -1, bool bk32 = false);
+               hipStream_t st, int keep_x1 = -1, bool bk32 = false, int keep_x2 = -1);
+// The DQN step's ACME_V_FUSE_X2 when unset (bit 0: the target forward, bit 1: the online).
+constexpr int kFuseX2Default = 3;
 // Optional second stream for the weight gradients: conv3 / conv2 weight gradients run on
 // `side` (with their own split-K slab) beside the input gradients on the main stream;
 // events e[0..2] are scratch (hipEventDisableTiming).  side == nullptr: one stream.

@@ -176,9 +176,11 @@ int conv1_fwd_p3(const PWeights& w, const Frames& frames, int rows, const Planes
 }
 
 // The fused conv1 -> conv2 forward (gemm_p3c12.h) over frames [nsep, rows).
+// keep_x2 >= 0: conv3 fused behind it (conv1 -> conv2 -> conv3 in one launch), x2 in HBM for
+// frames below keep_x2 only.
 template <bool U8>
 int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, const PActs& a,
-                  hipStream_t st, bool bk32) {
+                  hipStream_t st, bool bk32, int keep_x2) {
   const int nf = rows - nsep;
   const Frames fr = frames.rows_from(nsep);
   if (U8 && fr.split < nf)
@@ -195,9 +197,23 @@ int conv12_fwd_p3(const PWeights& w, const Frames& frames, int rows, int nsep, c
   p2.bias = w.b2;
   p2.y = Planes{a.x2.p + (int64_t)nsep * kFlat, a.x2.stride, a.x2.sc};
   const double fl = 2.0 * p1.M * p1.N * (double)p1.K + 2.0 * p2.M * p2.N * (double)p2.K;
-  ACME_PROF_PEAK("conv12_fwd", st, fl, 0.0, gemm::p3_peak_tflops<decltype(p2)>());
-  hipError_t e = bk32 ? gemm::launch_gemm_p3c12<32, 32>(p1, p2, nf, 0, st)
-                      : gemm::launch_gemm_p3c12<kBkFused1, kBkFused2>(p1, p2, nf, 0, st);
+  hipError_t e;
+  if (keep_x2 >= 0) {
+    P3ConvFwd<G3, gemm::kPlanes> p3;
+    p3.M = nf * G3::OPIX; p3.N = G3::CO; p3.K = G3::K; p3.k_chunk = G3::K;
+    p3.a_src = SRC(a.x2, (int64_t)rows * kFlat); p3.b_src = SRC(w.w3, G3::K * G3::CO);
+    p3.bias = w.b3;
+    p3.y = Planes{a.x3.p + (int64_t)nsep * kFlat, a.x3.stride, a.x3.sc};
+    const int keep = std::max(0, std::min(keep_x2, rows) - nsep);
+    ACME_PROF_PEAK("conv123_fwd", st, fl + 2.0 * p3.M * p3.N * (double)p3.K, 0.0,
+                   gemm::p3_peak_tflops<decltype(p2)>());
+    e = bk32 ? gemm::launch_gemm_p3c123<32, 32, 32>(p1, p2, p3, nf, 0, keep, st)
+             : gemm::launch_gemm_p3c123<kBkFused1, kBkFused2, kBkConv3>(p1, p2, p3, nf, 0, keep, st);
+  } else {
+    ACME_PROF_PEAK("conv12_fwd", st, fl, 0.0, gemm::p3_peak_tflops<decltype(p2)>());
+    e = bk32 ? gemm::launch_gemm_p3c12<32, 32>(p1, p2, nf, 0, st)
+             : gemm::launch_gemm_p3c12<kBkFused1, kBkFused2>(p1, p2, nf, 0, st);
+  }
   if (e != hipSuccess) return (set_error("gemm launch failed: %s", hipGetErrorString(e)), ACME_ERR_HIP);
   return ACME_OK;
 }
@@ -254,22 +270,45 @@ int64_t wgrad_slab_floats_p3() {
 }
 
 int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a,
-               hipStream_t st, int keep_x1, bool bk32) {
+               hipStream_t st, int keep_x1, bool bk32, int keep_x2) {
   // Frames [0, nsep) run conv1 then conv2 with x1 in HBM (the backward reads it); frames
   // [nsep, rows) the fused conv1 -> conv2 kernel (gemm_p3c12.h), whose x1 stays in LDS.
   // The target forward (keep_x1 == 0, on the side stream) is fused throughout: 0.716 ->
   // 0.713 ms per step when it was introduced.  The online forward runs unfused: fusing its
   // o_t rows (x1 kept for the o_tm1 rows only) measured 0.545 -> 0.603 ms per step with
   // the f16 planes (the fused kernel's one block per CU beside the other stream).
+  // keep_x2 >= 0: conv3 runs behind conv2 in conv2's launch (gemm_p3c12.h: conv1 -> conv2 ->
+  // conv3 for the fused frames, conv2 -> conv3 for the others), and x2 reaches HBM for frames
+  // below keep_x2 only; the same bits as the separate conv3_fwd.
   const int nsep = keep_x1 == 0 ? 0 : rows;
+  const bool fuse3 = keep_x2 >= 0;
   int rc;
   if (nsep < rows &&
-      (rc = frames.u8 ? conv12_fwd_p3<true>(w, frames, rows, nsep, a, st, bk32)
-                      : conv12_fwd_p3<false>(w, frames, rows, nsep, a, st, bk32)) != ACME_OK)
+      (rc = frames.u8 ? conv12_fwd_p3<true>(w, frames, rows, nsep, a, st, bk32, keep_x2)
+                      : conv12_fwd_p3<false>(w, frames, rows, nsep, a, st, bk32, keep_x2)) != ACME_OK)
     return rc;
   if (nsep > 0 && (rc = frames.u8 ? conv1_fwd_p3<true>(w, frames, nsep, PP(a.x1), st, bk32, g_stamps_conv[0])
                                   : conv1_fwd_p3<false>(w, frames, nsep, PP(a.x1), st, bk32, g_stamps_conv[0])) != ACME_OK)
     return rc;
+  if (fuse3 && nsep > 0) {
+    // conv2 -> conv3 over the two frames of a block (gemm_p3c12.h gemm_p3c23_kernel).
+    if (rows % 2 != 0)
+      return (set_error("the fused conv2 -> conv3 forward takes an even number of frames"),
+              ACME_ERR_INVALID);
+    P3ConvFwd<G2, gemm::kPlanes> p2;
+    p2.M = rows * G2::OPIX; p2.N = G2::CO; p2.K = G2::K; p2.k_chunk = G2::K;
+    p2.a_src = SRC(a.x1, (int64_t)rows * kX1); p2.b_src = SRC(w.w2, G2::K * G2::CO);
+    p2.bias = w.b2; p2.y = PP(a.x2);
+    P3ConvFwd<G3, gemm::kPlanes> p3;
+    p3.M = rows * G3::OPIX; p3.N = G3::CO; p3.K = G3::K; p3.k_chunk = G3::K;
+    p3.a_src = SRC(a.x2, (int64_t)rows * kFlat); p3.b_src = SRC(w.w3, G3::K * G3::CO);
+    p3.bias = w.b3; p3.y = PP(a.x3);
+    const double fl = 2.0 * p2.M * p2.N * (double)p2.K + 2.0 * p3.M * p3.N * (double)p3.K;
+    ACME_LAUNCH_GEMM("conv23_fwd", fl, gemm::p3_peak_tflops<decltype(p2)>(),
+                     (bk32 ? gemm::launch_gemm_p3c23<32, 32>(p2, p3, rows, keep_x2, st)
+                           : gemm::launch_gemm_p3c23<kBkConv2, kBkConv3>(p2, p3, rows, keep_x2, st)));
+    return ACME_OK;
+  }
   if (nsep > 0) {
     P3ConvFwd<G2, gemm::kPlanes> p;
     p.M = nsep * G2::OPIX; p.N = G2::CO; p.K = G2::K; p.k_chunk = G2::K;
@@ -282,7 +321,7 @@ int forward_p3(const PWeights& w, const Frames& frames, int rows, const PActs& a
     // runs each, one box; one frame per block: 0.571).
     P3I_GEMM_BK("conv2_fwd", I2F, 2, 64, 8, 2, 1, kBkConv2, bk32, p, nsep);
   }
-  {
+  if (!fuse3) {
     P3ConvFwd<G3, gemm::kPlanes> p;
     p.M = rows * G3::OPIX; p.N = G3::CO; p.K = G3::K; p.k_chunk = G3::K;
     p.a_src = SRC(a.x2, (int64_t)rows * kFlat); p.b_src = SRC(w.w3, G3::K * G3::CO);

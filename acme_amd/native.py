@@ -584,6 +584,10 @@ class NativeDQN(_PlaneState, _NativeLearner):
         """Steps whose priority write-back rode conv1's weight-gradient launch."""
         return int(lib().acme_dqn_update_rider_launches(self._h))
 
+    def fused_x2_launches(self) -> int:
+        """Forwards of the step that ran conv3 inside conv2's launch (x2 kept in LDS)."""
+        return int(lib().acme_dqn_fused_x2_launches(self._h))
+
     @property
     def applied_steps(self) -> int:
         """Updates applied (Adam's t after the last step); synchronises."""

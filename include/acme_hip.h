@@ -404,6 +404,10 @@ int64_t acme_dqn_verdicts_issued(const acme_dqn* l);
  * conv1's weight-gradient launch instead of a launch of its own (the fused plane step with
  * at most 512 updates, unless the learner was created with ACME_V_UPDATE_RIDER=0). */
 int64_t acme_dqn_update_rider_launches(const acme_dqn* l);
+/* Forwards of the plane step that ran conv3 inside conv2's launch, so that x2 stayed in LDS
+ * where the backward does not read it (two per step by default: the online and the target
+ * forward; ACME_V_FUSE_X2 at creation: 0 none, 1 the target's, 2 the online's, 3 both). */
+int64_t acme_dqn_fused_x2_launches(const acme_dqn* l);
 int acme_dqn_step_verdict(const acme_dqn* l, int64_t seq, int32_t* state);
 /* The plane scales (powers of two) as learner state for checkpoints: acme_dqn_scale_state
  * writes *count floats to out (when out is non-NULL and capacity suffices);

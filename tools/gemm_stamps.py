@@ -29,7 +29,7 @@ def main():
     for _ in range(5):
         d.step(o, a, r, dd, o2, pr)
     torch.cuda.synchronize()
-    allst = d.debug_buffer("gemm_stamps").view(np.int64).reshape(4, 4096, 8)
+    allst = d.debug_buffer("gemm_stamps").view(np.int64).reshape(-1, 4096, 8)[:4]  # slot 4: the write-back
     for name, st in zip(("fc_fwd (online)", "conv1_fwd", "conv2_fwd", "conv3_fwd (online)"),
                         allst):
         st = st[st[:, 0] != 0]

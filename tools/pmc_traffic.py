@@ -69,6 +69,8 @@ SECTIONS = [
     (r"head_dz_planes_kernel", "head_dz"),
     (r"dqn_loss_head_dz_kernel", "loss_head_dz"),
     (r"dqn_head_loss_dz_kernel", "head_loss_dz"),
+    (r"gemm_p3c23_kernel", "conv23_fwd"),
+    (r"gemm_p3c12_kernel<.*Geom<11,", "conv123_fwd"),  # with conv3 as its third geometry
     (r"gemm_p3c12_kernel", "conv12_fwd"),
     (r"gemm_\w+_kernel<128, 128, 2, 2,.*DenseFwd<true", "fc_fwd"),
     (r"ConvFwd<acme::conv::Geom<84,", "conv1_fwd"),
