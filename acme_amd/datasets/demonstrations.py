@@ -1,0 +1,250 @@
+"""Demonstrations mixed into replay batches — the dataset side of DQfD
+(acme/agents/tf/dqfd/agent.py:111-122).
+
+The reference maps each demonstration episode to one n-step transition on a tf.data thread
+(_n_step_transition_from_episode, agent.py:160-217) and interleaves the mapped dataset with
+the Reverb stream, element by element, with sample_from_datasets([replay, demos],
+[1 - ratio, ratio]).  Here the episodes are device arrays (`DemonstrationStore`) and the mix
+is one kernel on the dataset's stream (acme_demo_mix, csrc/demos.hip): the table draws and
+gathers its full batch, then each row independently becomes a demonstration with probability
+`demonstration_ratio` and is overwritten with an n-step transition of a uniformly drawn
+episode and first step.  The choice and the draws of row j of draw `step` are one Philox
+call keyed by the mix's own seed, so a batch is a function of (table state, table seed, mix
+seed, step) whatever the prefetch depth.
+
+A demonstration row reports probability 1, table_size 1 and priority 1 like the
+reference's, and the key DEMONSTRATION_KEY = 2**64 - 2 where the reference has 0: key 0 is
+this table's first item, and all-ones marks an empty slot, so either would let the learner's
+priority write-back touch the table; 2**64 - 2 equals no stored key and the write-back
+drops it as stale.
+"""
+
+from __future__ import annotations
+
+import os
+from typing import Iterable, Sequence
+
+import numpy as np
+import torch
+
+from acme_amd import replay
+from acme_amd.datasets.reverb import ReplayDataset, _data_parallel, _TableIterator, _Unbatched
+
+DEMONSTRATION_KEY = 0xFFFFFFFFFFFFFFFE
+
+
+def _transition_fields(table_or_signature):
+    """The flattened field layout of a transition table, its signature, or a field list."""
+    x = table_or_signature
+    if isinstance(x, (replay.FrameTable, replay.QueueTable)):
+        raise ValueError(f"demonstrations are mixed into transition tables, not a "
+                         f"{type(x).__name__}")
+    if isinstance(x, replay.Table):
+        fields = x.fields
+        if fields is None:
+            raise ValueError("the table has no item layout yet: construct it with a signature")
+    elif isinstance(x, (list, tuple)) and x and all(isinstance(f, replay._Field) for f in x):  # noqa: SLF001
+        fields = list(x)
+    else:
+        fields = replay._layout_from_signature(x)  # noqa: SLF001
+    if len(fields) < 5:
+        raise ValueError("a transition layout (o_tm1, a_tm1, r_t, d_t, o_t) has five fields, "
+                         f"got {len(fields)}")
+    o, _, r, d, o2 = fields[:5]
+    if (o.shape, o.dtype, o.row_bytes) != (o2.shape, o2.dtype, o2.row_bytes):
+        raise ValueError("fields 0 and 4 (the two observations) differ")
+    for f in (r, d):
+        if f.dtype != np.float32 or f.shape != () or f.row_bytes != 4:
+            raise ValueError("fields 2 and 3 (reward and discount) must be float32 scalars")
+    return fields
+
+
+class DemonstrationStore:
+    """Demonstration episodes held on the device for `mix_demonstrations`.
+
+    episodes: an iterable of (observations [L, ...], actions [L, ...], rewards [L],
+    discounts [L]) arrays, one tuple per episode, as DemonstrationRecorder.make_dataset()
+    returns them.  As in the reference the first reward and discount and the last action of
+    an episode are never used.  table_or_signature: the transition table the store will be
+    mixed with, or its signature (NStepTransitionAdder.signature(spec)): observations and
+    actions are converted to, and must have the shapes of, its fields 0 and 1.  Every episode
+    needs at least 3 steps (the reference draws the first step from [0, L - 2)).
+
+    The rows go to the device when the store is first mixed (or at `upload()`); nothing
+    here needs a GPU before that."""
+
+    def __init__(self, episodes: Iterable[Sequence[np.ndarray]], table_or_signature,
+                 device=None):
+        from acme_amd.native import NativeDemoStore
+        fields = _transition_fields(table_or_signature)
+        fo, fa = fields[0], fields[1]
+        self.obs_row_bytes, self.action_row_bytes = fo.row_bytes, fa.row_bytes
+        obs, act, rew, dis, lengths = [], [], [], [], []
+        for i, ep in enumerate(episodes):
+            if len(ep) != 4:
+                raise ValueError(f"episode {i}: expected (observations, actions, rewards, "
+                                 f"discounts), got {len(ep)} arrays")
+            o, a = np.asarray(ep[0]), np.asarray(ep[1])
+            r, d = np.asarray(ep[2], np.float32), np.asarray(ep[3], np.float32)
+            L = int(r.shape[0]) if r.ndim == 1 else -1
+            if L < 0 or d.shape != (L,) or o.shape[:1] != (L,) or a.shape[:1] != (L,):
+                raise ValueError(f"episode {i}: the four arrays must share their length")
+            if o.shape[1:] != fo.shape or a.shape[1:] != fa.shape:
+                raise ValueError(
+                    f"episode {i}: rows of {o.shape[1:]} observations and {a.shape[1:]} actions "
+                    f"do not match the table's {fo.shape} ({fo.row_bytes} bytes) and {fa.shape} "
+                    f"({fa.row_bytes} bytes)")
+            obs.append(self._rows(o, fo))
+            act.append(self._rows(a, fa))
+            rew.append(r)
+            dis.append(d)
+            lengths.append(L)
+        if not lengths:
+            raise ValueError("no demonstration episodes")
+        self.lengths = np.asarray(lengths, np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        # Checks the lengths (ValueError for an episode shorter than 3 steps).
+        self._native = NativeDemoStore(self.offsets, fo.row_bytes, fa.row_bytes)
+        self._host = (np.concatenate(obs), np.concatenate(act), np.concatenate(rew),
+                      np.concatenate(dis))
+        self._device = device
+
+    @staticmethod
+    def _rows(x: np.ndarray, f) -> np.ndarray:
+        """[L, row_bytes] uint8 rows as the table stores them (C order, zero padding)."""
+        x = np.ascontiguousarray(x, dtype=f.dtype)
+        rows = np.zeros((x.shape[0], f.row_bytes), np.uint8)
+        rows[:, :f.nbytes] = np.frombuffer(x.tobytes(), np.uint8).reshape(x.shape[0], f.nbytes)
+        return rows
+
+    @property
+    def num_episodes(self) -> int:
+        return len(self.lengths)
+
+    def upload(self, device=None):
+        """Puts the rows on the device (once) and returns the native store."""
+        if self._host is not None:
+            self._native.upload(*self._host, device=device or self._device)
+            self._host = None
+        return self._native
+
+
+class _MixIterator(_TableIterator):
+    """_TableIterator whose every draw is followed, on the same stream and before the batch's
+    ready event, by the demonstration overlay.  The table draws with the unpipelined
+    acme_replay_sample_gather: the pipelined form copies a batch's rows in the next launch,
+    which would overwrite the overlay."""
+
+    def __init__(self, table, batch, timeout, prefetch, mix: "MixedDataset"):
+        super().__init__(table, batch, timeout, prefetch, shard=None)
+        self._mix = mix
+        self._store = None
+        self._flags = {}        # keys buffer address -> the slot's is_demo flags
+        self.last_is_demo = None  # uint8 [B] of the batch handed out last (if recorded)
+
+    def _open_pipe(self) -> None:
+        self._pipe = None
+        self._pending = None
+
+    def _f16_frames(self) -> bool:
+        return False
+
+    def _alloc(self):
+        fields = _transition_fields(self._t)
+        mix = self._mix
+        if (fields[0].row_bytes, fields[1].row_bytes) != (mix.store.obs_row_bytes,
+                                                          mix.store.action_row_bytes):
+            raise ValueError(_mismatch(fields, mix.store))
+        self._store = mix.store.upload(self._t.native.device)
+        super()._alloc()
+        if mix.record_is_demo:
+            for raw, _, _, info, _ in self._slots:
+                self._flags[raw[1]] = torch.zeros(self._rows, dtype=torch.uint8,
+                                                  device=info["keys"].device)
+
+    def _draw(self, L, h, raw, ptrs, st, stream=None, fb=None):
+        from acme_amd._lib import check
+        mix = self._mix
+        step = self._t.next_draw() & 0xFFFFFFFFFFFFFFFF
+        check(L.acme_replay_sample_gather(h, self._B, step, *raw, ptrs, st), "replay sample")
+        flags = self._flags.get(raw[1])
+        self._store.mix(mix.demonstration_ratio, mix.n_step, mix.discount, mix.seed, step,
+                        self._B, ptrs, raw[1], raw[2], raw[3], raw[4],
+                        0 if flags is None else flags.data_ptr(), st)
+        return self._B
+
+    def _sample_view(self, i: int, n: int):
+        self.last_is_demo = self._flags.get(self._slots[i][0][1])
+        return super()._sample_view(i, n)
+
+
+def _mismatch(fields, store) -> str:
+    return (f"the store holds {store.obs_row_bytes}-byte observation and "
+            f"{store.action_row_bytes}-byte action rows, the table "
+            f"{fields[0].row_bytes} and {fields[1].row_bytes}")
+
+
+class MixedDataset:
+    """What mix_demonstrations returns: the surface of ReplayDataset (batch_size,
+    element_spec, an iterator with holds_last_batches, last_inputs_event, last_frames_f16 =
+    None), plus the iterator's `last_is_demo` flags."""
+
+    def __init__(self, dataset: ReplayDataset, store: DemonstrationStore,
+                 demonstration_ratio: float, n_step: int, discount: float, seed: int,
+                 record_is_demo: bool):
+        self._dataset = dataset
+        self.table = dataset.table
+        self.store = store
+        self.demonstration_ratio = float(demonstration_ratio)
+        self.n_step = int(n_step)
+        self.discount = float(discount)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.record_is_demo = bool(record_is_demo)
+        self.batched = dataset.batched
+        self.batch_size = dataset.batch_size
+        self.prefetch = dataset.prefetch
+        self.timeout = dataset.timeout
+
+    @property
+    def element_spec(self):
+        return self._dataset.element_spec
+
+    def __iter__(self):
+        if _data_parallel() is not None and self._dataset.global_sampling is not False:
+            raise ValueError("demonstrations cannot be mixed into global sampling over shards")
+        it = _MixIterator(self.table, self.batch_size, self.timeout, self.prefetch, self)
+        return it if self.batched else _Unbatched(it)
+
+
+def mix_demonstrations(dataset: ReplayDataset, store: DemonstrationStore,
+                       demonstration_ratio: float, n_step: int, discount: float,
+                       seed: int = 0, record_is_demo: bool = True) -> MixedDataset:
+    """`dataset` (make_reverb_dataset over a transition table) with each row of every batch
+    replaced, with probability demonstration_ratio, by an n-step transition from `store`
+    (module docstring).  n_step and discount are the adder's.  At ratio 0 the batches are
+    those of `dataset`, bit for bit.  record_is_demo keeps a uint8 flag per row
+    (iterator.last_is_demo)."""
+    if not isinstance(dataset, ReplayDataset):
+        raise ValueError("mix_demonstrations takes the dataset make_reverb_dataset returns")
+    table = dataset.table
+    if isinstance(table, (replay.FrameTable, replay.QueueTable)):
+        raise ValueError(f"demonstrations are mixed into transition tables, not a "
+                         f"{type(table).__name__}")
+    if dataset.global_sampling:
+        raise ValueError("demonstrations cannot be mixed into global sampling over shards")
+    if os.environ.get("ACME_DATASET_F16", "0") == "1":
+        raise ValueError("ACME_DATASET_F16=1 (the dataset's f16 frame copy) is not supported "
+                         "with demonstrations: the copy would hold the replaced rows")
+    ratio = float(demonstration_ratio)
+    if not 0.0 <= ratio <= 1.0:  # also refuses NaN
+        raise ValueError(f"demonstration_ratio {demonstration_ratio} is outside [0, 1]")
+    if int(n_step) < 1:
+        raise ValueError("n_step must be >= 1")
+    if not isinstance(store, DemonstrationStore):
+        raise ValueError("store must be a DemonstrationStore")
+    if table.fields is not None:
+        fields = _transition_fields(table)
+        if (fields[0].row_bytes, fields[1].row_bytes) != (store.obs_row_bytes,
+                                                          store.action_row_bytes):
+            raise ValueError(_mismatch(fields, store))
+    return MixedDataset(dataset, store, ratio, n_step, discount, seed, record_is_demo)

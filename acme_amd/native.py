@@ -292,6 +292,68 @@ class NativeNStepWriter:
         return int(self._pending(self._h))
 
 
+class NativeDemoStore:
+    """acme_demo_store: demonstration episodes as immutable device arrays (csrc/demos.hip).
+    The constructor checks the layout on the host (a short episode is a ValueError, no GPU
+    needed); `upload()` puts the packed rows on the device, once; `mix()` overlays the
+    demonstration rows of a drawn batch (acme_demo_mix)."""
+
+    def __init__(self, offsets: np.ndarray, obs_row_bytes: int, action_row_bytes: int):
+        self.offsets = np.ascontiguousarray(offsets, np.int64)
+        self.obs_row_bytes = int(obs_row_bytes)
+        self.action_row_bytes = int(action_row_bytes)
+        self.device = None
+        h = ctypes.c_void_p()
+        check(lib().acme_demo_store_create(len(self.offsets) - 1, self.offsets.ctypes.data,
+                                           self.obs_row_bytes, self.action_row_bytes,
+                                           ctypes.byref(h)), "demonstration store")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                lib().acme_demo_store_destroy(h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def upload(self, observations: np.ndarray, actions: np.ndarray, rewards: np.ndarray,
+               discounts: np.ndarray, device=None) -> None:
+        """Packed host rows: uint8 [total, obs_row_bytes] and [total, action_row_bytes],
+        float32 [total] twice."""
+        _lib.require_gpu()
+        total = int(self.offsets[-1])
+        arrays = [np.ascontiguousarray(observations, np.uint8),
+                  np.ascontiguousarray(actions, np.uint8),
+                  np.ascontiguousarray(rewards, np.float32),
+                  np.ascontiguousarray(discounts, np.float32)]
+        want = [total * self.obs_row_bytes, total * self.action_row_bytes, 4 * total, 4 * total]
+        for a, n in zip(arrays, want):
+            if a.nbytes != n:
+                raise ValueError(f"demonstration array has {a.nbytes} bytes, expected {n}")
+        self.device = torch.device(device or "cuda")
+        with torch.cuda.device(self.device):
+            check(lib().acme_demo_store_upload(self._h, *[a.ctypes.data for a in arrays]),
+                  "demonstration store upload")
+
+    def mix(self, ratio: float, n_step: int, discount: float, seed: int, step: int, batch: int,
+            out_fields, keys: int, probabilities: int, table_size: int, priorities: int,
+            is_demo: int = 0, stream: Optional[int] = None) -> None:
+        """out_fields: a ctypes array of the five transition fields' device pointers; the
+        other outputs raw device addresses (0: not written); stream: a raw hipStream_t."""
+        check(lib().acme_demo_mix(self._h, float(ratio), int(n_step), float(discount),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                  int(batch), out_fields, keys or None, probabilities or None,
+                                  table_size or None, priorities or None, is_demo or None,
+                                  stream_ptr() if stream is None else stream),
+              "demonstration mix")
+
+
 def _device_array(address: int, count: int, dtype, device) -> torch.Tensor:
     """Copies `count` elements at a raw device address into a new tensor (test helper)."""
     nbytes = count * np.dtype(dtype).itemsize

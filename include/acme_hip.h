@@ -300,6 +300,53 @@ int acme_replay_storage(acme_replay* r, int32_t field, void** out);
 int64_t acme_replay_inserted(const acme_replay* r);
 int acme_replay_restore(acme_replay* r, int64_t inserted, void* stream);
 
+/* ---------------------------------------------------------- demonstrations -- */
+
+/* Learning from demonstrations (acme/agents/tf/dqfd/agent.py:111-118 mixes a mapped episode
+ * dataset into the replay stream with tf.data's sample_from_datasets).  Here the episodes
+ * live on the device and one launch overlays the demonstration rows of a batch the table
+ * has already drawn and gathered.
+ *
+ * Store: E episodes of L_e >= 3 steps each (the reference draws `first` from [0, L - 2),
+ * empty below 3: a shorter episode is ACME_ERR_INVALID), immutable after upload:
+ *   observations [total][obs_row_bytes], actions [total][action_row_bytes], rewards and
+ *   discounts f32 [total], offsets i64 [E + 1] (episode e is steps offsets[e] ..
+ *   offsets[e + 1] - 1; offsets[0] = 0, offsets[E] = total).
+ * The row bytes are those of fields 0 and 1 of the transition table the store is mixed
+ * with (multiples of 4).  acme_demo_store_create checks and keeps the host-side layout (no
+ * device call); acme_demo_store_upload allocates the device arrays on the current device
+ * and copies the four host arrays into them (synchronous, once). */
+typedef struct acme_demo_store acme_demo_store;
+
+int acme_demo_store_create(int64_t num_episodes, const int64_t* offsets, int64_t obs_row_bytes,
+                           int64_t action_row_bytes, acme_demo_store** out);
+int acme_demo_store_destroy(acme_demo_store* s);
+int acme_demo_store_upload(acme_demo_store* s, const void* observations, const void* actions,
+                           const float* rewards, const float* discounts);
+
+#define ACME_DEMO_KEY 0xFFFFFFFFFFFFFFFEull /* the key of every demonstration row */
+
+/* Overwrites the demonstration rows of a drawn batch of transitions (out_fields[0..4] =
+ * o_tm1, a_tm1, r_t f32, d_t f32, o_t; device buffers as acme_replay_sample_gather fills
+ * them) in one launch.  Row j makes one Philox4x32-10 call, counter (j, step_counter lo,
+ * step_counter hi, 0x44454D4F "DEMO"), key = seed, result r:
+ *   demonstration iff u01_53(r.x, r.y) < ratio (a replay row is left untouched);
+ *   episode e = (u64(r.z) * E) >> 32;  first = (u64(r.w) * (L_e - 2)) >> 32;
+ *   last = min(first + n_step, L_e - 1);  m = last - first.
+ * The n-step return restates _n_step_transition_from_episode (dqfd/agent.py:160-217;
+ * rewards are shifted by one step, discounts are not), in f32, in this order, unfused:
+ *   g_0 = c_0 = 1;  g_k = g_{k-1} * discount;  c_k = c_{k-1} * d[first + k - 1];
+ *   disc_k = c_k * g_k;  r_t = sum_{k = 0..m-1, left to right} rewards[first + 1 + k] * disc_k;
+ *   d_t = disc_{m-1};  o_tm1 = observations[first], a_tm1 = actions[first], o_t = observations[last].
+ * Its SampleInfo is probability 1, table_size 1, priority 1 and key ACME_DEMO_KEY (the
+ * reference's 0 is a live key here, and ~0 marks an empty slot; 2^64 - 2 equals no stored
+ * key, so a priority update drops it as stale).  is_demo (u8 [batch], may be NULL) receives
+ * 1 / 0 per row.  keys / probabilities / table_size / priorities may be NULL. */
+int acme_demo_mix(const acme_demo_store* s, double ratio, int32_t n_step, float discount,
+                  uint64_t seed, uint64_t step_counter, int64_t batch, void* const* out_fields,
+                  uint64_t* keys, double* probabilities, int64_t* table_size,
+                  double* priorities, uint8_t* is_demo, void* stream);
+
 /* -------------------------------------------------------------------- DQN -- */
 
 enum { ACME_NET_NATURE_DQN = 0, ACME_NET_MLP = 1 };
