@@ -310,6 +310,9 @@ _SIGS = {
     "acme_r2d2_num_steps": (c_i64, [c_vp]),
     "acme_r2d2_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_r2d2_set_lstm_unroll": (c_i32, [c_vp, c_i32]),
+    "acme_r2d2_q_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f64,
+                                 c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_epsilon_greedy": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_u64, c_u64, c_vp, c_vp]),
     "acme_r2d2_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
                                        ctypes.POINTER(c_i64)]),
     "acme_impala_create": (c_i32, [ctypes.POINTER(IMPALAConfig), ctypes.POINTER(c_vp)]),

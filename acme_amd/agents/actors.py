@@ -1,5 +1,5 @@
-"""Actors (acme/agents/tf/actors.py:35-94 FeedForwardActor) and the epsilon-greedy DQN
-policy (trfl.epsilon_greedy used at acme/agents/tf/dqn/agent.py:118-124)."""
+"""Actors (acme/agents/tf/actors.py:35-94 FeedForwardActor, :95-172 RecurrentActor) and the
+epsilon-greedy DQN policy (trfl.epsilon_greedy used at acme/agents/tf/dqn/agent.py:118-124)."""
 
 from __future__ import annotations
 
@@ -29,6 +29,55 @@ class FeedForwardActor(core.Actor):
     def observe(self, action, next_timestep):
         if self._adder is not None:
             self._adder.add(action, next_timestep)
+
+    def update(self):
+        if self._variable_client is not None:
+            self._variable_client.update()
+
+
+class RecurrentActor(core.Actor):
+    """A recurrent actor (acme/agents/tf/actors.py:95-172): unbatched observations in,
+    unbatched actions out, the recurrent state reset at episode starts and the state that
+    went into each step handed to the adder as extras={"core_state": LSTMState(h, c)} (the
+    layout of agents/r2d2/make_replay's signature).
+
+    `policy(observation, state, store_state)` runs one step and returns (action,
+    state_before_the_step): `state` is the LSTMState [1, H] to start from on an episode's
+    first call (`initial_state(1)`), None afterwards (the policy carries its own state, which
+    may live on the device); the returned state is an LSTMState [1, H], or None when
+    store_state is False.  R2D2Learner.make_policy builds one."""
+
+    def __init__(self, policy: Callable, initial_state: Callable, adder=None,
+                 variable_client=None, store_recurrent_state: bool = True):
+        self._policy = policy
+        self._initial_state = initial_state  # batch_size -> LSTMState
+        self._adder = adder
+        self._variable_client = variable_client
+        self._store = bool(store_recurrent_state)
+        self._fresh = True        # the next call starts from initial_state(1)
+        self._prev_state = None   # the state that went into the last step
+
+    def select_action(self, observation):
+        state = self._initial_state(1) if self._fresh else None
+        self._fresh = False
+        action, self._prev_state = self._policy(observation, state, self._store)
+        return action
+
+    def observe_first(self, timestep):
+        if self._adder is not None:
+            self._adder.add_first(timestep)
+        self._fresh = True  # re-initialised at the next policy call
+
+    def observe(self, action, next_timestep):
+        if self._adder is None:
+            return
+        if not self._store:
+            self._adder.add(action, next_timestep)
+            return
+        from acme_amd.networks import LSTMState
+        h, c = self._prev_state
+        core_state = LSTMState(np.asarray(h, np.float32)[0], np.asarray(c, np.float32)[0])
+        self._adder.add(action, next_timestep, extras={"core_state": core_state})
 
     def update(self):
         if self._variable_client is not None:

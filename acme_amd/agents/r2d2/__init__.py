@@ -6,7 +6,8 @@ two replay-facing computations as device kernels (csrc/r2d2.hip):
   compute_priority     learning.py:230-236 (written back with update_priorities, :196-199)
   importance_weights   learning.py:178-183
 and the learner itself, R2D2Learner (learning.py: csrc/r2d2_learner.hip, the recurrent
-duelling Q-network with burn-in and the transformed n-step loss).
+duelling Q-network with burn-in and the transformed n-step loss), and the R2D2 agent
+(agent.py: the learner, this replay and a RecurrentActor on acme_r2d2_q_step).
 """
 
 from __future__ import annotations
@@ -75,3 +76,6 @@ def make_replay(environment_spec, extra_spec, burn_in_length: int, trace_length:
     dataset = make_reverb_dataset(server_address=server, batch_size=batch_size,
                                   prefetch_size=prefetch_size, sequence_length=sequence_length)
     return server, adder, dataset
+
+
+from acme_amd.agents.r2d2.agent import R2D2  # noqa: E402,F401  (needs make_replay above)

@@ -77,6 +77,18 @@ struct RescaleGuard {
 int launch_duel_head_finish(const float* slab, int splits, int rows, int A, const float* bv,
                             const float* ba, float* q, hipStream_t st);
 
+// launch_duel_head_finish and launch_epsilon_greedy in one launch: the same q (bit for bit;
+// optional) and each row's epsilon-greedy action from the row just formed (optional; the
+// selection of acme_epsilon_greedy, include/acme_hip.h, on row index, seed, step_counter).
+// Measured no faster than the two launches on the R2D2 acting step (tools/r2d2_act_time.py),
+// which runs them; acme_r2d2_create takes this one with ACME_V_R2ACT=1.
+int launch_duel_head_act(const float* slab, int splits, int rows, int A, const float* bv,
+                         const float* ba, double epsilon, uint64_t seed, uint64_t step_counter,
+                         float* q, int32_t* actions, hipStream_t st);
+// The selection alone on rows of q [rows][A] (acme_epsilon_greedy; checks its arguments).
+int launch_epsilon_greedy(const float* q, int64_t rows, int A, double epsilon, uint64_t seed,
+                          uint64_t step_counter, int32_t* actions, hipStream_t st);
+
 // dZ of the fused hidden layer for rows b < B with dq[b] = g[b] * onehot(a[b]), masked by
 // the hidden ReLU.
 // With `planes` non-null the result is written as scaled f16 planes (gemm_p3.h Planes,

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "detmath.h"
 
 namespace acme {
 namespace {
@@ -49,6 +50,116 @@ __global__ void __launch_bounds__(256) duel_head_finish_kernel(const float* __re
   }
   const float mean = wave_sum(part) / (float)A;
   for (int j = lane; j < A; j += 64) qr[j] = v + ((j == lane ? first : qr[j]) - mean);
+}
+
+// ---- epsilon-greedy selection of the acting paths (include/acme_hip.h acme_epsilon_greedy)
+constexpr uint32_t kActTag = 0x52324143u;  // "R2AC"
+constexpr int kActSlots = 16;              // A <= 1024: action lane + 64 i in slot i
+
+// max(a, b) with NaNs ignored (NaN only when both are).
+__device__ __forceinline__ float nanmax(float a, float b) {
+  return b != b ? a : (a != a || b > a ? b : a);
+}
+
+// One row's action, by the wave that holds the row: lane l has q[l + 64 i] in qv[i].  All 64
+// lanes call it (ballots) and get the same result.  One Philox call per row:
+// explore iff u01_53(r.x, r.y) < epsilon, then (r.z A) >> 32; else the ((r.w n) >> 32)-th of
+// the n actions equal to the row's maximum (NaNs ignored), ascending; no maximum: action 0.
+__device__ __forceinline__ int select_action(const float (&qv)[kActSlots], int A, int lane,
+                                             uint32_t row, double epsilon, uint64_t seed,
+                                             uint64_t step) {
+  const u32x4 r = philox4x32_10(u32x4{row, (uint32_t)step, (uint32_t)(step >> 32), kActTag},
+                                (uint32_t)seed, (uint32_t)(seed >> 32));
+  if (u01_53(r.x, r.y) < epsilon) return (int)(((uint64_t)r.z * (uint64_t)A) >> 32);
+  const int slots = (A + 63) >> 6;
+  float m = NAN;
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i)
+    if (i < slots && lane + 64 * i < A) m = nanmax(m, qv[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = nanmax(m, __shfl_xor(m, o, 64));
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i)
+    if (i < slots) n += __popcll(__ballot(lane + 64 * i < A && qv[i] == m));
+  if (n == 0) return 0;
+  int k = (int)(((uint64_t)r.w * (uint64_t)n) >> 32);
+  int a = 0;
+  bool found = false;
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i)
+    if (i < slots && !found) {
+      unsigned long long mask = __ballot(lane + 64 * i < A && qv[i] == m);
+      const int c = __popcll(mask);
+      if (k < c) {
+        for (int s = 0; s < k; ++s) mask &= mask - 1;  // drop the k lowest members
+        a = 64 * i + __ffsll((long long)mask) - 1;
+        found = true;
+      } else {
+        k -= c;
+      }
+    }
+  return a;
+}
+
+// The acting path's head epilogue: duel_head_finish_kernel's sums in its order (the same q
+// bits), the row kept in registers instead of parked in q, then the row's action from it.
+// q and actions are optional.
+__global__ void __launch_bounds__(256) duel_head_act_kernel(
+    const float* __restrict__ slab, int splits, int rows, int A, const float* __restrict__ bv,
+    const float* __restrict__ ba, double epsilon, uint64_t seed, uint64_t step,
+    float* __restrict__ q, int32_t* __restrict__ actions) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int N = A + 1, slots = (A + 63) >> 6;
+  float v = 0.f;
+  for (int s = 0; s < splits; ++s) v += slab[((size_t)s * rows + row) * N + A];
+  v += bv[0];
+  float qv[kActSlots];
+  float part = 0.f;
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i) {
+    const int j = lane + 64 * i;
+    qv[i] = 0.f;
+    if (i < slots && j < A) {
+      float acc = 0.f;
+      for (int s = 0; s < splits; ++s) acc += slab[((size_t)s * rows + row) * N + j];
+      acc += ba[j];
+      qv[i] = acc;
+      part = i == 0 ? acc : part + acc;
+    }
+  }
+  const float mean = wave_sum(part) / (float)A;
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i) {
+    const int j = lane + 64 * i;
+    if (i < slots && j < A) {
+      qv[i] = v + (qv[i] - mean);
+      if (q) q[(size_t)row * A + j] = qv[i];
+    }
+  }
+  const int a = select_action(qv, A, lane, (uint32_t)row, epsilon, seed, step);
+  if (actions && lane == 0) actions[row] = a;
+}
+
+// select_action on rows of a caller's q [rows][A].
+__global__ void __launch_bounds__(256) epsilon_greedy_kernel(const float* __restrict__ q,
+                                                             int64_t rows, int A, double epsilon,
+                                                             uint64_t seed, uint64_t step,
+                                                             int32_t* __restrict__ actions) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int slots = (A + 63) >> 6;
+  float qv[kActSlots];
+#pragma unroll
+  for (int i = 0; i < kActSlots; ++i) {
+    const int j = lane + 64 * i;
+    qv[i] = i < slots && j < A ? q[(size_t)row * A + j] : 0.f;
+  }
+  const int a = select_action(qv, A, lane, (uint32_t)row, epsilon, seed, step);
+  if (lane == 0) actions[row] = a;
 }
 
 // dZ of the fused hidden layer: thread per (b, k).
@@ -1333,6 +1444,28 @@ int launch_duel_head_finish(const float* slab, int splits, int rows, int A, cons
   return ACME_OK;
 }
 
+int launch_duel_head_act(const float* slab, int splits, int rows, int A, const float* bv,
+                         const float* ba, double epsilon, uint64_t seed, uint64_t step_counter,
+                         float* q, int32_t* actions, hipStream_t st) {
+  ACME_CHECK_ARG(A >= 1 && A <= 64 * kActSlots, "num_actions must be in [1, %d]", 64 * kActSlots);
+  duel_head_act_kernel<<<(unsigned)ceil_div(rows, 4), 256, 0, st>>>(
+      slab, splits, rows, A, bv, ba, epsilon, seed, step_counter, q, actions);
+  ACME_LAUNCH_CHECK();
+  return ACME_OK;
+}
+
+int launch_epsilon_greedy(const float* q, int64_t rows, int A, double epsilon, uint64_t seed,
+                          uint64_t step_counter, int32_t* actions, hipStream_t st) {
+  ACME_CHECK_ARG(q && actions, "null buffer");
+  ACME_CHECK_ARG(rows >= 1 && rows <= (int64_t)INT32_MAX, "rows must be in [1, 2^31 - 1]");
+  ACME_CHECK_ARG(A >= 1 && A <= 64 * kActSlots, "num_actions must be in [1, %d]", 64 * kActSlots);
+  ACME_CHECK_ARG(epsilon >= 0.0 && epsilon <= 1.0, "epsilon must be in [0, 1]");  // NaN fails
+  epsilon_greedy_kernel<<<(unsigned)ceil_div(rows, 4), 256, 0, st>>>(q, rows, A, epsilon, seed,
+                                                                     step_counter, actions);
+  ACME_LAUNCH_CHECK();
+  return ACME_OK;
+}
+
 int launch_duel_head_dz(const float* h, const float* g, const int32_t* a, int B, int H, int A,
                         const float* wv, const float* wa, float* dzh, hipStream_t st,
                         uint16_t* planes, int64_t pstride, gemm::PScale* sc) {
@@ -1755,6 +1888,12 @@ int acme_dense_forward_staged(const float* x, int64_t rows, int64_t in, const fl
     return ACME_ERR_HIP;
   }
   return ACME_OK;
+}
+
+int acme_epsilon_greedy(const float* q, int64_t rows, int32_t num_actions, double epsilon,
+                        uint64_t seed, uint64_t step_counter, int32_t* actions, void* stream) {
+  return acme::launch_epsilon_greedy(q, rows, num_actions, epsilon, seed, step_counter, actions,
+                                     acme::as_stream(stream));
 }
 
 int acme_min_f64(const double* x, int64_t n, double* out_dev, void* stream) {

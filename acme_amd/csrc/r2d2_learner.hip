@@ -97,6 +97,12 @@ struct acme_r2d2 : RecurrentNet {
   // ACME_V_RGTRACE=1 at creation: per-step timestamps of the last forward and BPTT launches
   // (debug_buffer "lstm_trace": [2][kMaxSeq][4] u64, forward then BPTT).
   unsigned long long* rg_trace = nullptr;
+  // The acting step (acme_r2d2_q_step) ends with launch_duel_head_finish and
+  // acme_epsilon_greedy's launch; act_q [max_batch][A] holds the row when the caller asks
+  // for no q.  ACME_V_R2ACT=1 at creation: one fused launch instead (launch_duel_head_act:
+  // measured no faster, tools/r2d2_act_time.py; kept for that comparison).
+  float* act_q = nullptr;
+  bool act_fused = false;
 };
 
 namespace {
@@ -767,6 +773,8 @@ int acme_r2d2_create(const acme_r2d2_config* cfg, acme_r2d2** out) {
     return fail(rc);
   if (hipMemset(l->zero_state, 0, (size_t)B * H * sizeof(float)) != hipSuccess)
     return fail((set_error("hipMemset failed"), ACME_ERR_HIP));
+  l->act_fused = tune_variant("R2ACT") == 1;
+  if ((rc = dev_alloc(l, &l->act_q, (int64_t)B * A))) return fail(rc);
   *out = l;
   return ACME_OK;
 }
@@ -830,6 +838,69 @@ int acme_r2d2_step(acme_r2d2* l, const acme_sequence_batch* b, const double* pro
   return calibrate_then_step(l, l->p3, st, [&](bool apply) {
     return r2d2_step_impl(l, b, probabilities, out, st, apply);
   });
+}
+
+// One time step of network_forward's f32 arithmetic over `rows` actor rows (T = 1: rows
+// [0, rows) of the workspace), then the actions selected from the q rows.
+int acme_r2d2_q_step(acme_r2d2* l, const void* obs, const int32_t* prev_action,
+                     const float* prev_reward, const float* h, const float* c,
+                     int64_t state_stride, int64_t rows, int32_t use_target, double epsilon,
+                     uint64_t seed, uint64_t step_counter, float* q, int32_t* actions,
+                     float* h_out, float* c_out, void* stream) {
+  ACME_CHECK_ARG(l && obs && prev_action && prev_reward && h && c, "null argument");
+  ACME_CHECK_ARG(l->params, "acme_r2d2_bind must be called first");
+  ACME_CHECK_ARG(rows >= 1 && rows <= l->cfg.max_batch, "rows must be in [1, max_batch=%d]",
+                 l->cfg.max_batch);
+  ACME_CHECK_ARG(epsilon >= 0.0 && epsilon <= 1.0, "epsilon must be in [0, 1]");  // NaN fails
+  ACME_CHECK_ARG(state_stride >= l->H && state_stride % 4 == 0 && ((uintptr_t)h & 15) == 0 &&
+                     ((uintptr_t)c & 15) == 0,
+                 "core state rows must be 16-byte aligned with state_stride >= lstm_size");
+  ACME_CHECK_ARG(!atari(l) || ((uintptr_t)obs & 15) == 0, "frames must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const int R = (int)rows, H = l->H, A = l->A, H2 = l->H2;
+  const float* prm = use_target ? l->target : l->params;
+  int rc = oar_forward_f32(l, prm, obs, R, prev_action, prev_reward, "r2d2_act_oar_fwd",
+                           "r2d2_act_oar_reduce", st);
+  if (rc != ACME_OK) return rc;
+  {
+    ACME_PROF("r2d2_act_lstm", st, 2.0 * R * (double)H * 4 * H, 0.0);
+    const dim3 grid((unsigned)(H / kFwdUnits), (unsigned)ceil_div(R, l->bc));
+    lstm_fwd_step_kernel<<<grid, 256, l->fwd_smem, st>>>(l->gx, P(l, prm, l->t_wh), h,
+                                                         state_stride, c, state_stride, R, 1, R,
+                                                         0, H, l->gates, l->h, l->c, l->bc);
+    ACME_LAUNCH_CHECK();
+  }
+  {
+    DenseFwd<true> p;
+    p.M = R; p.N = 2 * H2; p.K = H; p.k_chunk = H;
+    p.x = l->h; p.x2 = p.x; p.split_b = R; p.ldx = H;
+    p.w = P(l, prm, l->t_hw); p.bias = P(l, prm, l->t_hb); p.y = l->hid;
+    p.act = ACT_RELU; p.slab = nullptr;
+    ACME_GEMM("r2d2_act_hidden", 64, 64, 2, 2, 16, 1, p, 1);
+  }
+  {
+    DuelHeadFwd p;
+    p.M = R; p.N = A + 1; p.K = 2 * H2; p.k_chunk = chunk_for(p.K, kHeadFwdSplits);
+    p.H = H2; p.A = A; p.h = l->hid; p.wv = P(l, prm, l->t_vw); p.wa = P(l, prm, l->t_aw);
+    p.slab = l->slab;
+    ACME_GEMM("r2d2_act_head", 64, 32, 2, 1, 16, 1, p, kHeadFwdSplits);
+    ACME_PROF("r2d2_act_finish", st, 0.0, 0.0);
+    if (l->act_fused) {
+      rc = launch_duel_head_act(l->slab, kHeadFwdSplits, R, A, P(l, prm, l->t_vb),
+                                P(l, prm, l->t_ab), epsilon, seed, step_counter, q, actions, st);
+    } else {
+      float* qr = q ? q : l->act_q;
+      rc = launch_duel_head_finish(l->slab, kHeadFwdSplits, R, A, P(l, prm, l->t_vb),
+                                   P(l, prm, l->t_ab), qr, st);
+      if (rc == ACME_OK && actions)
+        rc = launch_epsilon_greedy(qr, R, A, epsilon, seed, step_counter, actions, st);
+    }
+    if (rc != ACME_OK) return rc;
+  }
+  const size_t state_bytes = (size_t)rows * H * sizeof(float);
+  if (h_out) ACME_HIP_TRY(hipMemcpyAsync(h_out, l->h, state_bytes, hipMemcpyDeviceToDevice, st));
+  if (c_out) ACME_HIP_TRY(hipMemcpyAsync(c_out, l->c, state_bytes, hipMemcpyDeviceToDevice, st));
+  return ACME_OK;
 }
 
 int acme_r2d2_set_lstm_unroll(acme_r2d2* l, int32_t mode) {

@@ -1278,3 +1278,52 @@ class NativeR2D2(_PlaneState, _NativeLearner):
         self._last = (T - self.burn_in_length - 1, B)
         check(lib().acme_r2d2_step(self._h, ctypes.byref(b), ptr(probabilities), ctypes.byref(o),
                                    stream_ptr(stream)), "r2d2 step")
+
+    def q_step(self, obs, prev_action, prev_reward, h, c, *, epsilon: float, seed: int,
+               step: int, use_target: bool = False, stream=None, out=None):
+        """One network step for `rows` actors (acme_r2d2_q_step): device tensors obs
+        [rows, ...], prev_action int32 / prev_reward float32 [rows], core state h / c
+        [rows, H] float32 views with unit inner stride and one row stride.  Returns (q
+        [rows, A], actions int32 [rows], h, c), the epsilon-greedy actions drawn from (seed,
+        step, row).  out: four device tensors (or None to skip an output) to write into; the
+        state outputs may be h and c themselves."""
+        rows = int(prev_action.shape[0])
+        A, H = self.num_actions, self.lstm_size
+        for name, t in (("h", h), ("c", c)):
+            if (t.dtype != torch.float32 or tuple(t.shape) != (rows, H) or t.stride(1) != 1
+                    or not t.is_cuda):
+                raise ValueError(f"{name} must be a float32 [{rows}, {H}] device tensor with "
+                                 "unit inner stride")
+        if h.stride(0) != c.stride(0):
+            raise ValueError("h and c must share a row stride")
+        if out is None:
+            out = [torch.empty(rows, A, dtype=torch.float32, device=self.device),
+                   torch.empty(rows, dtype=torch.int32, device=self.device),
+                   torch.empty(rows, H, dtype=torch.float32, device=self.device),
+                   torch.empty(rows, H, dtype=torch.float32, device=self.device)]
+        for o in out[2:]:
+            if o is not None and not o.is_contiguous():
+                raise ValueError("the state outputs must be contiguous [rows, H] tensors")
+        check(lib().acme_r2d2_q_step(
+            self._h, ptr(obs.contiguous()), ptr(prev_action.contiguous()),
+            ptr(prev_reward.contiguous()), ptr(h), ptr(c), int(h.stride(0)), rows,
+            1 if use_target else 0, float(epsilon), int(seed) & (2 ** 64 - 1),
+            int(step) & (2 ** 64 - 1), *[ptr(o) for o in out], stream_ptr(stream)), "r2d2 q_step")
+        return tuple(out)
+
+
+def epsilon_greedy(q: torch.Tensor, epsilon: float, seed: int, step: int,
+                   stream=None) -> torch.Tensor:
+    """Epsilon-greedy actions (int32 [rows]) of a contiguous float32 [rows, A] device tensor:
+    acme_epsilon_greedy, trfl's epsilon_greedy(q, epsilon).sample() drawn from (seed, step,
+    row)."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float32
+            and q.dim() == 2 and q.is_contiguous()):
+        raise ValueError("q must be a contiguous float32 [rows, A] device tensor")
+    rows, A = int(q.shape[0]), int(q.shape[1])
+    out = torch.empty(rows, dtype=torch.int32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib().acme_epsilon_greedy(ptr(q), rows, A, float(epsilon),
+                                        int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                        ptr(out), stream_ptr(stream)), "epsilon_greedy")
+    return out

@@ -1043,6 +1043,30 @@ int acme_r2d2_set_num_steps(acme_r2d2* l, int64_t n);
 /* mode 0 (default): the LSTM unroll and BPTT in one launch each when lstm_size is 256 or 512
  * and ceil(B / 4) * lstm_size / 16 <= 256; 1: one launch per time step (tests). */
 int acme_r2d2_set_lstm_unroll(acme_r2d2* l, int32_t mode);
+/* One network step for `rows` independent actors (1 <= rows <= max_batch) on the online
+ * parameters, or the target's with use_target != 0: inputs obs [rows, ...] (uint8 frames,
+ * 16-byte aligned, or f32 [rows, obs_dim]), prev_action / prev_reward [rows], core state rows
+ * h / c at h + i * state_stride (state_stride >= lstm_size, a multiple of 4, 16-byte aligned
+ * rows).  Outputs, each optional: q [rows, A], actions [rows] (acme_epsilon_greedy's
+ * selection on each row of q, row index = actor row), the next state h_out / c_out
+ * [rows, lstm_size]; h_out may be h and c_out may be c (the state is read before it is
+ * written), so an actor keeps its core state on the device.
+ * The arithmetic is one time step of the learner step's f32 forward (OAR embedding, one LSTM
+ * step, the duelling hidden layer and split-K head), also on a learner whose step runs the
+ * Atari plane path (as acme_impala_policy_step without policy planes).  The call reads the
+ * parameters and writes rows [0, rows) of the learner's activation workspace (gx, gates, h,
+ * c, the hidden layer, the split-K slab, the torso activations; a q scratch of its own when
+ * no q is requested) on `stream`; it neither reads nor writes the plane scale records, the
+ * step guard and skip word, the LSTM timeout words, the one-launch unroll's granule tags,
+ * num_steps or Adam's state.  Like acme_impala_policy_step it is ordered against learner
+ * steps by the caller: issue both on one stream, or order the streams with events.
+ * ACME_ERR_INVALID: unbound learner, rows out of range, epsilon outside [0, 1] (NaN
+ * included), a misaligned or too narrow state, misaligned frames. */
+int acme_r2d2_q_step(acme_r2d2* l, const void* obs, const int32_t* prev_action,
+                     const float* prev_reward, const float* h, const float* c,
+                     int64_t state_stride, int64_t rows, int32_t use_target, double epsilon,
+                     uint64_t seed, uint64_t step_counter, float* q, int32_t* actions,
+                     float* h_out, float* c_out, void* stream);
 /* "q" / "target_q" [(T - burn_in) * B, A] time-major suffix rows, "h" [T * B, H]
  * time-major, "g" [(T - burn_in) * B] d loss / d q[a], "hid", "x1" "x2" "x3", "lstm_timeout"
  * (the one-launch unroll's sticky spin-timeout word; the loss reads NaN once it is set). */
@@ -1050,6 +1074,21 @@ int acme_r2d2_debug_buffer(const acme_r2d2* l, const char* name, const float** o
                            int64_t* count);
 
 /* ----------------------------------------------------------- elementwise ops -- */
+
+/* Epsilon-greedy actions of q [rows, num_actions] (device, f32; num_actions in [1, 1024],
+ * rows in [1, 2^31 - 1], epsilon in [0, 1]) with trfl's epsilon_greedy(q, epsilon).sample()
+ * distribution: greedy ties share the greedy mass.  One wave per row, one Philox4x32-10 call
+ * per row, so a draw is reproducible from (seed, step_counter, row): counter (row,
+ * step_counter lo, step_counter hi, 0x52324143 "R2AC"), key = seed, result r:
+ *   the row explores iff u01_53(r.x, r.y) < epsilon;
+ *   exploring:  a = (u64(r.z) * A) >> 32;
+ *   greedy:     m = the row's maximum with NaNs ignored, G = {a : q[a] == m} ascending,
+ *               n = |G|, a = G[(u64(r.w) * n) >> 32];
+ *   a row with no maximum (every value NaN) gives action 0.
+ * The multiply-shift maps 2^32 words onto A (or n) values, so each value's probability
+ * departs from uniform by at most 2^-32, A / 2^32 in total. */
+int acme_epsilon_greedy(const float* q, int64_t rows, int32_t num_actions, double epsilon,
+                        uint64_t seed, uint64_t step_counter, int32_t* actions, void* stream);
 
 /* ------------------------------------------------------------- profiling -- */
 /* Section profiler: when enabled, every kernel section records a HIP event pair on the
