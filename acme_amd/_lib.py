@@ -243,23 +243,11 @@ _SIGS = {
     "acme_demo_store_upload": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_demo_mix": (c_i32, [c_vp, c_f64, c_i32, c_f32, c_u64, c_u64, c_i64,
                               ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_dqn_create": (c_i32, [ctypes.POINTER(DQNConfig), ctypes.POINTER(c_vp)]),
-    "acme_dqn_destroy": (c_i32, [c_vp]),
     "acme_dqn_num_params": (c_i64, [c_vp]),
-    "acme_dqn_flat_size": (c_i64, [c_vp]),
-    "acme_dqn_num_tensors": (c_i32, [c_vp]),
-    "acme_dqn_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                     ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_dqn_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_dqn_params_changed": (c_i32, [c_vp]),
     "acme_dqn_plane_overflow": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32]),
-    "acme_dqn_skipped_steps": (c_i64, [c_vp]),
-    "acme_dqn_guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_dqn_verdict_timeouts": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_dqn_update_rider_launches": (c_i64, [c_vp]),
     "acme_dqn_fused_x2_launches": (c_i64, [c_vp]),
-    "acme_dqn_set_applied_steps": (c_i32, [c_vp, c_i64]),
     "acme_dqn_skip_word": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
     "acme_dqn_set_reissue": (c_i32, [c_vp, c_i32]),
     "acme_dqn_verdicts_issued": (c_i64, [c_vp]),
@@ -272,8 +260,6 @@ _SIGS = {
     "acme_nccl_get_unique_id": (c_i32, [c_vp]),
     "acme_nccl_comm_init": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "acme_nccl_comm_destroy": (c_i32, [c_vp]),
-    "acme_dqn_scale_state": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32)]),
-    "acme_dqn_set_scale_state": (c_i32, [c_vp, c_vp, c_i32]),
     "acme_dqn_forward_backward": (c_i32, [c_vp, ctypes.POINTER(TransitionBatch),
                                           ctypes.POINTER(DQNOutputs), c_vp]),
     "acme_dqn_apply": (c_i32, [c_vp, c_vp]),
@@ -285,126 +271,24 @@ _SIGS = {
     "acme_dqn_step_update": (c_i32, [c_vp, ctypes.POINTER(TransitionBatch),
                                      ctypes.POINTER(DQNOutputs), c_vp, c_vp, c_vp, c_vp]),
     "acme_dqn_q_values": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
-    "acme_dqn_num_steps": (c_i64, [c_vp]),
-    "acme_dqn_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                      ctypes.POINTER(c_i64)]),
-    "acme_dqn_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_min_f64": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
-    "acme_r2d2_create": (c_i32, [ctypes.POINTER(R2D2Config), ctypes.POINTER(c_vp)]),
-    "acme_r2d2_destroy": (c_i32, [c_vp]),
-    "acme_r2d2_flat_size": (c_i64, [c_vp]),
-    "acme_r2d2_num_tensors": (c_i32, [c_vp]),
-    "acme_r2d2_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_r2d2_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_r2d2_step": (c_i32, [c_vp, ctypes.POINTER(SequenceBatch), c_vp,
                                ctypes.POINTER(R2D2Outputs), c_vp]),
-    "acme_r2d2_params_changed": (c_i32, [c_vp]),
-    "acme_r2d2_scale_state": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32)]),
-    "acme_r2d2_set_scale_state": (c_i32, [c_vp, c_vp, c_i32]),
-    "acme_r2d2_skipped_steps": (c_i64, [c_vp]),
-    "acme_r2d2_guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
     "acme_r2d2_skip_word": (c_vp, [c_vp]),
-    "acme_r2d2_set_applied_steps": (c_i32, [c_vp, c_i64]),
-    "acme_r2d2_num_steps": (c_i64, [c_vp]),
-    "acme_r2d2_set_num_steps": (c_i32, [c_vp, c_i64]),
     "acme_r2d2_set_lstm_unroll": (c_i32, [c_vp, c_i32]),
     "acme_r2d2_q_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f64,
                                  c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_epsilon_greedy": (c_i32, [c_vp, c_i64, c_i32, c_f64, c_u64, c_u64, c_vp, c_vp]),
-    "acme_r2d2_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                       ctypes.POINTER(c_i64)]),
-    "acme_impala_create": (c_i32, [ctypes.POINTER(IMPALAConfig), ctypes.POINTER(c_vp)]),
-    "acme_impala_destroy": (c_i32, [c_vp]),
-    "acme_impala_flat_size": (c_i64, [c_vp]),
-    "acme_impala_num_tensors": (c_i32, [c_vp]),
-    "acme_impala_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                        ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                        ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_impala_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_impala_params_changed": (c_i32, [c_vp]),
     "acme_impala_step": (c_i32, [c_vp, ctypes.POINTER(SequenceBatch), c_vp, c_vp]),
     "acme_impala_set_lstm_unroll": (c_i32, [c_vp, c_i32]),
     "acme_impala_plane_overflow": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32]),
-    "acme_impala_skipped_steps": (c_i64, [c_vp]),
-    "acme_impala_guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
-    "acme_impala_set_applied_steps": (c_i32, [c_vp, c_i64]),
-    "acme_impala_scale_state": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32)]),
-    "acme_impala_set_scale_state": (c_i32, [c_vp, c_vp, c_i32]),
     "acme_impala_policy_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),
     "acme_impala_set_policy_planes": (c_i32, [c_vp, c_i32]),
-    "acme_impala_num_steps": (c_i64, [c_vp]),
-    "acme_impala_set_num_steps": (c_i32, [c_vp, c_i64]),
-    "acme_impala_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                         ctypes.POINTER(c_i64)]),
-    "acme_d4pg_create": (c_i32, [ctypes.POINTER(D4PGConfig), ctypes.POINTER(c_vp)]),
-    "acme_d4pg_destroy": (c_i32, [c_vp]),
-    "acme_d4pg_flat_size": (c_i64, [c_vp]),
-    "acme_d4pg_policy_size": (c_i64, [c_vp]),
-    "acme_d4pg_num_tensors": (c_i32, [c_vp]),
-    "acme_d4pg_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_d4pg_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_d4pg_step": (c_i32, [c_vp, ctypes.POINTER(D4PGBatch), ctypes.POINTER(D4PGOutputs),
-                               c_vp]),
-    "acme_d4pg_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
-    "acme_d4pg_num_steps": (c_i64, [c_vp]),
-    "acme_d4pg_set_num_steps": (c_i32, [c_vp, c_i64]),
-    "acme_d4pg_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                       ctypes.POINTER(c_i64)]),
-    "acme_ddpg_create": (c_i32, [ctypes.POINTER(DDPGConfig), ctypes.POINTER(c_vp)]),
-    "acme_ddpg_destroy": (c_i32, [c_vp]),
-    "acme_ddpg_flat_size": (c_i64, [c_vp]),
-    "acme_ddpg_policy_size": (c_i64, [c_vp]),
-    "acme_ddpg_num_tensors": (c_i32, [c_vp]),
-    "acme_ddpg_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_ddpg_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_ddpg_step": (c_i32, [c_vp, ctypes.POINTER(D4PGBatch), ctypes.POINTER(D4PGOutputs),
-                               c_vp]),
-    "acme_ddpg_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
-    "acme_ddpg_num_steps": (c_i64, [c_vp]),
-    "acme_ddpg_set_num_steps": (c_i32, [c_vp, c_i64]),
-    "acme_ddpg_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                       ctypes.POINTER(c_i64)]),
-    "acme_mpo_create": (c_i32, [ctypes.POINTER(MPOConfig), ctypes.POINTER(c_vp)]),
-    "acme_mpo_destroy": (c_i32, [c_vp]),
-    "acme_mpo_flat_size": (c_i64, [c_vp]),
-    "acme_mpo_policy_size": (c_i64, [c_vp]),
     "acme_mpo_dual_offset": (c_i64, [c_vp]),
-    "acme_mpo_num_tensors": (c_i32, [c_vp]),
-    "acme_mpo_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                     ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_mpo_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_mpo_init_duals": (c_i32, [c_vp]),
-    "acme_mpo_step": (c_i32, [c_vp, ctypes.POINTER(MPOBatch), ctypes.POINTER(MPOOutputs), c_vp]),
-    "acme_mpo_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
-    "acme_mpo_num_steps": (c_i64, [c_vp]),
-    "acme_mpo_set_num_steps": (c_i32, [c_vp, c_i64]),
-    "acme_mpo_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                      ctypes.POINTER(c_i64)]),
-    "acme_dmpo_create": (c_i32, [ctypes.POINTER(DMPOConfig), ctypes.POINTER(c_vp)]),
-    "acme_dmpo_destroy": (c_i32, [c_vp]),
-    "acme_dmpo_flat_size": (c_i64, [c_vp]),
-    "acme_dmpo_policy_size": (c_i64, [c_vp]),
     "acme_dmpo_dual_offset": (c_i64, [c_vp]),
-    "acme_dmpo_num_tensors": (c_i32, [c_vp]),
-    "acme_dmpo_tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
-                                      ctypes.POINTER(ctypes.c_char_p)]),
-    "acme_dmpo_bind": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_dmpo_init_duals": (c_i32, [c_vp]),
-    "acme_dmpo_step": (c_i32, [c_vp, ctypes.POINTER(MPOBatch), ctypes.POINTER(MPOOutputs), c_vp]),
-    "acme_dmpo_policy": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
-    "acme_dmpo_num_steps": (c_i64, [c_vp]),
-    "acme_dmpo_set_num_steps": (c_i32, [c_vp, c_i64]),
-    "acme_dmpo_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
-                                       ctypes.POINTER(c_i64)]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),
@@ -415,6 +299,58 @@ _SIGS = {
     "acme_adam_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i64,
                                  c_vp]),
 }
+
+
+def _learner_sigs(prefix, config, bind, plane_guard=False, actor_critic=None):
+    """The prototypes every learner exports under acme_<prefix>_ (csrc/learner_common.h): the
+    handle's lifetime, its tensor table, the bind of `bind` flat buffers, the step count and
+    the debug buffers.  plane_guard: the plane-scale and step-guard exports as well
+    (csrc/plane_guard.h).  actor_critic = (batch struct, outputs struct, tensors policy()
+    writes): policy_size, step and policy as well."""
+    handle, count = (c_i32, [c_vp]), (c_i64, [c_vp])
+    sigs = {
+        "create": (c_i32, [ctypes.POINTER(config), ctypes.POINTER(c_vp)]),
+        "destroy": handle,
+        "flat_size": count,
+        "num_tensors": handle,
+        "tensor_info": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
+                                ctypes.POINTER(ctypes.c_char_p)]),
+        "bind": (c_i32, [c_vp] * (1 + bind)),
+        "num_steps": count,
+        "set_num_steps": (c_i32, [c_vp, c_i64]),
+        "debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
+                                 ctypes.POINTER(c_i64)]),
+    }
+    if plane_guard:
+        sigs.update({
+            "params_changed": handle,
+            "scale_state": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32)]),
+            "set_scale_state": (c_i32, [c_vp, c_vp, c_i32]),
+            "skipped_steps": count,
+            "guard_state": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),
+            "set_applied_steps": (c_i32, [c_vp, c_i64]),
+        })
+    if actor_critic:
+        batch, outputs, policy_outputs = actor_critic
+        sigs.update({
+            "policy_size": count,
+            "step": (c_i32, [c_vp, ctypes.POINTER(batch), ctypes.POINTER(outputs), c_vp]),
+            "policy": (c_i32, [c_vp, c_vp, c_i64, c_i32] + [c_vp] * (policy_outputs + 1)),
+        })
+    return {f"acme_{prefix}_{name}": sig for name, sig in sigs.items()}
+
+
+# One description per learner; what only one learner exports is written out above.
+for _learner in (
+        dict(prefix="dqn", config=DQNConfig, bind=5, plane_guard=True),
+        dict(prefix="impala", config=IMPALAConfig, bind=4, plane_guard=True),  # no target
+        dict(prefix="r2d2", config=R2D2Config, bind=5, plane_guard=True),
+        dict(prefix="d4pg", config=D4PGConfig, bind=5, actor_critic=(D4PGBatch, D4PGOutputs, 1)),
+        dict(prefix="ddpg", config=DDPGConfig, bind=5, actor_critic=(D4PGBatch, D4PGOutputs, 1)),
+        dict(prefix="mpo", config=MPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
+        dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2))):
+    _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

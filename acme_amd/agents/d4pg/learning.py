@@ -16,13 +16,12 @@ Adam(1e-4) for both (learning.py:113-114).
 
 from __future__ import annotations
 
-import time
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
-from acme_amd import core
+from acme_amd.agents._learner import Learner
 from acme_amd.native import NativeD4PG
 from acme_amd.utils import counting, loggers
 
@@ -41,9 +40,9 @@ def _learning_rate(optimizer, default: float = 1e-4) -> float:
     return float(getattr(optimizer, "learning_rate", default)) if optimizer is not None else default
 
 
-class D4PGLearner(core.Learner, core.Saveable):
+class D4PGLearner(Learner):
     """Also the base of DDPGLearner and MPOLearner, which build another native handle from
-    the same pieces (`_check_networks`, `_init_params`, `_init_bookkeeping`)."""
+    the same pieces (`_check_networks`, `_init_params`, Learner's `_init_bookkeeping`)."""
 
     _algorithm = "D4PG"  # names the learner in messages
 
@@ -67,7 +66,7 @@ class D4PGLearner(core.Learner, core.Saveable):
             critic_learning_rate=_learning_rate(critic_optimizer),
             clipping=clipping, device=device)
         self._init_params(target_policy_network, target_critic_network, seed)
-        self._init_bookkeeping(counter, logger, checkpoint)
+        self._init_bookkeeping(counter, logger)
 
     def _check_networks(self, policy_network, critic_network, observation_network,
                         target_observation_network, dataset, batch_size) -> int:
@@ -92,24 +91,18 @@ class D4PGLearner(core.Learner, core.Saveable):
         tinit.update(target_critic_network.init(seed + 3))
         self._native.set_params(init, tinit)
 
-    def _init_bookkeeping(self, counter, logger, checkpoint) -> None:
-        self._counter = counter or counting.Counter()
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
-        self._timestamp = None
-        self._checkpoint = checkpoint
-
-    def step(self):
+    def _native_step(self) -> None:
+        """Draws a batch and runs the native step on it."""
         sample = next(self._iterator)
         o_tm1, a_tm1, r_t, d_t, o_t = sample.data[:5]
         B = int(r_t.shape[0])
         f = lambda x: x.reshape(B, -1).to(torch.float32).contiguous()  # noqa: E731
         self._native.step(f(o_tm1), f(a_tm1), f(r_t).reshape(B), f(d_t).reshape(B), f(o_t))
-        now = time.time()
-        elapsed = now - self._timestamp if self._timestamp else 0
-        self._timestamp = now
-        result = {"critic_loss": self._native.critic_loss, "policy_loss": self._native.policy_loss}
-        result.update(self._counter.increment(steps=1, walltime=elapsed))
-        self._logger.write(result)
+
+    def step(self):
+        self._native_step()
+        self._finish_step({"critic_loss": self._native.critic_loss,
+                           "policy_loss": self._native.policy_loss})
 
     def policy(self, observations, use_target: bool = False) -> np.ndarray:
         x = torch.as_tensor(np.asarray(observations, np.float32))
@@ -126,18 +119,6 @@ class D4PGLearner(core.Learner, core.Saveable):
             out.append({k: v for k, v in target.items() if k.startswith(name + "/")})
         return out
 
-    @property
-    def native(self) -> NativeD4PG:
-        return self._native
-
-    @property
-    def num_steps(self) -> int:
-        return self._native.num_steps
-
-    @property
-    def state(self) -> Dict:
-        return self.save()
-
     def save(self) -> Dict:
         n = self._native
         return {"params": n.get_params("params"), "target": n.get_params("target"),
@@ -147,7 +128,5 @@ class D4PGLearner(core.Learner, core.Saveable):
     def restore(self, state: Dict):
         n = self._native
         n.set_params(state["params"], state["target"])
-        for buf, src in ((n.m, state["optimizer"]["m"]), (n.v, state["optimizer"]["v"])):
-            for k, t in n.views(buf).items():
-                t.copy_(torch.as_tensor(np.asarray(src[k], np.float32)).view(t.shape))
+        self._restore_moments(state["optimizer"])
         n.num_steps = int(state["num_steps"])

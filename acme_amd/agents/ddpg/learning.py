@@ -44,4 +44,4 @@ class DDPGLearner(D4PGLearner):
             critic_learning_rate=_learning_rate(critic_optimizer),
             clipping=clipping, device=device)
         self._init_params(target_policy_network, target_critic_network, seed)
-        self._init_bookkeeping(counter, logger, checkpoint)
+        self._init_bookkeeping(counter, logger)

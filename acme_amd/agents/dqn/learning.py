@@ -46,8 +46,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from acme_amd import core
 from acme_amd.adders import reverb as adders
+from acme_amd.agents._learner import PlaneLearner, obs_dtype
 from acme_amd.native import NativeDQN
 from acme_amd.utils import counting, loggers
 
@@ -57,7 +57,11 @@ _REISSUE_LAG = 2
 _REISSUE_ATTEMPTS = 3
 
 
-class DQNLearner(core.Learner, core.Saveable):
+class DQNLearner(PlaneLearner):
+
+    _algorithm = "DQN"
+    _skip_causes = "skipped on f16 plane overflow (their updates were not applied)"
+    _overflow_modes = ("reissue", "skip", "raise")
 
     def __init__(self, network, target_network, discount: float,
                  importance_sampling_exponent: float, learning_rate: float,
@@ -70,11 +74,9 @@ class DQNLearner(core.Learner, core.Saveable):
                  reduce_logged_loss: bool = True, on_plane_overflow: str = "reissue"):
         if huber_loss_parameter < 0:
             raise ValueError("quadratic_linear_boundary must be >= 0.")
-        if on_plane_overflow not in ("reissue", "skip", "raise"):
-            raise ValueError("on_plane_overflow must be 'reissue', 'skip' or 'raise'")
-        self._on_overflow = on_plane_overflow
-        self._skips_seen = 0
+        self._init_guard(on_plane_overflow)
         self._network = network
+        self._obs_dtype = obs_dtype(network)
         self._iterator = iter(dataset)
         B = batch_size or getattr(dataset, "batch_size", None) or 256
         self._B = B
@@ -98,11 +100,8 @@ class DQNLearner(core.Learner, core.Saveable):
         self._native.set_params(network.init(seed), target_network.init(
             seed + 1 if target_seed is None else target_seed))
         self._replay_client = replay_client
-        self._counter = counter or counting.Counter()
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.0)
-        self._timestamp = None
+        self._init_bookkeeping(counter, logger)
         self._obs_flat = int(np.prod(network.obs_shape))
-        self._checkpoint = checkpoint
         self._log_loss = True
         # Data parallel: whether the logged loss is all-reduced to the global batch's.  Every
         # rank must make the same choice (a collective issued on some ranks only would pair
@@ -149,20 +148,12 @@ class DQNLearner(core.Learner, core.Saveable):
         return x.contiguous()
 
     def _check_guard(self) -> int:
-        """Skipped steps the device has reported so far (no synchronisation); on a new one,
-        re-split the planes and recalibrate the scales before the next step, or raise."""
+        """With re-issue, the steps re-issued so far (after reading the verdicts due);
+        otherwise PlaneLearner's check."""
         if self._reissue:
             self._await_verdicts(settle=False)
             return self._reissued
-        n = self._native.skipped_steps
-        if n != self._skips_seen:
-            self._skips_seen = n
-            if self._on_overflow == "raise":
-                raise FloatingPointError(
-                    f"DQN learner: {n} step(s) skipped on f16 plane overflow (their updates "
-                    "were not applied)")
-            self._native.params_changed()
-        return n
+        return super()._check_guard()
 
     def _await_verdicts(self, settle: bool) -> None:
         """Reads the verdicts not yet settled: those of all steps but the last
@@ -251,17 +242,17 @@ class DQNLearner(core.Learner, core.Saveable):
         o_tm1, a_tm1, r_t, d_t, o_t = sample.data[:5]
         keys, probs = sample.info[:2]
         B = int(a_tm1.shape[0])
-        obs_dt = torch.uint8 if self._network.obs_dtype == "uint8" else torch.float32
+        obs_dt = self._obs_dtype
         views = (o_tm1.reshape(B, self._obs_flat), a_tm1.reshape(B), r_t.reshape(B),
                  d_t.reshape(B), o_t.reshape(B, self._obs_flat), probs)
         batch = tuple(self._prepare(x, dt) for x, dt in zip(
             views, (obs_dt, torch.int32, torch.float32, torch.float32, obs_dt, torch.float64)))
         # The batch's ready event lets the learner start its target forward without waiting
-        # for the previous step's tail, unless a conversion above produced new tensors on
-        # this stream.
-        inputs_event = getattr(self._iterator, "last_inputs_event", None)
-        if any(b is not v for b, v in zip(batch, views)):
-            inputs_event = None
+        # for the previous step's tail.  It covers the dataset's own tensors only: no event
+        # when this stream produced new ones, by a conversion above or the copies below.
+        inputs_event = None
+        if not self._copy_held and all(b is v for b, v in zip(batch, views)):
+            inputs_event = getattr(self._iterator, "last_inputs_event", None)
         # The dataset's fused gather also wrote the exact f16 copy of [o_tm1; o_t] (uint8
         # tables; rows [0, B) and [B, 2B) of its buffer): the learner then skips its own
         # conversion (same bits).
@@ -277,9 +268,6 @@ class DQNLearner(core.Learner, core.Saveable):
         self._issue(e)
         if self._reissue:
             self._held.append(e)
-        now = time.time()
-        elapsed = now - self._timestamp if self._timestamp else 0
-        self._timestamp = now
         loss = self._native.loss
         if self._dist is not None and self._log_loss and self._reduce_loss:
             # The logged loss is the global batch's (SURVEY §8(e) collective 3): each rank's
@@ -290,11 +278,7 @@ class DQNLearner(core.Learner, core.Saveable):
             else:
                 self._dist.all_reduce(loss)
                 loss.mul_(1.0 / self._dist.get_world_size())
-        result = {"loss": loss} if self._log_loss else {}
-        if skipped:
-            result["skipped_steps"] = skipped
-        result.update(self._counter.increment(steps=1, walltime=elapsed))
-        self._logger.write(result)
+        self._finish_step({"loss": loss} if self._log_loss else {}, skipped)
 
     def _staged_step(self, batch, fb, inputs_event=None):
         """The data-parallel step: the learner's stages with the collectives between them.
@@ -343,8 +327,7 @@ class DQNLearner(core.Learner, core.Saveable):
     # ------------------------------------------------------------------ variables
     def q_values(self, observations, use_target: bool = False) -> np.ndarray:
         self._settle()
-        obs_dt = torch.uint8 if self._network.obs_dtype == "uint8" else torch.float32
-        x = torch.as_tensor(np.asarray(observations)).to(self._native.device, obs_dt)
+        x = torch.as_tensor(np.asarray(observations)).to(self._native.device, self._obs_dtype)
         x = x.reshape(x.shape[0], -1).contiguous()
         q = self._native.q_values(x, use_target).cpu().numpy()
         if self._skip_word and self._native.guard_state()["q_values_overflowed"]:
@@ -358,42 +341,12 @@ class DQNLearner(core.Learner, core.Saveable):
         sonnet = self._network.to_sonnet(self._native.get_params("params"))
         return [[sonnet[k] for k in sorted(sonnet)]]
 
-    @property
-    def num_steps(self) -> int:
-        return self._native.num_steps
-
-    @property
-    def native(self) -> NativeDQN:
-        return self._native
-
-    @property
-    def state(self) -> Dict:
-        return self.save()
-
     def save(self) -> Dict:
         self._settle()
-        n = self._native
-        return {"network": n.get_params("params"), "target_network": n.get_params("target"),
-                # Adam's t: the updates applied (step() calls minus skipped steps).
-                "optimizer": {"m": n.get_params("m"), "v": n.get_params("v"),
-                              "step": n.applied_steps},
-                "num_steps": n.num_steps,
-                # f16 plane scales (csrc/gemm_p3.h): restoring them keeps a resumed run
-                # bit-identical to an uninterrupted one.
-                "plane_scales": n.scale_state()}
+        return super().save()
 
     def restore(self, state: Dict):
         self._settle()
         self._held.clear()
-        n = self._native
-        n.set_params(state["network"], state["target_network"])
-        for buf, src in ((n.m, state["optimizer"]["m"]), (n.v, state["optimizer"]["v"])):
-            views = n.views(buf)
-            for k, t in views.items():
-                t.copy_(torch.as_tensor(np.asarray(src[k], np.float32)).view(t.shape))
-        n.params_changed()
-        if "plane_scales" in state:
-            n.set_scale_state(state["plane_scales"])
-        n.num_steps = int(state["num_steps"])
-        n.applied_steps = int(state["optimizer"].get("step", state["num_steps"]))
-        self._checked = n.verdicts_issued
+        super().restore(state)
+        self._checked = self._native.verdicts_issued

@@ -17,22 +17,14 @@ FloatingPointError with on_plane_overflow="raise").
 from __future__ import annotations
 
 import threading
-import time
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
-from acme_amd import core
+from acme_amd.agents import _learner
 from acme_amd.native import NativeIMPALA
 from acme_amd.utils import counting, loggers
-
-
-def _state_parts(core_state):
-    if isinstance(core_state, dict):
-        return core_state["hidden"], core_state["cell"]
-    hidden, cell = core_state
-    return hidden, cell
 
 
 def _policy_engine(net: NativeIMPALA, rows: int) -> None:
@@ -42,7 +34,26 @@ def _policy_engine(net: NativeIMPALA, rows: int) -> None:
         net.set_policy_planes(True)
 
 
-class IMPALALearner(core.Learner, core.Saveable):
+def _actor_networks(learner: "IMPALALearner", rows: int) -> List[NativeIMPALA]:
+    """Two policy-only networks of `rows` rows bound to the learner's two parameter snapshots
+    (actor_policy, pipelined_policy)."""
+    n = learner.native
+    learner._ensure_snapshots()  # noqa: SLF001
+    nets = [NativeIMPALA(num_actions=n.num_actions, max_batch=rows, max_sequence_length=2,
+                         torso=n.torso, obs_dim=n.obs_dim, lstm_size=n.lstm_size,
+                         head_size=learner._network.head_size,  # noqa: SLF001
+                         device=n.device, shared_params=buf)
+            for buf in learner._snap_buf]  # noqa: SLF001
+    for net in nets:
+        _policy_engine(net, rows)
+    return nets
+
+
+class IMPALALearner(_learner.PlaneLearner):
+
+    _algorithm = "IMPALA"
+    _skip_causes = "skipped (f16 plane overflow or LSTM unroll timeout)"
+    _has_target = False
 
     def __init__(self, environment_spec, network, dataset, learning_rate: float,
                  discount: float = 0.99, entropy_cost: float = 0., baseline_cost: float = 1.,
@@ -52,12 +63,10 @@ class IMPALALearner(core.Learner, core.Saveable):
                  logger: Optional[loggers.Logger] = None, batch_size: Optional[int] = None,
                  sequence_length: Optional[int] = None, seed: int = 0, device=None,
                  semantics: str = "tf", adam=None, on_plane_overflow: str = "skip"):
-        if on_plane_overflow not in ("skip", "raise"):
-            raise ValueError("on_plane_overflow must be 'skip' or 'raise'")
-        self._on_overflow = on_plane_overflow
-        self._skips_seen = 0
+        self._init_guard(on_plane_overflow)
         self._env_spec = environment_spec
         self._network = network
+        self._obs_dtype = _learner.obs_dtype(network)
         self._iterator = iter(dataset)
         B = batch_size or getattr(dataset, "batch_size", None) or 16
         T = sequence_length or getattr(dataset, "sequence_length", None) or 20
@@ -70,68 +79,31 @@ class IMPALALearner(core.Learner, core.Saveable):
             device=device, **({} if adam is None else dict(
                 adam_beta1=adam.beta1, adam_beta2=adam.beta2, adam_epsilon=adam.epsilon)))
         self._native.set_params(network.init(seed))
-        self._counter = counter or counting.Counter()
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=1.)
-        self._timestamp = None
+        self._init_bookkeeping(counter, logger)
         m = self._native.metrics
         self._metric_views = {"loss": m[0], "critic_loss": m[1], "entropy_loss": m[2],
                               "policy_gradient_loss": m[3]}
         # Parameter snapshots for actor networks (actor_policy): allocated on first use.
         self._snap = None
 
-    def _check_guard(self) -> int:
-        n = self._native.skipped_steps  # pinned host word: no synchronisation
-        if n != self._skips_seen:
-            self._skips_seen = n
-            if self._on_overflow == "raise":
-                raise FloatingPointError(f"IMPALA learner: {n} step(s) skipped (f16 plane "
-                                         "overflow or LSTM unroll timeout)")
-            self._native.params_changed()
-        return n
-
     def step(self):
         skipped = self._check_guard()
-        sample = next(self._iterator)
-        data = sample.data
-        obs = data.observation
-        if not hasattr(obs, "observation"):
-            raise ValueError("IMPALAAtariNetwork takes OAR observations "
-                             "(wrap the environment in ObservationActionRewardWrapper)")
-        dt = torch.uint8 if self._network.torso == "atari" else torch.float32
-        c = lambda x, t: x.to(t).contiguous()  # noqa: E731
-        B, T = int(data.action.shape[0]), int(data.action.shape[1])
-        hidden, cell = _state_parts(data.extras["core_state"])
-        self._native.step(c(obs.observation.reshape((B, T, -1)) if dt == torch.float32
-                            else obs.observation, dt),
-                          c(obs.action.reshape(B, T), torch.int32),
-                          c(obs.reward.reshape(B, T), torch.float32),
-                          c(data.action.reshape(B, T), torch.int32),
-                          c(data.reward.reshape(B, T), torch.float32),
-                          c(data.discount.reshape(B, T), torch.float32),
-                          c(data.extras["logits"], torch.float32),
-                          hidden.to(torch.float32)[:, 0], cell.to(torch.float32)[:, 0])
+        data = next(self._iterator).data
+        _learner.check_oar(data.observation, "IMPALAAtariNetwork")
+        self._native.step(*_learner.sequence_batch(data, self._obs_dtype),
+                          data.extras["logits"].to(torch.float32).contiguous(),
+                          *_learner.initial_core_state(data.extras))
         if self._snap is not None:
             self._publish_snapshot()
-        now = time.time()
-        elapsed = now - self._timestamp if self._timestamp else 0
-        self._timestamp = now
-        result = dict(self._metric_views)
-        if skipped:
-            result["skipped_steps"] = skipped
-        result.update(self._counter.increment(steps=1, walltime=elapsed))
-        self._logger.write(result)
+        self._finish_step(dict(self._metric_views), skipped)
 
     def policy_step(self, observation, prev_action, prev_reward, hidden, cell):
         """Batched network step for actors (numpy in, numpy out)."""
         n = self._native
-        dt = torch.uint8 if self._network.torso == "atari" else torch.float32
-        dev = n.device
-        t = lambda x, d: torch.as_tensor(np.asarray(x)).to(dev, d)  # noqa: E731
-        rows = int(np.asarray(prev_action).shape[0])
-        lg, v, h, c = n.policy_step(t(observation, dt).reshape(rows, -1),
-                                    t(prev_action, torch.int32), t(prev_reward, torch.float32),
-                                    t(hidden, torch.float32), t(cell, torch.float32))
-        return lg.cpu().numpy(), v.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy()
+        out = n.policy_step(*_learner.acting_inputs(
+            _learner.to_device(n.device), self._obs_dtype, observation, prev_action, prev_reward,
+            hidden, cell))
+        return tuple(x.cpu().numpy() for x in out)
 
     # -- actor-side parameter snapshots (the reference's VariableClient hands actors a whole
     # set of weights; an actor forward reading the learner's buffer while Adam rewrites it
@@ -170,35 +142,24 @@ class IMPALALearner(core.Learner, core.Saveable):
         published snapshot, a whole set of weights, as a VariableClient refreshed every
         step would)."""
         n = self._native
-        self._ensure_snapshots()
-        nets = [NativeIMPALA(num_actions=n.num_actions, max_batch=int(max_rows),
-                             max_sequence_length=2, torso=n.torso, obs_dim=n.obs_dim,
-                             lstm_size=n.lstm_size, head_size=self._network.head_size,
-                             device=n.device, shared_params=buf) for buf in self._snap_buf]
-        for net in nets:
-            _policy_engine(net, max_rows)
+        nets = _actor_networks(self, int(max_rows))
         stream = torch.cuda.Stream(device=n.device)
-        dt = torch.uint8 if self._network.torso == "atari" else torch.float32
-        dev = n.device
+        convert = _learner.to_device(n.device, non_blocking=True)
 
         def step(observation, prev_action, prev_reward, hidden, cell):
-            t = lambda x, d: torch.as_tensor(np.asarray(x)).to(dev, d, non_blocking=True)  # noqa
-            rows = int(np.asarray(prev_action).shape[0])
             with self._snap_lock:
                 j = self._snap
                 stream.wait_event(self._snap_ready[j])
             with torch.cuda.stream(stream):
-                lg, v, h, c = nets[j].policy_step(t(observation, dt).reshape(rows, -1),
-                                                  t(prev_action, torch.int32),
-                                                  t(prev_reward, torch.float32),
-                                                  t(hidden, torch.float32),
-                                                  t(cell, torch.float32), stream=stream)
+                out = nets[j].policy_step(*_learner.acting_inputs(
+                    convert, self._obs_dtype, observation, prev_action, prev_reward, hidden,
+                    cell), stream=stream)
                 done = torch.cuda.Event()
                 done.record(stream)
                 with self._snap_lock:
                     self._snap_reads[j][id(stream)] = done  # later reads on a stream wait
                                                             # for the earlier ones
-                out = [x.cpu().numpy() for x in (lg, v, h, c)]
+                out = [x.cpu().numpy() for x in out]
             return tuple(out)
 
         step.native = nets  # keeps the networks alive with the closure
@@ -214,37 +175,8 @@ class IMPALALearner(core.Learner, core.Saveable):
     def get_variables(self, names: List[str]) -> List[Dict[str, np.ndarray]]:
         return [self._native.get_params("params")]
 
-    @property
-    def native(self) -> NativeIMPALA:
-        return self._native
-
-    @property
-    def num_steps(self) -> int:
-        return self._native.num_steps
-
-    @property
-    def state(self) -> Dict:
-        return self.save()
-
-    def save(self) -> Dict:
-        n = self._native
-        return {"network": n.get_params("params"),
-                "optimizer": {"m": n.get_params("m"), "v": n.get_params("v"),
-                              "step": n.applied_steps},
-                "num_steps": n.num_steps,
-                # f16 plane scales: a resumed run is bit-identical to an uninterrupted one.
-                "plane_scales": n.scale_state()}
-
     def restore(self, state: Dict):
-        n = self._native
-        n.set_params(state["network"])
-        for buf, src in ((n.m, state["optimizer"]["m"]), (n.v, state["optimizer"]["v"])):
-            for k, t in n.views(buf).items():
-                t.copy_(torch.as_tensor(np.asarray(src[k], np.float32)).view(t.shape))
-        n.num_steps = int(state["num_steps"])
-        n.applied_steps = int(state["optimizer"].get("step", state["num_steps"]))
-        if "plane_scales" in state:
-            n.set_scale_state(state["plane_scales"])
+        super().restore(state)
         if self._snap is not None:  # actors act with the restored weights from now on
             self._publish_snapshot()
 
@@ -257,17 +189,9 @@ class _PipelinedPolicy:
     (straight from page-locked memory when the caller has it there)."""
 
     def __init__(self, learner: "IMPALALearner", rows: int):
-        n = learner._native  # noqa: SLF001
-        learner._ensure_snapshots()  # noqa: SLF001
+        n = learner.native
         self._l = learner
-        self._nets = [NativeIMPALA(num_actions=n.num_actions, max_batch=rows,
-                                   max_sequence_length=2, torso=n.torso, obs_dim=n.obs_dim,
-                                   lstm_size=n.lstm_size,
-                                   head_size=learner._network.head_size,  # noqa: SLF001
-                                   device=n.device, shared_params=buf)
-                      for buf in learner._snap_buf]  # noqa: SLF001
-        for net in self._nets:
-            _policy_engine(net, rows)
+        self._nets = _actor_networks(learner, rows)
         try:  # the actors' policy ahead of the learner's kernels where both are queued
             self._stream = torch.cuda.Stream(device=n.device, priority=-1)
         except (RuntimeError, TypeError):
@@ -275,7 +199,7 @@ class _PipelinedPolicy:
         A, H, dev = n.num_actions, n.lstm_size, n.device
         net = learner._network  # noqa: SLF001
         F = 84 * 84 * 4 if net.torso == "atari" else net.obs_dim
-        odt = torch.uint8 if net.torso == "atari" else torch.float32
+        odt = _learner.obs_dtype(net)
         self._rows, self._A, self._H = rows, A, H
         self._pin_obs = torch.empty((rows, F), dtype=odt, pin_memory=True)
         self._dev_obs = torch.empty((rows, F), dtype=odt, device=dev)

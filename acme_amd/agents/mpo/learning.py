@@ -18,7 +18,6 @@ moments and `get_params` cover them.  `dual_optimizer` gives the duals' learning
 from __future__ import annotations
 
 import dataclasses
-import time
 from typing import Dict, Optional
 
 import numpy as np
@@ -97,25 +96,17 @@ class MPOLearner(D4PGLearner):
             seed=seed, device=device, **dataclasses.asdict(loss))
         # The duals keep their init_log_* values.
         self._init_params(target_policy_network, target_critic_network, seed)
-        self._init_bookkeeping(counter, logger, checkpoint)
+        self._init_bookkeeping(counter, logger)
 
     def step(self):
-        sample = next(self._iterator)
-        o_tm1, a_tm1, r_t, d_t, o_t = sample.data[:5]
-        B = int(r_t.shape[0])
-        f = lambda x: x.reshape(B, -1).float().contiguous()  # noqa: E731
+        self._native_step()
         n = self._native
-        n.step(f(o_tm1), f(a_tm1), f(r_t).reshape(B), f(d_t).reshape(B), f(o_t))
-        now = time.time()
-        elapsed = now - self._timestamp if self._timestamp else 0
-        self._timestamp = now
         result: Dict = {"critic_loss": n.critic_loss, "policy_loss": n.policy_loss}
         for name in n.stat_names:  # the reference's fetches.update(policy_stats)
             if name != "penalty_kl_q_rel" or self._policy_loss_module.action_penalization:
                 result[name] = n.stat(name)
         result["kl_mean_rel"], result["kl_stddev_rel"] = n.kl_mean_rel, n.kl_stddev_rel
-        result.update(self._counter.increment(steps=1, walltime=elapsed))
-        self._logger.write(result)
+        self._finish_step(result)
 
     def policy_distribution(self, observations, use_target: bool = False):
         """(mean, stddev) of the policy's diagonal Gaussian as host arrays."""

@@ -18,23 +18,15 @@ reference takes Sonnet RNN cores); the target starts from its own initialisation
 
 from __future__ import annotations
 
-import time
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import numpy as np
 import torch
 
-from acme_amd import core
 from acme_amd.adders import reverb as adders
+from acme_amd.agents import _learner
 from acme_amd.native import NativeR2D2
 from acme_amd.utils import counting, loggers
-
-
-def _state_parts(core_state):
-    if isinstance(core_state, dict):
-        return core_state["hidden"], core_state["cell"]
-    hidden, cell = core_state
-    return hidden, cell
 
 
 class R2D2Policy:
@@ -52,7 +44,8 @@ class R2D2Policy:
         self.epsilon, self.seed = float(epsilon), int(seed)
         self.calls = 0  # the next call's step counter
         dev, H = native.device, native.lstm_size
-        self._dt = torch.uint8 if network.torso == "atari" else torch.float32
+        self._dt = _learner.obs_dtype(network)
+        self._convert = _learner.to_device(dev)
         self._h = torch.zeros(1, H, dtype=torch.float32, device=dev)
         self._c = torch.zeros(1, H, dtype=torch.float32, device=dev)
         self._action = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -67,14 +60,11 @@ class R2D2Policy:
         (action, the LSTMState [1, H] that went into the step, or None without
         store_state)."""
         from acme_amd.networks import LSTMState
-        if not hasattr(observation, "observation"):
-            raise ValueError("R2D2AtariNetwork takes OAR observations "
-                             "(wrap the environment in ObservationActionRewardWrapper)")
-        n, dev = self._native, self._native.device
-        t = lambda x, d: torch.as_tensor(np.asarray(x)).to(dev, d)  # noqa: E731
+        _learner.check_oar(observation, "R2D2AtariNetwork")
+        n, t = self._native, self._convert
         prev = None
         if state is not None:
-            hidden, cell = _state_parts(state)
+            hidden, cell = _learner.state_parts(state)
             self._h.copy_(t(hidden, torch.float32).reshape(self._h.shape))
             self._c.copy_(t(cell, torch.float32).reshape(self._c.shape))
             if store_state:
@@ -90,7 +80,13 @@ class R2D2Policy:
         return np.int32(self._action.item()), prev
 
 
-class R2D2Learner(core.Learner, core.Saveable):
+class R2D2Learner(_learner.PlaneLearner):
+
+    _algorithm = "R2D2"
+    _skip_causes = ("skipped on f16 plane overflow or an LSTM timeout (their updates were not "
+                    "applied)")
+    _counter_args = (None, "learner")
+    _log_time_delta = 100.
 
     def __init__(self, environment_spec, network, target_network, burn_in_length: int,
                  sequence_length: int, dataset, reverb_client=None,
@@ -105,11 +101,10 @@ class R2D2Learner(core.Learner, core.Saveable):
         # A step whose f16 planes overflowed (or whose LSTM unroll timed out) is skipped on
         # the device and the scales recalibrated ("skip", as IMPALA), or raises
         # FloatingPointError at the next step() ("raise").
-        if on_plane_overflow not in ("skip", "raise"):
-            raise ValueError("on_plane_overflow must be 'skip' or 'raise'")
-        self._on_overflow = on_plane_overflow
+        self._init_guard(on_plane_overflow)
         self._env_spec = environment_spec
         self._network = network
+        self._obs_dtype = _learner.obs_dtype(network)
         self._iterator = iter(dataset)
         self._client = reverb_client
         self._burn_in = int(burn_in_length)
@@ -126,61 +121,28 @@ class R2D2Learner(core.Learner, core.Saveable):
         self._native.set_params(network.init(seed),
                                 target_network.init(seed + 1 if target_seed is None
                                                     else target_seed))
-        self._skips_seen = 0
-        self._counter = counter or counting.Counter(None, "learner")
-        self._logger = logger or loggers.TerminalLogger("learner", time_delta=100.)
-        self._timestamp = None
-
-    def _check_guard(self) -> int:
-        n = self._native.skipped_steps  # pinned host word: no synchronisation
-        if n != self._skips_seen:
-            self._skips_seen = n
-            if self._on_overflow == "raise":
-                raise FloatingPointError(
-                    f"R2D2 learner: {n} step(s) skipped on f16 plane overflow or an LSTM "
-                    "timeout (their updates were not applied)")
-            self._native.params_changed()  # recalibrate the plane scales before the next step
-        return n
+        self._init_bookkeeping(counter, logger)
 
     def step(self):
         skipped = self._check_guard()
         sample = next(self._iterator)
         data = sample.data
-        obs = data.observation
-        if not hasattr(obs, "observation"):
-            raise ValueError("R2D2AtariNetwork takes OAR observations "
-                             "(wrap the environment in ObservationActionRewardWrapper)")
+        _learner.check_oar(data.observation, "R2D2AtariNetwork")
         n = self._native
-        dt = torch.uint8 if self._network.torso == "atari" else torch.float32
-        c = lambda x, t: x.to(t).contiguous()  # noqa: E731
-        B, T = int(data.action.shape[0]), int(data.action.shape[1])
+        B = int(data.action.shape[0])
         h0 = c0 = None
         if n.store_lstm_state:
-            hidden, cell = _state_parts(data.extras["core_state"])
-            h0, c0 = hidden.to(torch.float32)[:, 0], cell.to(torch.float32)[:, 0]
+            h0, c0 = _learner.initial_core_state(data.extras)
         keys, probs = sample.info.key, sample.info.probability
         if probs.dim() == 2:  # per-step info of a sequence item: the item's own
             keys, probs = keys[:, 0], probs[:, 0]
-        n.step(c(obs.observation.reshape((B, T, -1)) if dt == torch.float32
-                 else obs.observation, dt),
-               c(obs.action.reshape(B, T), torch.int32),
-               c(obs.reward.reshape(B, T), torch.float32),
-               c(data.action.reshape(B, T), torch.int32),
-               c(data.reward.reshape(B, T), torch.float32),
-               c(data.discount.reshape(B, T), torch.float32),
-               c(probs, torch.float64), h0, c0)
+        n.step(*_learner.sequence_batch(data, self._obs_dtype),
+               probs.to(torch.float64).contiguous(), h0, c0)
         if self._client is not None:  # learning.py:195-198; a skipped step writes none
             kw = {"skip_word": n.skip_word} if n.skip_word else {}
             self._client.update_priorities(table=adders.DEFAULT_PRIORITY_TABLE, keys=keys,
                                            priorities=n.priorities[:B], **kw)
-        now = time.time()
-        elapsed = now - self._timestamp if self._timestamp else 0
-        self._timestamp = now
-        result = {"loss": n.loss[0]}
-        if skipped:
-            result["skipped_steps"] = skipped
-        result.update(self._counter.increment(steps=1, walltime=elapsed))
-        self._logger.write(result)
+        self._finish_step({"loss": n.loss[0]}, skipped)
 
     # ------------------------------------------------------------------ acting
     def q_step(self, observation, prev_action, prev_reward, hidden, cell, *,
@@ -188,16 +150,10 @@ class R2D2Learner(core.Learner, core.Saveable):
         """Batched network step for actors (numpy in, numpy out): (q [rows, A], actions
         [rows], hidden, cell), the actions epsilon-greedy draws from (seed, step, row)."""
         n = self._native
-        dt = torch.uint8 if self._network.torso == "atari" else torch.float32
-        dev = n.device
-        t = lambda x, d: torch.as_tensor(np.asarray(x)).to(dev, d)  # noqa: E731
-        rows = int(np.asarray(prev_action).shape[0])
-        q, a, h, c = n.q_step(t(observation, dt).reshape(rows, -1), t(prev_action, torch.int32),
-                              t(prev_reward, torch.float32),
-                              t(hidden, torch.float32).contiguous(),
-                              t(cell, torch.float32).contiguous(), epsilon=epsilon, seed=seed,
-                              step=step, use_target=use_target)
-        return q.cpu().numpy(), a.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy()
+        out = n.q_step(*_learner.acting_inputs(
+            _learner.to_device(n.device), self._obs_dtype, observation, prev_action, prev_reward,
+            hidden, cell), epsilon=epsilon, seed=seed, step=step, use_target=use_target)
+        return tuple(x.cpu().numpy() for x in out)
 
     def make_policy(self, epsilon: float, seed: int = 0) -> "R2D2Policy":
         """The epsilon-greedy recurrent policy of one actor on this learner's online network
@@ -209,40 +165,3 @@ class R2D2Learner(core.Learner, core.Saveable):
         # As the TF learner (learning.py:216-217): one collection, names ignored.
         p = self._native.get_params("params")
         return [[p[k] for k in sorted(p)]]
-
-    @property
-    def num_steps(self) -> int:
-        return self._native.num_steps
-
-    @property
-    def native(self) -> NativeR2D2:
-        return self._native
-
-    @property
-    def state(self) -> Dict:
-        return self.save()
-
-    def save(self) -> Dict:
-        n = self._native
-        # The DQN / IMPALA learners' format: Adam's t (the updates applied) as
-        # optimizer["step"], num_steps the step() calls, and the f16 plane scales, so a
-        # resumed run is bit-identical to an uninterrupted one.
-        return {"network": n.get_params("params"), "target_network": n.get_params("target"),
-                "optimizer": {"m": n.get_params("m"), "v": n.get_params("v"),
-                              "step": n.guard_state()["applied"]},
-                "num_steps": n.num_steps,
-                "plane_scales": n.scale_state()}
-
-    def restore(self, state: Dict):
-        n = self._native
-        n.set_params(state["network"], state["target_network"])
-        for buf, src in ((n.m, state["optimizer"]["m"]), (n.v, state["optimizer"]["v"])):
-            for k, t in n.views(buf).items():
-                t.copy_(torch.as_tensor(np.asarray(src[k], np.float32)).view(t.shape))
-        n.params_changed()
-        if "plane_scales" in state:
-            n.set_scale_state(state["plane_scales"])
-        n.num_steps = int(state["num_steps"])
-        opt = state["optimizer"]
-        # round-4 checkpoints: "step" = num_steps, the applied count in "applied_steps"
-        n.set_applied_steps(int(opt.get("applied_steps", opt.get("step", state["num_steps"]))))

@@ -538,10 +538,22 @@ class _NativeLearner:
         b.batch, b.sequence_length = B, T
         return b
 
+    def _acting_outputs(self, rows: int, second_dtype) -> List[torch.Tensor]:
+        """The outputs of a recurrent learner's network step for `rows` actors: [rows, A],
+        [rows] of second_dtype (values or actions) and the core state [rows, H] twice."""
+        A, H, dev = self.num_actions, self.lstm_size, self.device
+        return [torch.empty(rows, A, dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=second_dtype, device=dev),
+                torch.empty(rows, H, dtype=torch.float32, device=dev),
+                torch.empty(rows, H, dtype=torch.float32, device=dev)]
+
 
 class _PlaneState:
     """Plane-scale and step-guard state of the learners on the f16 plane engine (NativeDQN,
     NativeIMPALA, NativeR2D2), beside _NativeLearner."""
+
+    # The words <prefix>_guard_state writes, in order.
+    _guard_fields = ("applied", "skipped", "last_skipped")
 
     def params_changed(self) -> None:
         """Tells the learner its params / target buffers were written from outside (its
@@ -572,21 +584,47 @@ class _PlaneState:
         finished (no synchronisation)."""
         return int(self._fn("skipped_steps")(self._h))
 
+    def guard_state(self) -> Dict[str, int]:
+        """The step guard's counters under the names in _guard_fields (synchronises the
+        device)."""
+        a = (ctypes.c_int64 * len(self._guard_fields))()
+        check(self._fn("guard_state")(self._h, a), f"{self._tag} guard_state")
+        return dict(zip(self._guard_fields, (int(x) for x in a)))
 
-def _plane_overflow(self, reset: bool = False) -> bool:
-    """True if a plane tensor exceeded f16's range at its scale since the last reset
-    (synchronises the device).  NativeDQN's and NativeIMPALA's plane_overflow."""
-    v = ctypes.c_int32(0)
-    check(self._fn("plane_overflow")(self._h, ctypes.byref(v), int(reset)),
-          f"{self._tag} plane_overflow")
-    return bool(v.value)
+    @property
+    def applied_steps(self) -> int:
+        """Updates applied (Adam's t after the last step); synchronises."""
+        return self.guard_state()["applied"]
+
+    @applied_steps.setter
+    def applied_steps(self, n: int) -> None:
+        check(self._fn("set_applied_steps")(self._h, int(n)), f"{self._tag} set_applied_steps")
+
+    @property
+    def skip_word(self) -> Optional[int]:
+        """Device address of the word an after-step priority update is gated on (set while
+        the last step was skipped), or None: no plane path, or a learner that writes no
+        priorities (IMPALA has no such export)."""
+        return None
 
 
-class NativeDQN(_PlaneState, _NativeLearner):
+class _PlaneOverflow:
+    """plane_overflow of the learners that export it (NativeDQN, NativeIMPALA)."""
+
+    def plane_overflow(self, reset: bool = False) -> bool:
+        """True if a plane tensor exceeded f16's range at its scale since the last reset
+        (synchronises the device)."""
+        v = ctypes.c_int32(0)
+        check(self._fn("plane_overflow")(self._h, ctypes.byref(v), int(reset)),
+              f"{self._tag} plane_overflow")
+        return bool(v.value)
+
+
+class NativeDQN(_PlaneOverflow, _PlaneState, _NativeLearner):
     """acme_dqn learner + its flat buffers."""
 
     _prefix, _tag = "acme_dqn", "dqn"
-    plane_overflow = _plane_overflow
+    _guard_fields = _PlaneState._guard_fields + ("q_values_overflowed",)
 
     def __init__(self, *, network: str, num_actions: int, max_batch: int, obs_dtype: str,
                  obs_dim: int = 0, hidden: Sequence[int] = (), discount: float = 0.99,
@@ -635,12 +673,11 @@ class NativeDQN(_PlaneState, _NativeLearner):
     def guard_state(self) -> Dict[str, int]:
         """{applied, skipped, last_skipped, q_values_overflowed, verdict_timeouts} (synchronises
         the device)."""
-        a = (ctypes.c_int64 * 4)()
-        check(lib().acme_dqn_guard_state(self._h, a), "dqn guard_state")
+        g = super().guard_state()
         t = ctypes.c_int64()
         check(lib().acme_dqn_verdict_timeouts(self._h, ctypes.byref(t)), "dqn verdict_timeouts")
-        return dict(applied=int(a[0]), skipped=int(a[1]), last_skipped=int(a[2]),
-                    q_values_overflowed=int(a[3]), verdict_timeouts=int(t.value))
+        g["verdict_timeouts"] = int(t.value)
+        return g
 
     def update_rider_launches(self) -> int:
         """Steps whose priority write-back rode conv1's weight-gradient launch."""
@@ -651,17 +688,7 @@ class NativeDQN(_PlaneState, _NativeLearner):
         return int(lib().acme_dqn_fused_x2_launches(self._h))
 
     @property
-    def applied_steps(self) -> int:
-        """Updates applied (Adam's t after the last step); synchronises."""
-        return self.guard_state()["applied"]
-
-    @applied_steps.setter
-    def applied_steps(self, n: int) -> None:
-        check(lib().acme_dqn_set_applied_steps(self._h, int(n)), "dqn set_applied_steps")
-
-    @property
     def skip_word(self) -> Optional[int]:
-        """Device address of the word an after-step priority update is gated on."""
         p = ctypes.c_void_p()
         check(lib().acme_dqn_skip_word(self._h, ctypes.byref(p)), "dqn skip_word")
         return p.value
@@ -1098,11 +1125,11 @@ class NativeDMPO(NativeMPO):
         return (np.float64(self.vmin) + np.arange(self.num_atoms) * step).astype(np.float32)
 
 
-class NativeIMPALA(_PlaneState, _NativeLearner):
+class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):
     """acme_impala learner + its flat buffers (no target network)."""
 
     _prefix, _tag, _has_target = "acme_impala", "impala", False
-    plane_overflow = _plane_overflow
+    _guard_fields = _PlaneState._guard_fields + ("lstm_timeouts",)
 
     def __init__(self, *, num_actions: int, max_batch: int, max_sequence_length: int,
                  torso: str = "atari", obs_dim: int = 0, lstm_size: int = 256,
@@ -1140,21 +1167,6 @@ class NativeIMPALA(_PlaneState, _NativeLearner):
     def set_params(self, params: Dict[str, np.ndarray]) -> None:
         super().set_params(params)
 
-    def guard_state(self) -> Dict[str, int]:
-        """{applied, skipped, last_skipped, lstm_timeouts} (synchronises the device)."""
-        a = (ctypes.c_int64 * 4)()
-        check(lib().acme_impala_guard_state(self._h, a), "impala guard_state")
-        return dict(applied=int(a[0]), skipped=int(a[1]), last_skipped=int(a[2]),
-                    lstm_timeouts=int(a[3]))
-
-    @property
-    def applied_steps(self) -> int:
-        return self.guard_state()["applied"]
-
-    @applied_steps.setter
-    def applied_steps(self, n: int) -> None:
-        check(lib().acme_impala_set_applied_steps(self._h, int(n)), "impala set_applied_steps")
-
     def set_policy_planes(self, on: bool = True) -> None:
         """Policy steps (>= 64 rows, Atari torso) on the plane engine: for actor-side networks
         that only run policy steps (acme_impala_set_policy_planes)."""
@@ -1177,12 +1189,8 @@ class NativeIMPALA(_PlaneState, _NativeLearner):
         """One network step for `rows` actors; returns (logits, values, h, c) (into `out`,
         four contiguous device tensors of those shapes, when given)."""
         rows = int(prev_action.shape[0])
-        A, H = self.num_actions, self.lstm_size
         if out is None:
-            out = [torch.empty(rows, A, dtype=torch.float32, device=self.device),
-                   torch.empty(rows, dtype=torch.float32, device=self.device),
-                   torch.empty(rows, H, dtype=torch.float32, device=self.device),
-                   torch.empty(rows, H, dtype=torch.float32, device=self.device)]
+            out = self._acting_outputs(rows, torch.float32)
         check(lib().acme_impala_policy_step(
             self._h, ptr(obs.contiguous()), ptr(prev_action.contiguous()),
             ptr(prev_reward.contiguous()), ptr(h.contiguous()), ptr(c.contiguous()), rows,
@@ -1242,18 +1250,8 @@ class NativeR2D2(_PlaneState, _NativeLearner):
     def set_params(self, params: Dict[str, np.ndarray], target: Dict[str, np.ndarray]) -> None:
         super().set_params(params, target)
 
-    def guard_state(self) -> Dict[str, int]:
-        """{applied, skipped, last_skipped} (synchronises the device)."""
-        a = (ctypes.c_int64 * 3)()
-        check(lib().acme_r2d2_guard_state(self._h, a), "r2d2 guard_state")
-        return dict(applied=int(a[0]), skipped=int(a[1]), last_skipped=int(a[2]))
-
-    def set_applied_steps(self, n: int) -> None:
-        check(lib().acme_r2d2_set_applied_steps(self._h, int(n)), "r2d2 set_applied_steps")
-
     @property
     def skip_word(self) -> Optional[int]:
-        """Device address of the step's skip word (gates the priority write-back), or None."""
         return lib().acme_r2d2_skip_word(self._h) or None
 
     def set_lstm_unroll(self, per_step: bool) -> None:
@@ -1288,7 +1286,7 @@ class NativeR2D2(_PlaneState, _NativeLearner):
         step, row).  out: four device tensors (or None to skip an output) to write into; the
         state outputs may be h and c themselves."""
         rows = int(prev_action.shape[0])
-        A, H = self.num_actions, self.lstm_size
+        H = self.lstm_size
         for name, t in (("h", h), ("c", c)):
             if (t.dtype != torch.float32 or tuple(t.shape) != (rows, H) or t.stride(1) != 1
                     or not t.is_cuda):
@@ -1297,10 +1295,7 @@ class NativeR2D2(_PlaneState, _NativeLearner):
         if h.stride(0) != c.stride(0):
             raise ValueError("h and c must share a row stride")
         if out is None:
-            out = [torch.empty(rows, A, dtype=torch.float32, device=self.device),
-                   torch.empty(rows, dtype=torch.int32, device=self.device),
-                   torch.empty(rows, H, dtype=torch.float32, device=self.device),
-                   torch.empty(rows, H, dtype=torch.float32, device=self.device)]
+            out = self._acting_outputs(rows, torch.int32)
         for o in out[2:]:
             if o is not None and not o.is_contiguous():
                 raise ValueError("the state outputs must be contiguous [rows, H] tensors")

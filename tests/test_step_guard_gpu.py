@@ -343,6 +343,53 @@ def test_learner_reissues_skipped_step(dataset):
     assert not np.array_equal(raw_got[:64 * len(batches)], np.ones(64 * len(batches)))
 
 
+@pytest.mark.parametrize("holds", [None, 2])
+def test_learner_drops_inputs_event_for_copied_batches(holds):
+    """The dataset's ready event covers the dataset's own tensors.  A learner that copies the
+    batches it may re-issue (an iterator that holds fewer than two batches: ADVICE r6) hands
+    the step copies made on its own stream, so it must pass no event: the step's side stream
+    would otherwise read a copy after waiting for the event only.  An iterator that holds
+    its last two batches gets its event passed through."""
+    from acme_amd import _lib
+    from acme_amd.agents.dqn import DQNLearner
+    from acme_amd.networks import DQNAtariNetwork
+    from acme_amd.utils import loggers
+    B, A = 4, 18
+    net = DQNAtariNetwork(A)
+    event = _lib.OrderEvent()
+
+    class _WithEvent:
+        last_inputs_event = event
+
+        def __init__(self, sample):
+            self.sample, self.batch_size = sample, B
+            if holds is not None:
+                self.holds_last_batches = holds
+
+        def __iter__(self):
+            return self
+
+        def __next__(self):
+            event.record()
+            return self.sample
+
+    lr = DQNLearner(net, net, discount=0.99, importance_sampling_exponent=0.2,
+                    learning_rate=1e-3, target_update_period=2,
+                    dataset=_WithEvent(_sample(_batch(np.random.default_rng(9), B, A), 0)),
+                    logger=loggers.NoOpLogger(), on_plane_overflow="reissue")
+    assert lr._copy_held == (holds is None)  # noqa: SLF001
+    seen, step = [], lr.native.step
+
+    def recording_step(*batch, **kw):
+        seen.append(kw["inputs_event"])
+        return step(*batch, **kw)
+
+    lr.native.step = recording_step
+    lr.step()
+    lr.save()  # settles
+    assert seen == [None if holds is None else event]
+
+
 def _rel(a, b, base):
     num = sum(float(np.sum((a[k].astype(np.float64) - b[k]) ** 2)) for k in a)
     den = sum(float(np.sum((b[k] - base[k].astype(np.float64)) ** 2)) for k in a)
