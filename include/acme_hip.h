@@ -888,7 +888,9 @@ typedef struct acme_impala_config {
   int32_t num_actions;          /* <= 63 */
   int32_t max_batch;            /* sequences per step (B) */
   int32_t max_sequence_length;  /* T */
-  int32_t lstm_size;            /* multiple of 8, max_batch * (lstm_size + 32) <= 12288 */
+  int32_t lstm_size;            /* multiple of 8; (max_batch + 16) * (lstm_size + 16) <= 12544
+                                   (the per-step LSTM forward's 64 KB of LDS), or lstm_size
+                                   256 with max_batch <= 64 (the one-launch LSTM) */
   int32_t head_size;            /* multiple of 4 */
   float discount, entropy_cost, baseline_cost;
   float max_abs_reward;         /* INFINITY = no reward clipping (learning.py:70-71) */

@@ -106,15 +106,24 @@ def _check_buffers(n, ref, B, A, tag=""):
     _close(n.debug_buffer("norms"), ref["norms"], name=f"norms{tag}")
 
 
-def _run_steps(cfg, max_batch, B, steps, pseed, bseed):
+def _run_steps(cfg, max_batch, B, steps, pseed, bseed, learner=None):
     """`steps` teacher-forced steps against the oracle: after each one the oracle continues
-    from the kernel's parameters and moments, so fp32 drift cannot compound."""
-    n = _native(cfg, max_batch)
+    from the kernel's parameters and moments, so fp32 drift cannot compound.  B: the rows of
+    every step, or a sequence with the rows of each (a learner created once for max_batch,
+    stepped at whatever arrives).  learner: an already created learner to step instead (it
+    starts over: these parameters, zero moments, step 0)."""
+    n = learner if learner is not None else _native(cfg, max_batch)
     params, target = _random_params(cfg, pseed), _random_params(cfg, pseed + 1)
     n.set_params(params, target)
+    if learner is not None:
+        n.m.zero_()
+        n.v.zero_()
+        n.num_steps = 0
+    sizes = [B] * steps if np.isscalar(B) else list(B)
+    assert len(sizes) == steps
     z = {k: np.zeros_like(v) for k, v in params.items()}
     state = dict(params=params, target=target, m=z, v=dict(z), num_steps=0)
-    for s in range(steps):
+    for s, B in enumerate(sizes):
         batch = _batch(cfg, B, bseed + s)
         n.step(*_dev(batch))
         torch.cuda.synchronize()
@@ -131,6 +140,7 @@ def _run_steps(cfg, max_batch, B, steps, pseed, bseed):
             np.testing.assert_array_equal(tgt[k], np.asarray(r, np.float32), err_msg=k)
         state["target"] = tgt
     assert n.num_steps == steps
+    return n
 
 
 def test_tensor_layout_matches_oracle():

@@ -192,18 +192,27 @@ def _check_grads(n, ref):
 
 
 def _run_steps(cfg, B, steps, pseed, bseed, mean_scale=1.0, critic_scale=1.0, params=None,
-               target=None, start=0, batch_fn=_batch, check_branches=True, min_tv=None):
+               target=None, start=0, batch_fn=_batch, check_branches=True, min_tv=None,
+               max_batch=None, learner=None):
     """`steps` teacher-forced steps against the oracle: after each one the oracle continues
     from the kernel's parameters and moments, so fp32 drift cannot compound.  `min_tv`: what
-    _sample_spread of every step's oracle output must reach."""
-    n = _native(cfg, B)
+    _sample_spread of every step's oracle output must reach.  B: the rows of every step, or
+    a sequence with the rows of each; max_batch: the learner's creation (default: the largest
+    step); learner: an already created learner to step instead (it starts over: these
+    parameters, zero moments, step `start`)."""
+    sizes = [B] * steps if np.isscalar(B) else list(B)
+    assert len(sizes) == steps
+    n = learner if learner is not None else _native(cfg, max_batch or max(sizes))
     params = params or _random_params(cfg, pseed, mean_scale, critic_scale)
     target = target or _random_params(cfg, pseed + 1, mean_scale, critic_scale)
     n.set_params(params, target)
+    if learner is not None:
+        n.m.zero_()
+        n.v.zero_()
     n.num_steps = start
     state = _state(params, target, start)
     refs = []
-    for s in range(start, start + steps):
+    for s, B in zip(range(start, start + steps), sizes):
         batch, eps = batch_fn(cfg, B, bseed + s), _eps(cfg, B, bseed + 100 + s)
         if check_branches:
             _assert_projection_branches(cfg, batch)

@@ -214,18 +214,27 @@ def _state(params, target, num_steps=0):
     return dict(params=params, target=target, m=z, v=dict(z), num_steps=num_steps)
 
 
-def _run_steps(cfg, B, steps, pseed, bseed, mean_scale=1.0, params=None, target=None, start=0):
+def _run_steps(cfg, B, steps, pseed, bseed, mean_scale=1.0, params=None, target=None, start=0,
+               max_batch=None, learner=None):
     """`steps` teacher-forced steps against the oracle: after each one the oracle continues
     from the kernel's parameters and moments, so fp32 drift cannot compound.  `start`: the
-    step count to begin at (1: the first step copies no target, whatever the periods)."""
-    n = _native(cfg, B)
+    step count to begin at (1: the first step copies no target, whatever the periods).
+    B: the rows of every step, or a sequence with the rows of each; max_batch: the learner's
+    creation (default: the largest step); learner: an already created learner to step instead
+    (it starts over: these parameters, zero moments, step `start`)."""
+    sizes = [B] * steps if np.isscalar(B) else list(B)
+    assert len(sizes) == steps
+    n = learner if learner is not None else _native(cfg, max_batch or max(sizes))
     params = params or _random_params(cfg, pseed, mean_scale)
     target = target or _random_params(cfg, pseed + 1, mean_scale)
     n.set_params(params, target)
+    if learner is not None:
+        n.m.zero_()
+        n.v.zero_()
     n.num_steps = start
     state = _state(params, target, start)
     refs = []
-    for s in range(start, start + steps):
+    for s, B in zip(range(start, start + steps), sizes):
         batch, eps = _batch(cfg, B, bseed + s), _eps(cfg, B, bseed + 100 + s)
         n.step(*_dev(batch), noise=torch.as_tensor(eps).cuda())
         torch.cuda.synchronize()

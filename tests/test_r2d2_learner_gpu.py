@@ -168,7 +168,7 @@ def _check_step(cfg, n, state, b, copies, errors_rtol=1e-4, k=0):
     # values (teacher-forced): errors, priorities, d loss / d q[a].
     err_tf, _ = O.transformed_loss(cfg, q_k.reshape(L, B, A), tq_k.reshape(L, B, A), b)
     np.testing.assert_array_equal(n.errors.cpu().numpy(), err_tf, err_msg=f"errors {k}")
-    np.testing.assert_array_equal(n.priorities.cpu().numpy(),
+    np.testing.assert_array_equal(n.priorities[:B].cpu().numpy(),
                                   O.compute_priority(err_tf, cfg.max_priority_weight),
                                   err_msg=f"priorities {k}")
     w32 = O.importance_weights(b["probabilities"], cfg.max_replay_size,
@@ -212,28 +212,43 @@ def _check_step(cfg, n, state, b, copies, errors_rtol=1e-4, k=0):
                 num_steps=state["num_steps"] + 1)
 
 
-def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False, errors_rtol=1e-4):
+def _compare(cfg, B, T, seed=0, steps=1, f32_engine=False, errors_rtol=1e-4, maxima=None,
+             learner=None, shapes=None):
     """errors_rtol: the relative bar of the end-to-end errors (1e-4 unless a caller derives
-    another from the float32 oracle's own error at its shape)."""
+    another from the float32 oracle's own error at its shape; a sequence: one per step).
+    maxima: the learner's creation (max_batch, max_sequence_length), default (B, T); learner:
+    an already created learner to step instead (its parameters are set here); shapes: the
+    (B, T) of each step, default (B, T) throughout.  The workspaces are sized for the maxima
+    and every check reads the step's rows alone, laid out with that step's B and T."""
     from acme_amd._lib import lib
-    if f32_engine:
-        lib().acme_tune_set(b"R2P3", 1)  # read at the learner's creation
-    try:
-        n = _native(cfg, B, T)
-    finally:
+    n = learner
+    if n is None:
         if f32_engine:
-            lib().acme_tune_set(b"R2P3", 0)
+            lib().acme_tune_set(b"R2P3", 1)  # read at the learner's creation
+        try:
+            n = _native(cfg, *(maxima or (B, T)))
+        finally:
+            if f32_engine:
+                lib().acme_tune_set(b"R2P3", 0)
     p0, t0 = _params(cfg, 10 + seed), _params(cfg, 20 + seed)
     n.set_params(p0, t0)
+    if learner is not None:  # a used learner starts over: zero moments, step 0
+        n.m.zero_()
+        n.v.zero_()
+        n.num_steps = 0
+        n.applied_steps = 0
     z = {k: np.zeros_like(v) for k, v in p0.items()}
     state = dict(params=p0, target=t0, m=z, v=dict(z), num_steps=0)
+    g0 = n.guard_state()
     for k in range(steps):
-        b = _batch(cfg, B, T, 100 * seed + k)
+        Bk, Tk = shapes[k] if shapes is not None else (B, T)
+        b = _batch(cfg, Bk, Tk, 100 * seed + k)
         _run(n, b)
-        state = _check_step(cfg, n, state, b, k % cfg.target_update_period == 0, errors_rtol, k)
+        rtol = errors_rtol if np.isscalar(errors_rtol) else errors_rtol[k]
+        state = _check_step(cfg, n, state, b, k % cfg.target_update_period == 0, rtol, k)
         assert n.num_steps == k + 1
     g = n.guard_state()
-    assert g["skipped"] == 0 and g["applied"] == steps, g
+    assert g["skipped"] == g0["skipped"] and g["applied"] == g0["applied"] + steps, g
     return n
 
 
