@@ -243,6 +243,12 @@ _SIGS = {
     "acme_demo_store_upload": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_demo_mix": (c_i32, [c_vp, c_f64, c_i32, c_f32, c_u64, c_u64, c_i64,
                               ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_seq_demo_store_create": (c_i32, [c_i64, c_vp, c_i32, c_vp, ctypes.POINTER(c_vp)]),
+    "acme_seq_demo_store_destroy": (c_i32, [c_vp]),
+    "acme_seq_demo_store_upload": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
+    "acme_seq_demo_mix": (c_i32, [c_vp, c_f64, c_i64, c_i64, c_u64, c_u64, c_i64,
+                                  ctypes.POINTER(c_vp), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp]),
     "acme_dqn_num_params": (c_i64, [c_vp]),
     "acme_dqn_plane_overflow": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32]),
     "acme_dqn_verdict_timeouts": (c_i32, [c_vp, ctypes.POINTER(c_i64)]),

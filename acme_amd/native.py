@@ -354,6 +354,75 @@ class NativeDemoStore:
               "demonstration mix")
 
 
+SEQ_DEMO_MAX_FIELDS = 16       # ACME_SEQ_DEMO_MAX_FIELDS
+SEQ_DEMO_MAX_OUT_FIELDS = 32   # ACME_SEQ_DEMO_MAX_OUT_FIELDS
+
+
+class NativeSeqDemoStore:
+    """acme_seq_demo_store: demonstration episodes as K immutable per-step device arrays
+    (csrc/seq_demos.hip).  The constructor checks the layout on the host (no GPU needed);
+    `upload()` puts the packed fields on the device, once; `mix()` overlays the demonstration
+    rows of a drawn batch of sequences (acme_seq_demo_mix)."""
+
+    def __init__(self, offsets: np.ndarray, step_bytes: Sequence[int]):
+        self.offsets = np.ascontiguousarray(offsets, np.int64)
+        self.step_bytes = np.ascontiguousarray(step_bytes, np.int64)
+        self.device = None
+        h = ctypes.c_void_p()
+        check(lib().acme_seq_demo_store_create(len(self.offsets) - 1, self.offsets.ctypes.data,
+                                               len(self.step_bytes), self.step_bytes.ctypes.data,
+                                               ctypes.byref(h)), "sequence demonstration store")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                lib().acme_seq_demo_store_destroy(h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def upload(self, fields: Sequence[np.ndarray], device=None) -> None:
+        """Packed host fields: uint8 [total, step_bytes[f]] each."""
+        _lib.require_gpu()
+        total = int(self.offsets[-1])
+        arrays = [np.ascontiguousarray(a, np.uint8) for a in fields]
+        if len(arrays) != len(self.step_bytes):
+            raise ValueError(f"{len(arrays)} demonstration fields, expected "
+                             f"{len(self.step_bytes)}")
+        for a, sb in zip(arrays, self.step_bytes):
+            if a.nbytes != total * int(sb):
+                raise ValueError(f"demonstration field has {a.nbytes} bytes, expected "
+                                 f"{total * int(sb)}")
+        self.device = torch.device(device or "cuda")
+        ptrs = (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+        with torch.cuda.device(self.device):
+            check(lib().acme_seq_demo_store_upload(self._h, ptrs),
+                  "sequence demonstration store upload")
+
+    def mix(self, ratio: float, period: int, sequence_length: int, seed: int, step: int,
+            batch: int, out_fields, row_bytes: np.ndarray, logical_bytes: np.ndarray, keys: int,
+            probabilities: int, table_size: int, priorities: int, is_demo: int = 0,
+            stream: Optional[int] = None) -> None:
+        """out_fields: a ctypes array of every batch field's device pointer; row_bytes /
+        logical_bytes: int64 arrays of the same length; the other outputs raw device
+        addresses (0: not written); stream: a raw hipStream_t."""
+        check(lib().acme_seq_demo_mix(self._h, float(ratio), int(period), int(sequence_length),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                      int(step) & 0xFFFFFFFFFFFFFFFF, int(batch), out_fields,
+                                      len(out_fields), row_bytes.ctypes.data,
+                                      logical_bytes.ctypes.data, keys or None,
+                                      probabilities or None, table_size or None,
+                                      priorities or None, is_demo or None,
+                                      stream_ptr() if stream is None else stream),
+              "sequence demonstration mix")
+
+
 def _device_array(address: int, count: int, dtype, device) -> torch.Tensor:
     """Copies `count` elements at a raw device address into a new tensor (test helper)."""
     nbytes = count * np.dtype(dtype).itemsize

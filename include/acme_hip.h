@@ -347,6 +347,55 @@ int acme_demo_mix(const acme_demo_store* s, double ratio, int32_t n_step, float 
                   uint64_t* keys, double* probabilities, int64_t* table_size,
                   double* priorities, uint8_t* is_demo, void* stream);
 
+/* Demonstration sequences for sequence tables (R2D3, acme/agents/tf/r2d3/agent.py:99-106,
+ * 163-235): the same overlay for batches of T-step items (SequenceAdder's Step(observation,
+ * action, reward, discount, start_of_episode, extras)).
+ *
+ * Store: E episodes of L_e >= 1 steps each as K per-step field arrays (the flattened leaves
+ * of observation, action, reward, discount, in the table's field order), 1 <= K <=
+ * ACME_SEQ_DEMO_MAX_FIELDS.  Field f is [total][step_bytes[f]] bytes, densely packed (no
+ * per-step padding; step_bytes[f] >= 1 is the logical size of one step's leaf), offsets as
+ * above.  acme_seq_demo_store_create checks and keeps the layout on the host (no device
+ * call); acme_seq_demo_store_upload allocates the device arrays on the current device and
+ * copies the K host arrays fields[0..K-1] into them (synchronous, once; the store is
+ * immutable afterwards). */
+#define ACME_SEQ_DEMO_MAX_FIELDS 16     /* copied per-step fields of a store */
+#define ACME_SEQ_DEMO_MAX_OUT_FIELDS 32 /* all fields of a batch the mix writes */
+typedef struct acme_seq_demo_store acme_seq_demo_store;
+
+int acme_seq_demo_store_create(int64_t num_episodes, const int64_t* offsets, int32_t num_fields,
+                               const int64_t* step_bytes, acme_seq_demo_store** out);
+int acme_seq_demo_store_destroy(acme_seq_demo_store* s);
+int acme_seq_demo_store_upload(acme_seq_demo_store* s, const void* const* fields);
+
+/* Overwrites the demonstration rows of a drawn batch of sequences in one launch.
+ * out_fields[0..num_out_fields-1] are the batch's device buffers as
+ * acme_replay_sample_gather fills them: row j of field f starts at out_fields[f] +
+ * j * out_row_bytes[f] and has out_logical_bytes[f] <= out_row_bytes[f] meaningful bytes.
+ * Fields 0..K-1 are the store's (logical bytes T * step_bytes[f], T = sequence_length),
+ * field K is start_of_episode (T bytes), the others are extras; K < num_out_fields <=
+ * ACME_SEQ_DEMO_MAX_OUT_FIELDS, 1 <= batch <= 65535.  Row j makes one Philox4x32-10 call,
+ * counter (j, step_counter lo, step_counter hi, 0x53455144 "SEQD"), key = seed, result r:
+ *   demonstration iff u01_53(r.x, r.y) < ratio (a replay row is left untouched);
+ *   episode e = (u64(r.z) * E) >> 32;  pos = (u64(r.w) * L_e) >> 32;
+ *   first = pos / period * period;  to = min(first + T, L_e)
+ * (_sequence_from_episode, r2d3/agent.py:193-196).  A demonstration row receives
+ *   fields 0..K-1: steps [first, to) of episode e, then zeros up to T steps;
+ *   field K: T bytes of (first == 0);  every other field: zeros over its logical bytes;
+ *   SampleInfo: key ACME_DEMO_KEY, probability 1, table_size 1, priority 1 (see above).
+ * Bytes of a row beyond a field's logical bytes are unspecified.  is_demo (u8 [batch], may
+ * be NULL) receives 1 / 0 per row.  keys / probabilities / table_size / priorities may be
+ * NULL.  Accesses are 16, 4 or 1 bytes wide per field: the widest that divides the field's
+ * step bytes (logical bytes for field K and the extras), its row bytes and both base
+ * addresses.  The grid is (ceil(largest logical bytes / 16 KiB), batch); every workgroup
+ * recomputes its row's draw. */
+int acme_seq_demo_mix(const acme_seq_demo_store* s, double ratio, int64_t period,
+                      int64_t sequence_length, uint64_t seed, uint64_t step_counter,
+                      int64_t batch, void* const* out_fields, int32_t num_out_fields,
+                      const int64_t* out_row_bytes, const int64_t* out_logical_bytes,
+                      uint64_t* keys, double* probabilities, int64_t* table_size,
+                      double* priorities, uint8_t* is_demo, void* stream);
+
 /* -------------------------------------------------------------------- DQN -- */
 
 enum { ACME_NET_NATURE_DQN = 0, ACME_NET_MLP = 1 };
