@@ -238,14 +238,11 @@ _SIGS = {
     "acme_replay_storage": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
     "acme_replay_inserted": (c_i64, [c_vp]),
     "acme_replay_restore": (c_i32, [c_vp, c_i64, c_vp]),
-    "acme_demo_store_create": (c_i32, [c_i64, c_vp, c_i64, c_i64, ctypes.POINTER(c_vp)]),
+    "acme_demo_store_create": (c_i32, [c_i64, c_vp, c_i32, c_vp, c_i64, ctypes.POINTER(c_vp)]),
     "acme_demo_store_destroy": (c_i32, [c_vp]),
-    "acme_demo_store_upload": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "acme_demo_store_upload": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
     "acme_demo_mix": (c_i32, [c_vp, c_f64, c_i32, c_f32, c_u64, c_u64, c_i64,
                               ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "acme_seq_demo_store_create": (c_i32, [c_i64, c_vp, c_i32, c_vp, ctypes.POINTER(c_vp)]),
-    "acme_seq_demo_store_destroy": (c_i32, [c_vp]),
-    "acme_seq_demo_store_upload": (c_i32, [c_vp, ctypes.POINTER(c_vp)]),
     "acme_seq_demo_mix": (c_i32, [c_vp, c_f64, c_i64, c_i64, c_u64, c_u64, c_i64,
                                   ctypes.POINTER(c_vp), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp]),

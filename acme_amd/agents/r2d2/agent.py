@@ -27,37 +27,31 @@ from acme_amd.networks import LSTMState
 from acme_amd.utils import savers
 
 
-class R2D2(agent.Agent):
+def core_state_spec(network):
+    """The extras an R2D2 actor stores with every step: the core state that went into it."""
+    H = network.lstm_size
+    return {"core_state": LSTMState(specs.Array((H,), np.float32),
+                                    specs.Array((H,), np.float32))}
 
-    def __init__(self, environment_spec: specs.EnvironmentSpec, network, burn_in_length: int,
-                 trace_length: int, replay_period: int, counter=None, logger=None,
-                 discount: float = 0.99, batch_size: int = 32,
-                 prefetch_size: Optional[int] = None, target_update_period: int = 100,
-                 importance_sampling_exponent: float = 0.2, priority_exponent: float = 0.6,
-                 epsilon: float = 0.01, learning_rate: float = 1e-3,
-                 min_replay_size: int = 1000, max_replay_size: int = 1_000_000,
-                 samples_per_insert: float = 32.0, store_lstm_state: bool = True,
-                 max_priority_weight: float = 0.9, checkpoint: bool = True,
-                 checkpoint_subpath: str = "~/acme/", seed: int = 0):
-        from acme_amd.agents.r2d2 import make_replay
-        H = network.lstm_size
-        extra_spec = {"core_state": LSTMState(specs.Array((H,), np.float32),
-                                              specs.Array((H,), np.float32))}
-        self._server, adder, dataset = make_replay(
-            environment_spec, extra_spec, burn_in_length, trace_length, replay_period,
-            batch_size=batch_size, max_replay_size=max_replay_size,
-            priority_exponent=priority_exponent, prefetch_size=prefetch_size, seed=1234 + seed)
-        sequence_length = burn_in_length + trace_length + 1
+
+class RecurrentReplayAgent(agent.Agent):
+    """What R2D2 and R2D3 share once their replay stands: the R2D2 learner on `dataset`, its
+    checkpointer, the epsilon-greedy policy on the learner's online network, a RecurrentActor
+    writing to `adder`, and the agent's observation arithmetic.  `learner_kwargs` go to
+    R2D2Learner as they are."""
+
+    def _finish(self, server, adder, dataset, *, environment_spec, network, target_network,
+                burn_in_length: int, trace_length: int, replay_period: int, batch_size: int,
+                min_replay_size: int, samples_per_insert: float, epsilon: float,
+                checkpoint: bool, checkpoint_subpath: str, seed: int, **learner_kwargs):
+        self._server = server
         learner = R2D2Learner(
             environment_spec=environment_spec, network=network,
-            target_network=copy.deepcopy(network), burn_in_length=burn_in_length,
-            sequence_length=sequence_length, dataset=dataset,
-            reverb_client=replay.Client(self._server), counter=counter, logger=logger,
-            discount=discount, target_update_period=target_update_period,
-            importance_sampling_exponent=importance_sampling_exponent,
-            max_replay_size=max_replay_size, learning_rate=learning_rate,
-            store_lstm_state=store_lstm_state, max_priority_weight=max_priority_weight,
-            batch_size=batch_size, seed=seed)
+            target_network=copy.deepcopy(network) if target_network is None else target_network,
+            burn_in_length=burn_in_length,
+            sequence_length=burn_in_length + trace_length + 1, dataset=dataset,
+            reverb_client=replay.Client(server), batch_size=batch_size, seed=seed,
+            **learner_kwargs)
         self._checkpointer = None
         if checkpoint:
             self._checkpointer = savers.Checkpointer(
@@ -91,3 +85,32 @@ class R2D2(agent.Agent):
         super().update()
         if self._checkpointer is not None:
             self._checkpointer.save()
+
+
+class R2D2(RecurrentReplayAgent):
+
+    def __init__(self, environment_spec: specs.EnvironmentSpec, network, burn_in_length: int,
+                 trace_length: int, replay_period: int, counter=None, logger=None,
+                 discount: float = 0.99, batch_size: int = 32,
+                 prefetch_size: Optional[int] = None, target_update_period: int = 100,
+                 importance_sampling_exponent: float = 0.2, priority_exponent: float = 0.6,
+                 epsilon: float = 0.01, learning_rate: float = 1e-3,
+                 min_replay_size: int = 1000, max_replay_size: int = 1_000_000,
+                 samples_per_insert: float = 32.0, store_lstm_state: bool = True,
+                 max_priority_weight: float = 0.9, checkpoint: bool = True,
+                 checkpoint_subpath: str = "~/acme/", seed: int = 0):
+        from acme_amd.agents.r2d2 import make_replay
+        replay_parts = make_replay(
+            environment_spec, core_state_spec(network), burn_in_length, trace_length,
+            replay_period, batch_size=batch_size, max_replay_size=max_replay_size,
+            priority_exponent=priority_exponent, prefetch_size=prefetch_size, seed=1234 + seed)
+        self._finish(
+            *replay_parts, environment_spec=environment_spec, network=network,
+            target_network=None, burn_in_length=burn_in_length, trace_length=trace_length,
+            replay_period=replay_period, batch_size=batch_size, min_replay_size=min_replay_size,
+            samples_per_insert=samples_per_insert, epsilon=epsilon, checkpoint=checkpoint,
+            checkpoint_subpath=checkpoint_subpath, seed=seed, counter=counter, logger=logger,
+            discount=discount, target_update_period=target_update_period,
+            importance_sampling_exponent=importance_sampling_exponent,
+            max_replay_size=max_replay_size, learning_rate=learning_rate,
+            store_lstm_state=store_lstm_state, max_priority_weight=max_priority_weight)

@@ -9,7 +9,7 @@ the arguments after it are passed by keyword, as the reference's callers pass th
 single-process R2D2 agent whose every batch mixes demonstration sequences with the actor's
 experience: a Uniform + Fifo sequence table (agent.py:74-81), the SequenceAdder, the table's
 dataset with the demonstrations mixed in on the GPU (acme_amd.datasets.demonstrations,
-csrc/seq_demos.hip), the R2D2 learner with store_lstm_state=False (a demonstration has no
+csrc/demos.hip), the R2D2 learner with store_lstm_state=False (a demonstration has no
 core state: its extras are zeros, so every sequence is burnt in from a zero state) and a
 RecurrentActor on the learner's online network.
 
@@ -19,22 +19,13 @@ actions, rewards, discounts) episodes one is built from
 
 from __future__ import annotations
 
-import copy
-import os
-
-import numpy as np
-
 from acme_amd import datasets, replay, specs
 from acme_amd.adders import reverb as adders
-from acme_amd.agents import agent
-from acme_amd.agents.actors import RecurrentActor
-from acme_amd.agents.r2d2.learning import R2D2Learner
+from acme_amd.agents.r2d2.agent import RecurrentReplayAgent, core_state_spec
 from acme_amd.datasets import demonstrations
-from acme_amd.networks import LSTMState
-from acme_amd.utils import savers
 
 
-class R2D3(agent.Agent):
+class R2D3(RecurrentReplayAgent):
 
     def __init__(self, environment_spec: specs.EnvironmentSpec, network, target_network=None,
                  *, burn_in_length: int, trace_length: int, replay_period: int,
@@ -45,68 +36,35 @@ class R2D3(agent.Agent):
                  min_replay_size: int = 1000, max_replay_size: int = 1_000_000,
                  samples_per_insert: float = 32.0, checkpoint_subpath: str = "~/acme/",
                  seed: int = 0):
-        H = network.lstm_size
-        extra_spec = {"core_state": LSTMState(specs.Array((H,), np.float32),
-                                              specs.Array((H,), np.float32))}
         table = replay.Table(
             name=adders.DEFAULT_PRIORITY_TABLE, sampler=replay.selectors.Uniform(),
             remover=replay.selectors.Fifo(), max_size=max_replay_size,
             rate_limiter=replay.rate_limiters.MinSize(1),
-            signature=adders.SequenceAdder.signature(environment_spec, extra_spec),
+            signature=adders.SequenceAdder.signature(environment_spec,
+                                                     core_state_spec(network)),
             seed=1234 + seed)
-        self._server = replay.Server([table], port=None)
+        server = replay.Server([table], port=None)
         sequence_length = burn_in_length + trace_length + 1
-        adder = adders.SequenceAdder(client=replay.Client(self._server), period=replay_period,
+        adder = adders.SequenceAdder(client=replay.Client(server), period=replay_period,
                                      sequence_length=sequence_length)
         store = demonstration_dataset
         if not isinstance(store, demonstrations.SequenceDemonstrationStore):
             store = demonstrations.SequenceDemonstrationStore(store, table)
-        dataset = datasets.make_reverb_dataset(server_address=self._server,
-                                               batch_size=batch_size,
+        dataset = datasets.make_reverb_dataset(server_address=server, batch_size=batch_size,
                                                sequence_length=sequence_length)
         # The demonstrations' draws have a stream of their own (seed + tag), apart from the
         # table's.
         dataset = demonstrations.mix_sequence_demonstrations(
             dataset, store, demonstration_ratio=demonstration_ratio, period=replay_period,
             sequence_length=sequence_length, seed=4321 + seed)
-        self._dataset = dataset
-        learner = R2D2Learner(
-            environment_spec=environment_spec, network=network,
-            target_network=copy.deepcopy(network) if target_network is None else target_network,
-            burn_in_length=burn_in_length, sequence_length=sequence_length, dataset=dataset,
-            reverb_client=replay.Client(self._server), counter=counter, logger=logger,
-            discount=discount, target_update_period=target_update_period,
+        self._finish(
+            server, adder, dataset, environment_spec=environment_spec, network=network,
+            target_network=target_network, burn_in_length=burn_in_length,
+            trace_length=trace_length, replay_period=replay_period, batch_size=batch_size,
+            min_replay_size=min_replay_size, samples_per_insert=samples_per_insert,
+            epsilon=epsilon, checkpoint=checkpoint, checkpoint_subpath=checkpoint_subpath,
+            seed=seed, counter=counter, logger=logger, discount=discount,
+            target_update_period=target_update_period,
             importance_sampling_exponent=importance_sampling_exponent,
             max_replay_size=max_replay_size, learning_rate=learning_rate,
-            store_lstm_state=False, batch_size=batch_size, seed=seed)
-        self._checkpointer = None
-        if checkpoint:
-            self._checkpointer = savers.Checkpointer(
-                objects_to_save={"learner": learner},
-                directory=os.path.join(os.path.expanduser(checkpoint_subpath), "r2d2_learner"),
-                time_delta_minutes=60.0)
-        self._learner_obj = learner
-        self._policy = learner.make_policy(epsilon, seed)
-        actor = RecurrentActor(self._policy, network.initial_state, adder)
-        observations_per_step = float(replay_period * batch_size) / samples_per_insert
-        super().__init__(actor=actor, learner=learner,
-                         min_observations=replay_period * max(batch_size, min_replay_size),
-                         observations_per_step=observations_per_step)
-
-    @property
-    def learner(self) -> R2D2Learner:
-        return self._learner_obj
-
-    @property
-    def policy(self):
-        """The actor's policy (its seed and call counter replay its draws)."""
-        return self._policy
-
-    @property
-    def server(self):
-        return self._server
-
-    def update(self):
-        super().update()
-        if self._checkpointer is not None:
-            self._checkpointer.save()
+            store_lstm_state=False)

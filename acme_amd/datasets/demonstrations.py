@@ -19,8 +19,8 @@ priority write-back touch the table; 2**64 - 2 equals no stored key and the writ
 drops it as stale.
 
 The second half of the module is the same mix for sequence tables (R2D3):
-`SequenceDemonstrationStore` and `mix_sequence_demonstrations`, on acme_seq_demo_mix
-(csrc/seq_demos.hip).  Both share the iterator, the refusals and the key.
+`SequenceDemonstrationStore` and `mix_sequence_demonstrations`, on acme_seq_demo_mix (the
+same file).  Both share the store's bookkeeping, the iterator, the refusals and the key.
 """
 
 from __future__ import annotations
@@ -39,16 +39,21 @@ from acme_amd.datasets.reverb import ReplayDataset, _data_parallel, _TableIterat
 DEMONSTRATION_KEY = 0xFFFFFFFFFFFFFFFE
 
 
+def _refuse_table(x, kind: str) -> None:
+    """The tables no store can be laid out for (`kind`: "transition" or "sequence")."""
+    if isinstance(x, (replay.FrameTable, replay.QueueTable)):
+        raise ValueError(f"demonstrations are mixed into {kind} tables, not a "
+                         f"{type(x).__name__}")
+    if isinstance(x, replay.Table) and x.fields is None:
+        raise ValueError("the table has no item layout yet: construct it with a signature")
+
+
 def _transition_fields(table_or_signature):
     """The flattened field layout of a transition table, its signature, or a field list."""
     x = table_or_signature
-    if isinstance(x, (replay.FrameTable, replay.QueueTable)):
-        raise ValueError(f"demonstrations are mixed into transition tables, not a "
-                         f"{type(x).__name__}")
+    _refuse_table(x, "transition")
     if isinstance(x, replay.Table):
         fields = x.fields
-        if fields is None:
-            raise ValueError("the table has no item layout yet: construct it with a signature")
     elif isinstance(x, (list, tuple)) and x and all(isinstance(f, replay._Field) for f in x):  # noqa: SLF001
         fields = list(x)
     else:
@@ -65,7 +70,41 @@ def _transition_fields(table_or_signature):
     return fields
 
 
-class DemonstrationStore:
+class _Store:
+    """What both stores keep: the episodes' lengths and offsets, the native store, and the
+    packed host fields (uint8 [total, step_bytes] each) until they go to the device."""
+
+    def _keep(self, lengths, packed, min_episode_steps: int, device) -> None:
+        from acme_amd.native import NativeDemoStore
+        if not lengths:
+            raise ValueError("no demonstration episodes")
+        self.lengths = np.asarray(lengths, np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        # Checks the lengths and the step bytes (ValueError for a short episode).
+        self._native = NativeDemoStore(self.offsets, [p[0].shape[1] for p in packed],
+                                       min_episode_steps)
+        self._host = [np.concatenate(p) for p in packed]
+        self._device = device
+
+    @property
+    def num_episodes(self) -> int:
+        return len(self.lengths)
+
+    def upload(self, device=None):
+        """Puts the fields on the device (once) and returns the native store."""
+        if self._host is not None:
+            self._native.upload(self._host, device=device or self._device)
+            self._host = None
+        return self._native
+
+
+def _step_bytes(x: np.ndarray, dtype, nbytes: int) -> np.ndarray:
+    """[L, nbytes] uint8: the steps of x as `dtype`, C order."""
+    x = np.ascontiguousarray(x, dtype=dtype)
+    return np.frombuffer(x.tobytes(), np.uint8).reshape(x.shape[0], nbytes)
+
+
+class DemonstrationStore(_Store):
     """Demonstration episodes held on the device for `mix_demonstrations`.
 
     episodes: an iterable of (observations [L, ...], actions [L, ...], rewards [L],
@@ -81,11 +120,11 @@ class DemonstrationStore:
 
     def __init__(self, episodes: Iterable[Sequence[np.ndarray]], table_or_signature,
                  device=None):
-        from acme_amd.native import NativeDemoStore
         fields = _transition_fields(table_or_signature)
         fo, fa = fields[0], fields[1]
         self.obs_row_bytes, self.action_row_bytes = fo.row_bytes, fa.row_bytes
-        obs, act, rew, dis, lengths = [], [], [], [], []
+        packed = [[], [], [], []]  # observation rows, action rows, rewards, discounts
+        lengths = []
         for i, ep in enumerate(episodes):
             if len(ep) != 4:
                 raise ValueError(f"episode {i}: expected (observations, actions, rewards, "
@@ -100,39 +139,19 @@ class DemonstrationStore:
                     f"episode {i}: rows of {o.shape[1:]} observations and {a.shape[1:]} actions "
                     f"do not match the table's {fo.shape} ({fo.row_bytes} bytes) and {fa.shape} "
                     f"({fa.row_bytes} bytes)")
-            obs.append(self._rows(o, fo))
-            act.append(self._rows(a, fa))
-            rew.append(r)
-            dis.append(d)
+            for p, x in zip(packed, (self._rows(o, fo), self._rows(a, fa),
+                                     _step_bytes(r, np.float32, 4),
+                                     _step_bytes(d, np.float32, 4))):
+                p.append(x)
             lengths.append(L)
-        if not lengths:
-            raise ValueError("no demonstration episodes")
-        self.lengths = np.asarray(lengths, np.int64)
-        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        # Checks the lengths (ValueError for an episode shorter than 3 steps).
-        self._native = NativeDemoStore(self.offsets, fo.row_bytes, fa.row_bytes)
-        self._host = (np.concatenate(obs), np.concatenate(act), np.concatenate(rew),
-                      np.concatenate(dis))
-        self._device = device
+        self._keep(lengths, packed, 3, device)
 
     @staticmethod
     def _rows(x: np.ndarray, f) -> np.ndarray:
         """[L, row_bytes] uint8 rows as the table stores them (C order, zero padding)."""
-        x = np.ascontiguousarray(x, dtype=f.dtype)
         rows = np.zeros((x.shape[0], f.row_bytes), np.uint8)
-        rows[:, :f.nbytes] = np.frombuffer(x.tobytes(), np.uint8).reshape(x.shape[0], f.nbytes)
+        rows[:, :f.nbytes] = _step_bytes(x, f.dtype, f.nbytes)
         return rows
-
-    @property
-    def num_episodes(self) -> int:
-        return len(self.lengths)
-
-    def upload(self, device=None):
-        """Puts the rows on the device (once) and returns the native store."""
-        if self._host is not None:
-            self._native.upload(*self._host, device=device or self._device)
-            self._host = None
-        return self._native
 
 
 class _MixIterator(_TableIterator):
@@ -233,8 +252,9 @@ class MixedDataset(_Mixed):
         native = self.store.upload(table.native.device)
 
         def launch(step, batch, ptrs, raw, is_demo, st):
-            native.mix(self.demonstration_ratio, self.n_step, self.discount, self.seed, step,
-                       batch, ptrs, raw[1], raw[2], raw[3], raw[4], is_demo, st)
+            native.mix_transitions(self.demonstration_ratio, self.n_step, self.discount,
+                                   self.seed, step, batch, ptrs, raw[1], raw[2], raw[3], raw[4],
+                                   is_demo, st)
         return launch
 
 
@@ -287,7 +307,7 @@ def mix_demonstrations(dataset: ReplayDataset, store: DemonstrationStore,
 # from there zero-padded to the sequence length, start_of_episode = (first == 0) over the
 # whole window, all-zero extras) and interleaves that dataset with the Reverb stream.  Here
 # it is the same per-row overlay as above with a kernel of its own (acme_seq_demo_mix,
-# csrc/seq_demos.hip) that writes any number of per-step fields and spreads a row over as
+# csrc/demos.hip) that writes any number of per-step fields and spreads a row over as
 # many workgroups as its bytes need.
 
 
@@ -297,14 +317,10 @@ def _sequence_layout(table_or_signature):
     action, reward, discount, start_of_episode, extras), the number K of leaves in front of
     start_of_episode, and the table's sequence length (None when not yet known)."""
     x = table_or_signature
-    if isinstance(x, (replay.FrameTable, replay.QueueTable)):
-        raise ValueError(f"demonstrations are mixed into sequence tables, not a "
-                         f"{type(x).__name__}")
+    _refuse_table(x, "sequence")
     T = None
     if isinstance(x, replay.Table):
         structure, fields, T = x._structure, x.fields, x.sequence_length  # noqa: SLF001
-        if fields is None:
-            raise ValueError("the table has no item layout yet: construct it with a signature")
     else:
         structure, fields = x, None
     if not isinstance(structure, adders.Step):
@@ -330,7 +346,7 @@ def _same_steps(a, b) -> bool:
     return [(f.shape, f.dtype) for f in a] == [(f.shape, f.dtype) for f in b]
 
 
-class SequenceDemonstrationStore:
+class SequenceDemonstrationStore(_Store):
     """Demonstration episodes held on the device for `mix_sequence_demonstrations`.
 
     episodes: an iterable of (observations, actions, rewards, discounts), one tuple per
@@ -346,11 +362,11 @@ class SequenceDemonstrationStore:
     here needs a GPU before that."""
 
     def __init__(self, episodes: Iterable[Sequence], table_or_signature, device=None):
-        from acme_amd.native import SEQ_DEMO_MAX_FIELDS, NativeSeqDemoStore
+        from acme_amd.native import DEMO_MAX_FIELDS
         fields, K, _ = _sequence_layout(table_or_signature)
-        if K > SEQ_DEMO_MAX_FIELDS:
+        if K > DEMO_MAX_FIELDS:
             raise ValueError(f"{K} per-step fields in front of start_of_episode; a store "
-                             f"holds at most {SEQ_DEMO_MAX_FIELDS}")
+                             f"holds at most {DEMO_MAX_FIELDS}")
         self.step_fields = fields[:K]
         packed = [[] for _ in range(K)]
         lengths = []
@@ -373,28 +389,9 @@ class SequenceDemonstrationStore:
                 if not np.can_cast(x.dtype, f.dtype, casting="same_kind"):
                     raise ValueError(f"episode {i}, leaf {k}: {x.dtype} steps cannot be "
                                      f"stored in the table's {f.dtype} field")
-                x = np.ascontiguousarray(x, dtype=f.dtype)
-                packed[k].append(np.frombuffer(x.tobytes(), np.uint8).reshape(L, f.nbytes))
+                packed[k].append(_step_bytes(x, f.dtype, f.nbytes))
             lengths.append(L)
-        if not lengths:
-            raise ValueError("no demonstration episodes")
-        self.lengths = np.asarray(lengths, np.int64)
-        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        # Checks the lengths and the step bytes (ValueError for an empty episode or leaf).
-        self._native = NativeSeqDemoStore(self.offsets, [f.nbytes for f in self.step_fields])
-        self._host = [np.concatenate(p) for p in packed]
-        self._device = device
-
-    @property
-    def num_episodes(self) -> int:
-        return len(self.lengths)
-
-    def upload(self, device=None):
-        """Puts the fields on the device (once) and returns the native store."""
-        if self._host is not None:
-            self._native.upload(self._host, device=device or self._device)
-            self._host = None
-        return self._native
+        self._keep(lengths, packed, 1, device)
 
 
 class SequenceMixedDataset(_Mixed):
@@ -432,9 +429,9 @@ class SequenceMixedDataset(_Mixed):
         native = self.store.upload(table.native.device)
 
         def launch(step, batch, ptrs, raw, is_demo, st):
-            native.mix(self.demonstration_ratio, self.period, self.sequence_length, self.seed,
-                       step, batch, ptrs, row_bytes, logical, raw[1], raw[2], raw[3], raw[4],
-                       is_demo, st)
+            native.mix_sequences(self.demonstration_ratio, self.period, self.sequence_length,
+                                 self.seed, step, batch, ptrs, row_bytes, logical, raw[1],
+                                 raw[2], raw[3], raw[4], is_demo, st)
         return launch
 
 
@@ -461,5 +458,3 @@ def mix_sequence_demonstrations(dataset: ReplayDataset, store: SequenceDemonstra
     if dataset.table.fields is not None:
         mixed.check_layout(dataset.table)
     return mixed
-
-

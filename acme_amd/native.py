@@ -292,21 +292,27 @@ class NativeNStepWriter:
         return int(self._pending(self._h))
 
 
-class NativeDemoStore:
-    """acme_demo_store: demonstration episodes as immutable device arrays (csrc/demos.hip).
-    The constructor checks the layout on the host (a short episode is a ValueError, no GPU
-    needed); `upload()` puts the packed rows on the device, once; `mix()` overlays the
-    demonstration rows of a drawn batch (acme_demo_mix)."""
+DEMO_MAX_FIELDS = 16           # ACME_DEMO_MAX_FIELDS
+SEQ_DEMO_MAX_OUT_FIELDS = 32   # ACME_SEQ_DEMO_MAX_OUT_FIELDS
 
-    def __init__(self, offsets: np.ndarray, obs_row_bytes: int, action_row_bytes: int):
+
+class NativeDemoStore:
+    """acme_demo_store: demonstration episodes as K immutable per-step device arrays
+    (csrc/demos.hip).  The constructor checks the layout on the host (an episode shorter than
+    min_episode_steps is a ValueError, no GPU needed); `upload()` puts the packed fields on
+    the device, once; `mix_transitions()` (acme_demo_mix) and `mix_sequences()`
+    (acme_seq_demo_mix) overlay the demonstration rows of a drawn batch."""
+
+    def __init__(self, offsets: np.ndarray, step_bytes: Sequence[int],
+                 min_episode_steps: int = 1):
         self.offsets = np.ascontiguousarray(offsets, np.int64)
-        self.obs_row_bytes = int(obs_row_bytes)
-        self.action_row_bytes = int(action_row_bytes)
+        self.step_bytes = np.ascontiguousarray(step_bytes, np.int64)
         self.device = None
         h = ctypes.c_void_p()
         check(lib().acme_demo_store_create(len(self.offsets) - 1, self.offsets.ctypes.data,
-                                           self.obs_row_bytes, self.action_row_bytes,
-                                           ctypes.byref(h)), "demonstration store")
+                                           len(self.step_bytes), self.step_bytes.ctypes.data,
+                                           int(min_episode_steps), ctypes.byref(h)),
+              "demonstration store")
         self._h = h
 
     def __del__(self):
@@ -314,71 +320,6 @@ class NativeDemoStore:
         if h is not None and h.value:
             try:
                 lib().acme_demo_store_destroy(h)
-            except Exception:  # interpreter shutdown
-                pass
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def upload(self, observations: np.ndarray, actions: np.ndarray, rewards: np.ndarray,
-               discounts: np.ndarray, device=None) -> None:
-        """Packed host rows: uint8 [total, obs_row_bytes] and [total, action_row_bytes],
-        float32 [total] twice."""
-        _lib.require_gpu()
-        total = int(self.offsets[-1])
-        arrays = [np.ascontiguousarray(observations, np.uint8),
-                  np.ascontiguousarray(actions, np.uint8),
-                  np.ascontiguousarray(rewards, np.float32),
-                  np.ascontiguousarray(discounts, np.float32)]
-        want = [total * self.obs_row_bytes, total * self.action_row_bytes, 4 * total, 4 * total]
-        for a, n in zip(arrays, want):
-            if a.nbytes != n:
-                raise ValueError(f"demonstration array has {a.nbytes} bytes, expected {n}")
-        self.device = torch.device(device or "cuda")
-        with torch.cuda.device(self.device):
-            check(lib().acme_demo_store_upload(self._h, *[a.ctypes.data for a in arrays]),
-                  "demonstration store upload")
-
-    def mix(self, ratio: float, n_step: int, discount: float, seed: int, step: int, batch: int,
-            out_fields, keys: int, probabilities: int, table_size: int, priorities: int,
-            is_demo: int = 0, stream: Optional[int] = None) -> None:
-        """out_fields: a ctypes array of the five transition fields' device pointers; the
-        other outputs raw device addresses (0: not written); stream: a raw hipStream_t."""
-        check(lib().acme_demo_mix(self._h, float(ratio), int(n_step), float(discount),
-                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
-                                  int(batch), out_fields, keys or None, probabilities or None,
-                                  table_size or None, priorities or None, is_demo or None,
-                                  stream_ptr() if stream is None else stream),
-              "demonstration mix")
-
-
-SEQ_DEMO_MAX_FIELDS = 16       # ACME_SEQ_DEMO_MAX_FIELDS
-SEQ_DEMO_MAX_OUT_FIELDS = 32   # ACME_SEQ_DEMO_MAX_OUT_FIELDS
-
-
-class NativeSeqDemoStore:
-    """acme_seq_demo_store: demonstration episodes as K immutable per-step device arrays
-    (csrc/seq_demos.hip).  The constructor checks the layout on the host (no GPU needed);
-    `upload()` puts the packed fields on the device, once; `mix()` overlays the demonstration
-    rows of a drawn batch of sequences (acme_seq_demo_mix)."""
-
-    def __init__(self, offsets: np.ndarray, step_bytes: Sequence[int]):
-        self.offsets = np.ascontiguousarray(offsets, np.int64)
-        self.step_bytes = np.ascontiguousarray(step_bytes, np.int64)
-        self.device = None
-        h = ctypes.c_void_p()
-        check(lib().acme_seq_demo_store_create(len(self.offsets) - 1, self.offsets.ctypes.data,
-                                               len(self.step_bytes), self.step_bytes.ctypes.data,
-                                               ctypes.byref(h)), "sequence demonstration store")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().acme_seq_demo_store_destroy(h)
             except Exception:  # interpreter shutdown
                 pass
             self._h = None
@@ -402,13 +343,27 @@ class NativeSeqDemoStore:
         self.device = torch.device(device or "cuda")
         ptrs = (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
         with torch.cuda.device(self.device):
-            check(lib().acme_seq_demo_store_upload(self._h, ptrs),
-                  "sequence demonstration store upload")
+            check(lib().acme_demo_store_upload(self._h, ptrs), "demonstration store upload")
 
-    def mix(self, ratio: float, period: int, sequence_length: int, seed: int, step: int,
-            batch: int, out_fields, row_bytes: np.ndarray, logical_bytes: np.ndarray, keys: int,
-            probabilities: int, table_size: int, priorities: int, is_demo: int = 0,
-            stream: Optional[int] = None) -> None:
+    def mix_transitions(self, ratio: float, n_step: int, discount: float, seed: int, step: int,
+                        batch: int, out_fields, keys: int, probabilities: int,
+                        table_size: int, priorities: int, is_demo: int = 0,
+                        stream: Optional[int] = None) -> None:
+        """out_fields: a ctypes array of the five transition fields' device pointers; the
+        other outputs raw device addresses (0: not written); stream: a raw hipStream_t.  The
+        store's fields are observation rows, action rows, f32 rewards, f32 discounts."""
+        check(lib().acme_demo_mix(self._h, float(ratio), int(n_step), float(discount),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                  int(batch), out_fields, keys or None, probabilities or None,
+                                  table_size or None, priorities or None, is_demo or None,
+                                  stream_ptr() if stream is None else stream),
+              "demonstration mix")
+
+    def mix_sequences(self, ratio: float, period: int, sequence_length: int, seed: int,
+                      step: int, batch: int, out_fields, row_bytes: np.ndarray,
+                      logical_bytes: np.ndarray, keys: int, probabilities: int,
+                      table_size: int, priorities: int, is_demo: int = 0,
+                      stream: Optional[int] = None) -> None:
         """out_fields: a ctypes array of every batch field's device pointer; row_bytes /
         logical_bytes: int64 arrays of the same length; the other outputs raw device
         addresses (0: not written); stream: a raw hipStream_t."""

@@ -307,22 +307,22 @@ int acme_replay_restore(acme_replay* r, int64_t inserted, void* stream);
  * live on the device and one launch overlays the demonstration rows of a batch the table
  * has already drawn and gathered.
  *
- * Store: E episodes of L_e >= 3 steps each (the reference draws `first` from [0, L - 2),
- * empty below 3: a shorter episode is ACME_ERR_INVALID), immutable after upload:
- *   observations [total][obs_row_bytes], actions [total][action_row_bytes], rewards and
- *   discounts f32 [total], offsets i64 [E + 1] (episode e is steps offsets[e] ..
- *   offsets[e + 1] - 1; offsets[0] = 0, offsets[E] = total).
- * The row bytes are those of fields 0 and 1 of the transition table the store is mixed
- * with (multiples of 4).  acme_demo_store_create checks and keeps the host-side layout (no
- * device call); acme_demo_store_upload allocates the device arrays on the current device
- * and copies the four host arrays into them (synchronous, once). */
+ * Store (shared by both mixes below): E episodes of L_e >= min_episode_steps >= 1 steps
+ * each (a shorter episode is ACME_ERR_INVALID) as K per-step field arrays, 1 <= K <=
+ * ACME_DEMO_MAX_FIELDS, immutable after upload.  Field f is [total][step_bytes[f]] bytes,
+ * densely packed (1 <= step_bytes[f] <= 2^40 is the size of one step's entry); offsets i64
+ * [E + 1]: episode e is steps offsets[e] .. offsets[e + 1] - 1, offsets[0] = 0, offsets[E] =
+ * total, E and every L_e at most 2^31.  acme_demo_store_create checks and keeps the layout
+ * on the host (no device call); acme_demo_store_upload allocates the device arrays on the
+ * current device and copies the K host arrays fields[0..K-1] into them (synchronous, once). */
+#define ACME_DEMO_MAX_FIELDS 16 /* per-step fields of a store */
 typedef struct acme_demo_store acme_demo_store;
 
-int acme_demo_store_create(int64_t num_episodes, const int64_t* offsets, int64_t obs_row_bytes,
-                           int64_t action_row_bytes, acme_demo_store** out);
+int acme_demo_store_create(int64_t num_episodes, const int64_t* offsets, int32_t num_fields,
+                           const int64_t* step_bytes, int64_t min_episode_steps,
+                           acme_demo_store** out);
 int acme_demo_store_destroy(acme_demo_store* s);
-int acme_demo_store_upload(acme_demo_store* s, const void* observations, const void* actions,
-                           const float* rewards, const float* discounts);
+int acme_demo_store_upload(acme_demo_store* s, const void* const* fields);
 
 #define ACME_DEMO_KEY 0xFFFFFFFFFFFFFFFEull /* the key of every demonstration row */
 
@@ -341,7 +341,12 @@ int acme_demo_store_upload(acme_demo_store* s, const void* observations, const v
  * Its SampleInfo is probability 1, table_size 1, priority 1 and key ACME_DEMO_KEY (the
  * reference's 0 is a live key here, and ~0 marks an empty slot; 2^64 - 2 equals no stored
  * key, so a priority update drops it as stale).  is_demo (u8 [batch], may be NULL) receives
- * 1 / 0 per row.  keys / probabilities / table_size / priorities may be NULL. */
+ * 1 / 0 per row.  keys / probabilities / table_size / priorities may be NULL.
+ * The store must hold exactly four fields: observation rows and action rows in the byte
+ * layout of fields 0 and 1 of the transition table (step bytes positive multiples of 4),
+ * f32 rewards and f32 discounts (step bytes 4), and must have been created with
+ * min_episode_steps >= 3 (the reference draws `first` from [0, L - 2), empty below 3);
+ * any other store is ACME_ERR_INVALID, before any device call. */
 int acme_demo_mix(const acme_demo_store* s, double ratio, int32_t n_step, float discount,
                   uint64_t seed, uint64_t step_counter, int64_t batch, void* const* out_fields,
                   uint64_t* keys, double* probabilities, int64_t* table_size,
@@ -351,22 +356,10 @@ int acme_demo_mix(const acme_demo_store* s, double ratio, int32_t n_step, float 
  * 163-235): the same overlay for batches of T-step items (SequenceAdder's Step(observation,
  * action, reward, discount, start_of_episode, extras)).
  *
- * Store: E episodes of L_e >= 1 steps each as K per-step field arrays (the flattened leaves
- * of observation, action, reward, discount, in the table's field order), 1 <= K <=
- * ACME_SEQ_DEMO_MAX_FIELDS.  Field f is [total][step_bytes[f]] bytes, densely packed (no
- * per-step padding; step_bytes[f] >= 1 is the logical size of one step's leaf), offsets as
- * above.  acme_seq_demo_store_create checks and keeps the layout on the host (no device
- * call); acme_seq_demo_store_upload allocates the device arrays on the current device and
- * copies the K host arrays fields[0..K-1] into them (synchronous, once; the store is
- * immutable afterwards). */
-#define ACME_SEQ_DEMO_MAX_FIELDS 16     /* copied per-step fields of a store */
+ * The store holds the K flattened leaves of observation, action, reward, discount, in the
+ * table's field order, without per-step padding (step_bytes[f] is the logical size of one
+ * step's leaf; a 3-byte step stays 3 bytes). */
 #define ACME_SEQ_DEMO_MAX_OUT_FIELDS 32 /* all fields of a batch the mix writes */
-typedef struct acme_seq_demo_store acme_seq_demo_store;
-
-int acme_seq_demo_store_create(int64_t num_episodes, const int64_t* offsets, int32_t num_fields,
-                               const int64_t* step_bytes, acme_seq_demo_store** out);
-int acme_seq_demo_store_destroy(acme_seq_demo_store* s);
-int acme_seq_demo_store_upload(acme_seq_demo_store* s, const void* const* fields);
 
 /* Overwrites the demonstration rows of a drawn batch of sequences in one launch.
  * out_fields[0..num_out_fields-1] are the batch's device buffers as
@@ -389,7 +382,7 @@ int acme_seq_demo_store_upload(acme_seq_demo_store* s, const void* const* fields
  * step bytes (logical bytes for field K and the extras), its row bytes and both base
  * addresses.  The grid is (ceil(largest logical bytes / 16 KiB), batch); every workgroup
  * recomputes its row's draw. */
-int acme_seq_demo_mix(const acme_seq_demo_store* s, double ratio, int64_t period,
+int acme_seq_demo_mix(const acme_demo_store* s, double ratio, int64_t period,
                       int64_t sequence_length, uint64_t seed, uint64_t step_counter,
                       int64_t batch, void* const* out_fields, int32_t num_out_fields,
                       const int64_t* out_row_bytes, const int64_t* out_logical_bytes,

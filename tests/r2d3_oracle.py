@@ -1,5 +1,5 @@
 """Numpy oracle of the sequence demonstration mix (acme_seq_demo_mix,
-acme_amd/csrc/seq_demos.hip) — test infrastructure, no GPU.
+acme_amd/csrc/demos.hip) — test infrastructure, no GPU.
 
 - draw(): the per-row mapping of one Philox4x32-10 call (tests/_oracle.philox) to
   (demonstration?, episode, first, to), as _sequence_from_episode draws them

@@ -187,12 +187,39 @@ def test_store_refusals():
 
 
 def test_native_store_refusals():
-    from acme_amd.native import NativeSeqDemoStore
-    NativeSeqDemoStore(np.array([0, 1]), [3])
+    from acme_amd.native import NativeDemoStore
+    NativeDemoStore(np.array([0, 1]), [3])
+    NativeDemoStore(np.array([0, 3]), [12, 4, 4, 4], min_episode_steps=3)
     for offsets, step_bytes in (([0], [4]), ([0, 0], [4]), ([0, 2, 2], [4]), ([0, 2], []),
                                 ([0, 2], [4] * 17), ([0, 2], [4, 0]), ([1, 2], [4])):
         with pytest.raises(ValueError):
-            NativeSeqDemoStore(np.array(offsets), step_bytes)
+            NativeDemoStore(np.array(offsets), step_bytes)
+    with pytest.raises(ValueError, match="at least 3"):
+        NativeDemoStore(np.array([0, 2]), [4], min_episode_steps=3)
+
+
+def test_transition_mix_refuses_other_stores_without_a_device():
+    """acme_demo_mix checks what it asks of the store (four fields, f32 rewards and
+    discounts, rows of multiples of 4 bytes, min_episode_steps >= 3) before anything that
+    needs a device: the stores here were never uploaded, and the refusal names the layout."""
+    import ctypes
+    from acme_amd.native import NativeDemoStore
+    ptrs = (ctypes.c_void_p * 5)()
+
+    def mix(store):
+        store.mix_transitions(0.5, 1, 0.99, 0, 0, 1, ptrs, 0, 0, 0, 0, stream=0)
+
+    with pytest.raises(ValueError, match="min_episode_steps of at least 3"):
+        mix(NativeDemoStore(np.array([0, 3]), [12, 4, 4, 4], min_episode_steps=1))
+    for step_bytes in ([12, 4, 4], [12, 4, 4, 4, 4], [12, 4, 8, 4], [12, 4, 4, 2]):
+        with pytest.raises(ValueError, match="four fields"):
+            mix(NativeDemoStore(np.array([0, 3]), step_bytes, min_episode_steps=3))
+    for step_bytes in ([3, 4, 4, 4], [12, 6, 4, 4]):
+        with pytest.raises(ValueError, match="multiples of 4"):
+            mix(NativeDemoStore(np.array([0, 3]), step_bytes, min_episode_steps=3))
+    # a store of the right layout gets past these checks: it is refused for not being uploaded
+    with pytest.raises(ValueError, match="not been uploaded"):
+        mix(NativeDemoStore(np.array([0, 3]), [12, 4, 4, 4], min_episode_steps=3))
 
 
 def test_transition_and_frame_tables_are_refused():

@@ -1,5 +1,5 @@
 """Demonstration sequences mixed into sequence batches on the GPU (acme_seq_demo_mix,
-csrc/seq_demos.hip; acme_amd/datasets/demonstrations.py; acme_amd/agents/r2d3) against the
+csrc/demos.hip; acme_amd/datasets/demonstrations.py; acme_amd/agents/r2d3) against the
 numpy oracle tests/r2d3_oracle.py, bit for bit.
 
   * test_mixed_sequences_equal_oracle: is_demo, the info fields, every data field (the copied

@@ -134,7 +134,8 @@ def main():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for s in range(STEPS):
-            native.mix(RATIO, N_STEP, DISCOUNT, 1, s, B, ptrs, raw[1], raw[2], raw[3], raw[4])
+            native.mix_transitions(RATIO, N_STEP, DISCOUNT, 1, s, B, ptrs, raw[1], raw[2], raw[3],
+                                   raw[4])
         e1.record()
         e1.synchronize()
         launch.append(e0.elapsed_time(e1) / STEPS)

@@ -1,5 +1,5 @@
 """Cost of mixing demonstration sequences into the R2D2 batches
-(acme_amd.datasets.demonstrations.mix_sequence_demonstrations, csrc/seq_demos.hip): the
+(acme_amd.datasets.demonstrations.mix_sequence_demonstrations, csrc/demos.hip): the
 headline layout, B = 32 sequences of T = 121 steps of an OAR observation with 84x84x4 uint8
 frames (3.4 MB per row), demonstration ratio 0.25, a Uniform table as the R2D3 agent builds it.
 
