@@ -131,7 +131,7 @@ struct acme_dqn : PlaneGuard {
   float* slab = nullptr;
   int64_t slab_floats = 0;
   bool stamps_on = false;      // ACME_V_STAMPS=1: the online fc_fwd launch stamps its phases
-  uint64_t* stamps = nullptr;  // [4096][8] (debug_buffer "gemm_stamps")
+  uint64_t* stamps = nullptr;  // [6][4096][8] (debug_buffer "gemm_stamps")
   float* g = nullptr;  // per-sample dLoss/dq_tm1[a]
   int32_t* a_cache = nullptr;  // actions of the current batch (for the backward kernels)
   float* loss_tmp = nullptr;
@@ -184,6 +184,10 @@ struct acme_dqn : PlaneGuard {
   // (ACME_V_UPDATE_RIDER=0 at creation: the separate launch; the same bits).
   bool update_rider = true;
   int64_t rider_launches = 0;
+  // The online head inside the loss launch (launch_dqn_head_loss_dz).  ACME_V_HEAD_FUSE=0 at
+  // creation: fc_head_fwd + loss_head_dz, the launches it replaced (the same bits;
+  // tests/test_loss_tail_gpu.py).
+  bool head_fuse = true;
   // The step's forwards with conv3 inside conv2's launch, so that x2 stays in LDS wherever the
   // backward does not read it (torso.h keep_x2; ACME_V_FUSE_X2 at creation: 0 the separate
   // conv3_fwd launches, 1 the target forward fused, 2 the online forward, 3 both; the same bits).
@@ -396,7 +400,7 @@ int nature_forward_p3(acme_dqn* l, const float* prm, uint16_t* wpl, const torso:
                        : fc_fwd_gemm<128>(l, "fc_fwd", p, splits, st);
     if (rc != ACME_OK) return rc;
     // The online forward of a step: the head runs inside the loss launch (nature_backward).
-    if (defer_head &&
+    if (defer_head && l->head_fuse &&
         dqn_head_loss_dz_fusable(kHidden, l->cfg.num_actions, splits, P(l, prm, l->t_vw),
                                  P(l, prm, l->t_aw), P(l, prm, l->t_fcb))) {
       l->step.head_deferred = true;
@@ -563,7 +567,8 @@ int nature_backward(acme_dqn* l, const StepPlan& plan, const void* o_tm1, int B,
     rc = launch_dqn_head_loss_dz(la, l->slab, s.head_splits, kHidden, P(l, prm, l->t_fcb),
                                  P(l, prm, l->t_vw), P(l, prm, l->t_vb), P(l, prm, l->t_aw),
                                  P(l, prm, l->t_ab), l->hid, l->dzhp.p, l->dzhp.stride,
-                                 l->dzhp.sc, st);
+                                 l->dzhp.sc, st,
+                                 l->stamps && B <= 4096 ? l->stamps + (int64_t)5 * 4096 * 8 : nullptr);
     if (rc != ACME_OK) return rc;
   } else if (p3 && s.loss_pending) {  // the loss and the head dZ planes, one launch
     s.loss_pending = false;
@@ -759,6 +764,7 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
   l->single_role = tune_variant("WSN") == 1;
   l->bk32 = tune_variant("BK32") == 1;
   l->update_rider = tune_variant("UPDATE_RIDER", kUpdateRiderDefault) != 0;
+  l->head_fuse = tune_variant("HEAD_FUSE", 1) != 0;
   l->fuse_x2 = tune_variant("FUSE_X2", torso::kFuseX2Default) & 3;
   l->stamps_on = tune_variant("STAMPS") == 1;
   const int A = cfg->num_actions;
@@ -887,9 +893,10 @@ int acme_dqn_create(const acme_dqn_config* cfg, acme_dqn** out) {
       (rc = dev_alloc(l, &l->g, (int64_t)B)) || (rc = dev_alloc(l, &l->a_cache, (int64_t)B)) ||
       (rc = dev_alloc(l, &l->loss_tmp, 4)) || (rc = dev_alloc(l, &l->td_tmp, (int64_t)B)) ||
       (rc = dev_alloc(l, &l->prio_tmp, (int64_t)B)) ||
-      (l->stamps_on && (rc = dev_alloc(l, &l->stamps, (int64_t)5 * 4096 * 8))))
+      (l->stamps_on && (rc = dev_alloc(l, &l->stamps, (int64_t)6 * 4096 * 8))))
     return fail(rc);
-  if (l->stamps_on) {  // [fc_fwd, conv1, conv2, conv3, update][4096][8] (one learner at a time)
+  // [fc_fwd, conv1, conv2, conv3, update, head_loss_dz][4096][8] (one learner at a time)
+  if (l->stamps_on) {
     for (int i = 0; i < 3; ++i) torso::g_stamps_conv[i] = l->stamps + (int64_t)(i + 1) * 4096 * 8;
     g_update_stamps = l->stamps + (int64_t)4 * 4096 * 8;
   }
@@ -1054,7 +1061,7 @@ int acme_dqn_debug_buffer(const acme_dqn* l, const char* name, const float** out
     const char* n;
     const float* p;
     int64_t c;
-  } tab[] = {{"gemm_stamps", reinterpret_cast<const float*>(l->stamps), 2 * 5 * 4096 * 8},
+  } tab[] = {{"gemm_stamps", reinterpret_cast<const float*>(l->stamps), 2 * 6 * 4096 * 8},
              {"x1", l->x1, 2 * B * 441 * 32}, {"x2", l->x2, 2 * B * kFlat},
              {"x3", l->x3, 2 * B * kFlat},    {"hid", l->hid, 2 * B * 2 * kHidden},
              {"dzh", l->dzh, B * 2 * kHidden}, {"dz3", l->dz3, B * kFlat},

@@ -154,13 +154,13 @@ int64_t dqn_loss_head_dz_blocks(int B, int H);
 // The online duelling head (from the fc split-K slab of 2B rows: o_tm1 then o_t) fused with
 // the loss and the head dZ planes: one block per batch row; writes hid, args.q_on, the
 // loss outputs and args.loss_part[b] (B partials).  Nature head only (H = 512, A = 18,
-// splits 4 or 8): dqn_head_loss_dz_fusable.
+// splits 4 or 8): dqn_head_loss_dz_fusable.  stamps (timing experiment): [B][8] phase stamps.
 bool dqn_head_loss_dz_fusable(int H, int A, int splits, const float* wv, const float* wa,
                               const float* fcb);
 int launch_dqn_head_loss_dz(const LossArgs& args, const float* slab, int splits, int H,
                             const float* fcb, const float* wv, const float* bv, const float* wa,
                             const float* ba, float* hid, uint16_t* planes, int64_t pstride,
-                            gemm::PScale* sc, hipStream_t st);
+                            gemm::PScale* sc, hipStream_t st, uint64_t* stamps = nullptr);
 // loss[0] = (sum of the n partials, in order) / mean_over.
 int launch_dqn_loss_sum(const double* part, int64_t n, int mean_over, float* loss, hipStream_t st);
 

@@ -247,17 +247,49 @@ constexpr int kLossThreads = 1024;
 struct LossRow {
   float g, td, hub_w;
 };
-__device__ __forceinline__ LossRow loss_row(const LossArgs& p, int b, double wmax) {
-  const int B = p.B, A = p.A;
-  const float* qt = p.q_on + (size_t)b * A;
-  const float* qs = p.q_on + (size_t)(B + b) * A;
-  const float* qv = p.q_tg + (size_t)b * A;
+// The importance weight's numerator (1 / prob)^beta, in f32 for the JAX form (held in a double:
+// the cast back is exact).
+__device__ __forceinline__ double loss_weight_num(const LossArgs& p, double prob) {
+  return p.jax ? (double)powf((float)(1.0 / prob), p.beta) : pow(1.0 / prob, (double)p.beta);
+}
+// Where loss_row reads transition b from.  Global memory: the q rows the head launch wrote,
+// the batch's scalars, the weight's numerator computed on demand.
+struct LossRowGlobal {
+  const LossArgs& p;
+  const float *qt, *qs, *qv;  // rows b of q_tm1, q_t_selector and q_t_value
+  int b;
+  __device__ LossRowGlobal(const LossArgs& p_, int b_)
+      : p(p_), qt(p_.q_on + (size_t)b_ * p_.A), qs(p_.q_on + (size_t)(p_.B + b_) * p_.A),
+        qv(p_.q_tg + (size_t)b_ * p_.A), b(b_) {}
+  __device__ int action() const { return p.a[b]; }
+  __device__ float reward() const { return p.r[b]; }
+  __device__ float discount() const { return p.d[b]; }
+  __device__ double prob() const { return p.probs[b]; }
+  __device__ double weight_num(double prob) const { return loss_weight_num(p, prob); }
+};
+// Staged by the caller (dqn_head_loss_dz_kernel): the q rows in LDS, the scalars in registers
+// and the weight's numerator already computed, all before the row's q values exist.
+struct LossRowStaged {
+  const float *qt, *qs, *qv;
+  int ab;
+  float r, d;
+  double num;
+  __device__ int action() const { return ab; }
+  __device__ float reward() const { return r; }
+  __device__ float discount() const { return d; }
+  __device__ double prob() const { return 0.0; }  // only weight_num's argument
+  __device__ double weight_num(double) const { return num; }
+};
+template <class Src>
+__device__ __forceinline__ LossRow loss_row(const LossArgs& p, const Src& src, double wmax) {
+  const int A = p.A;
+  const float *qt = src.qt, *qs = src.qs, *qv = src.qv;
   // The row's scalars first (and q_tm1[a], which depends only on a), so their latency
   // overlaps the argmax's loads.
-  const int ab = p.a[b];
-  float r = p.r[b];
-  const float dgv = p.d[b];
-  const double prob = p.probs[b];
+  const int ab = src.action();
+  float r = src.reward();
+  const float dgv = src.discount();
+  const double prob = src.prob();
   const float qa = qt[ab];
   // tf.argmax: first maximal index.  The selector row is read 8 entries at a time, all 8
   // loads issued before the compares (clamped addresses): one latency per 8 actions
@@ -287,15 +319,19 @@ __device__ __forceinline__ LossRow loss_row(const LossArgs& p, int b, double wma
   const float quad = fminf(ax, p.delta);
   const float lin = ax - quad;
   const float hub = __fadd_rn(__fmul_rn(0.5f, __fmul_rn(quad, quad)), __fmul_rn(p.delta, lin));
+  const double num = src.weight_num(prob);
   float wf;
   if (p.jax) {  // ((1 / probs).astype(f32) ** beta) / max, all in f32 (jax/dqn/learning.py:94-96)
-    wf = __fdiv_rn(powf((float)(1.0 / prob), p.beta), (float)wmax);
+    wf = __fdiv_rn((float)num, (float)wmax);
   } else {      // f64 weights cast at the multiply (tf/dqn/learning.py:138-143)
-    wf = (float)(pow(1.0 / prob, (double)p.beta) / wmax);
+    wf = (float)(num / wmax);
   }
   const float dtd = fminf(fmaxf(td, -p.delta), p.delta);  // d huber / d td
   const float inv_b = 1.f / (float)p.mean_over;
   return LossRow{-(inv_b * wf * dtd), td, hub * wf};
+}
+__device__ __forceinline__ LossRow loss_row(const LossArgs& p, int b, double wmax) {
+  return loss_row(p, LossRowGlobal(p, b), wmax);
 }
 
 __global__ void __launch_bounds__(kLossThreads) dqn_loss_kernel(LossArgs p) {
@@ -794,19 +830,65 @@ __global__ void __launch_bounds__(256) dqn_loss_head_dz_kernel(
 // row b as planes from the registers that hold its units and their weights (head_dz8's
 // terms in its order), masked by its ReLU.  One launch for the online head, the loss and
 // the head dZ: the head's launch and its boundary leave the step's critical path.
+// Timing experiment (ACME_V_STAMPS=1, tools/head_loss_stamps.py): thread 0 of block b stamps
+// stamps[8 b + 2 + i] with the shader clock (s_memtime) at entry (0), after the slab loads and
+// the partial dot products (1), the reductions (2), the q rows (3), the loss row (4) and at
+// exit (5); [8 b] and [8 b + 1] take the 100-MHz clock at entry and exit.
+#define HEAD_STAMP(i)                                                       \
+  do {                                                                      \
+    if (stamps && threadIdx.x == 0) {                                       \
+      if ((i) == 0) stamps[8 * blockIdx.x] = wall_clock64();                \
+      if ((i) == 5) stamps[8 * blockIdx.x + 1] = wall_clock64();            \
+      stamps[8 * blockIdx.x + 2 + (i)] = __builtin_amdgcn_s_memtime();      \
+    }                                                                       \
+  } while (0)
 template <int SPL, int A>
 __global__ void __launch_bounds__(256) dqn_head_loss_dz_kernel(
     LossArgs p, const float* __restrict__ slab, const float* __restrict__ fcb,
     const float* __restrict__ wv, const float* __restrict__ bv, const float* __restrict__ wa,
     const float* __restrict__ ba, float* __restrict__ hid, uint16_t* __restrict__ planes,
-    int64_t pstride, gemm::PScale* __restrict__ sc) {
+    int64_t pstride, gemm::PScale* __restrict__ sc, uint64_t* __restrict__ stamps) {
   constexpr int N4 = 256, HALF = 128, R = 2, H = 512;
+  // The launch is one round of blocks, so its time is one block's dependency chain.  What the
+  // loss row needs and the slab does not decide is therefore loaded and computed under the
+  // slab loads: wave kLossWave takes the normaliser (all B probabilities, one wave-wide min:
+  // exact in any order) and its f64 pow, wave kNumWave the row's own weight numerator (the
+  // second pow), wave 0 the head biases; the row's scalars and its q_t_value row wait in
+  // registers / LDS.  After the reductions the q rows stay in LDS for the loss thread (the
+  // same floats that go to global memory), which is lane 0 of kLossWave.
+  constexpr int kLossWave = 3, kNumWave = 2;
+  static_assert(A + 1 <= 64 && R * A <= 64, "one lane per head output");
+  HEAD_STAMP(0);
   __shared__ float part[R][A + 1][HALF];
   __shared__ float dots[R][A + 1];
-  __shared__ double red[4];
+  __shared__ float qrow[R][A];      // q_tm1 row b and q_t_selector row B + b
+  __shared__ float s_qtg[A];        // q_t_value row b
+  __shared__ float s_hbias[A + 1];  // ba[0 .. A-1], bv[0]
+  __shared__ double s_num;
   __shared__ float s_g;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int B = p.B, b = blockIdx.x;
+  // The early loads come first in program order: loads return in order, so what waits for
+  // them must not wait for the slab's as well.
+  double pmin = INFINITY, prob_b = 1.0;
+  float r_b = 0.f, d_b = 0.f, qtg_l = 0.f, hbias_l = 0.f;
+  if (wave == kLossWave) {
+    for (int i0 = 0; i0 < B; i0 += 64 * 8) {
+      double pv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) pv[k] = p.probs[min(i0 + 64 * k + lane, B - 1)];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) pmin = fmin(pmin, pv[k]);
+    }
+    r_b = p.r[b];
+    d_b = p.d[b];
+    if (lane < A) qtg_l = p.q_tg[(size_t)b * A + lane];
+  } else if (wave == kNumWave) {
+    prob_b = p.probs[b];
+  } else if (wave == 0) {
+    if (lane <= A) hbias_l = lane == A ? bv[0] : ba[lane];
+  }
+  const int ab = p.a[b];
   const int64_t count4 = (int64_t)2 * B * N4;  // the online slab holds 2B rows
   const f32x4* s4 = reinterpret_cast<const f32x4*>(slab);
   f32x4 sp[R][SPL];
@@ -827,13 +909,20 @@ __global__ void __launch_bounds__(256) dqn_head_loss_dz_kernel(
     w[0] = reinterpret_cast<const f32x4*>(wv)[c];
   }
   const f32x4 bias = reinterpret_cast<const f32x4*>(fcb)[t];
-  const int ab = p.a[b];
-  // Importance-weight normaliser: max_b (1/p_b)^beta = (1/min_b p_b)^beta.
-  double pmin = INFINITY;
-  for (int i = t; i < B; i += 256) pmin = fmin(pmin, p.probs[i]);
+  // Under the slab loads: the importance-weight normaliser max_b (1/p_b)^beta =
+  // (1/min_b p_b)^beta in every lane of the loss wave, and the row's own numerator.
+  double wmax = 0.0;
+  if (wave == kLossWave) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) pmin = fmin(pmin, __shfl_xor(pmin, o, 64));
-  if (lane == 0) red[wave] = pmin;
+    for (int o = 32; o > 0; o >>= 1) pmin = fmin(pmin, __shfl_xor(pmin, o, 64));
+    if (p.global_min_prob) pmin = *p.global_min_prob;
+    wmax = p.jax ? (double)powf((float)(1.0 / pmin), p.beta) : pow(1.0 / pmin, (double)p.beta);
+    if (lane < A) s_qtg[lane] = qtg_l;
+  } else if (wave == kNumWave) {
+    if (lane == 0) s_num = loss_weight_num(p, prob_b);
+  } else if (wave == 0) {
+    if (lane <= A) s_hbias[lane] = hbias_l;
+  }
   f32x4 h_own;  // hidden row b, this thread's units (the dZ mask)
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -866,29 +955,46 @@ __global__ void __launch_bounds__(256) dqn_head_loss_dz_kernel(
     }
   }
   __syncthreads();
-  for (int j = wave; j < R * (A + 1); j += 4) {
+  HEAD_STAMP(1);
+  // Each output summed by one wave in a fixed order (lane pairs, then a shuffle tree), the
+  // bias from LDS; unrolled, so a wave's outputs advance through their trees together.
+  // (A wave past the last output sums a clamped duplicate it never stores: no branch
+  // between the trees.)
+  constexpr int kOuts = R * (A + 1), kPerWave = (kOuts + 3) / 4;
+  float xs[kPerWave];
+#pragma unroll
+  for (int i = 0; i < kPerWave; ++i) {
+    const int j = min(wave + 4 * i, kOuts - 1);
     const int r = j / (A + 1), o = j - r * (A + 1);
     float x = part[r][o][2 * lane] + part[r][o][2 * lane + 1];
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    if (lane == 0) dots[r][o] = x + (o == A ? bv[0] : ba[o]);
+    xs[i] = x;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < kPerWave; ++i) {
+      const int j = wave + 4 * i;
+      const int r = j / (A + 1), o = j - r * (A + 1);
+      if (j < kOuts) dots[r][o] = xs[i] + s_hbias[o];
+    }
   }
   __syncthreads();
-  if (t < R * A) {
-    const int r = t / A, jj = t - r * A;
+  HEAD_STAMP(2);
+  if (wave == kLossWave && lane < R * A) {
+    const int r = lane / A, jj = lane - r * A;
     float mean = 0.f;
     for (int k = 0; k < A; ++k) mean += dots[r][k];
     mean /= (float)A;
-    const_cast<float*>(p.q_on)[(size_t)(r == 0 ? b : B + b) * A + jj] =
-        dots[r][A] + (dots[r][jj] - mean);
+    const float q = dots[r][A] + (dots[r][jj] - mean);
+    qrow[r][jj] = q;
+    const_cast<float*>(p.q_on)[(size_t)(r == 0 ? b : B + b) * A + jj] = q;
   }
-  __syncthreads();  // the block's q rows are in global memory for loss_row
-  if (t == 0) {
-    pmin = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-    if (p.global_min_prob) pmin = *p.global_min_prob;
-    const double wmax = p.jax ? (double)powf((float)(1.0 / pmin), p.beta)
-                              : pow(1.0 / pmin, (double)p.beta);
-    const LossRow row = loss_row(p, b, wmax);
+  __syncthreads();  // the block's q rows are in LDS for loss_row
+  HEAD_STAMP(3);
+  if (wave == kLossWave && lane == 0) {
+    const LossRow row =
+        loss_row(p, LossRowStaged{qrow[0], qrow[1], s_qtg, ab, r_b, d_b, s_num}, wmax);
     s_g = row.g;
     p.g[b] = row.g;
     p.td[b] = row.td;
@@ -897,6 +1003,7 @@ __global__ void __launch_bounds__(256) dqn_head_loss_dz_kernel(
     p.loss_part[b] = (double)row.hub_w;
   }
   __syncthreads();
+  HEAD_STAMP(4);
   // dZ of hidden units 4c .. 4c+3 of this thread's half (head_dz8's terms, in its order).
   const float gb = s_g;
   float v4[4];
@@ -921,7 +1028,9 @@ __global__ void __launch_bounds__(256) dqn_head_loss_dz_kernel(
   const int64_t i4 = ((int64_t)b * 2 * H + (adv ? H : 0) + 4 * c) / 4;
   const float mx = store_planes4(planes, pstride, i4, d, sc->w);
   gemm::amax_commit(sc, mx);
+  HEAD_STAMP(5);
 }
+#undef HEAD_STAMP
 
 // dZ of the fused hidden layer as planes, 8 consecutive units per thread:
 // k < H: g_b wv[k];  k >= H: g_b (wa[k-H][a_b] - mean_j wa[k-H][j]); masked by hid > 0.
@@ -1563,16 +1672,16 @@ bool dqn_head_loss_dz_fusable(int H, int A, int splits, const float* wv, const f
 int launch_dqn_head_loss_dz(const LossArgs& args, const float* slab, int splits, int H,
                             const float* fcb, const float* wv, const float* bv, const float* wa,
                             const float* ba, float* hid, uint16_t* planes, int64_t pstride,
-                            gemm::PScale* sc, hipStream_t st) {
+                            gemm::PScale* sc, hipStream_t st, uint64_t* stamps) {
   ACME_CHECK_ARG(dqn_head_loss_dz_fusable(H, args.A, splits, wv, wa, fcb) && args.loss_part &&
                      planes && sc && args.B >= 1,
                  "bad fused head / loss / head dZ arguments");
   if (splits == 8)
     dqn_head_loss_dz_kernel<8, 18><<<(unsigned)args.B, 256, 0, st>>>(args, slab, fcb, wv, bv, wa, ba,
-                                                                   hid, planes, pstride, sc);
+                                                                   hid, planes, pstride, sc, stamps);
   else
     dqn_head_loss_dz_kernel<4, 18><<<(unsigned)args.B, 256, 0, st>>>(args, slab, fcb, wv, bv, wa, ba,
-                                                                   hid, planes, pstride, sc);
+                                                                   hid, planes, pstride, sc, stamps);
   ACME_LAUNCH_CHECK();
   return ACME_OK;
 }
