@@ -104,6 +104,10 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 __device__ __forceinline__ u32x4 zero_u4() { return u32x4{0u, 0u, 0u, 0u}; }
 
+// The two register sets of a double-buffered stager, as tags: fetch(Set0{}, ..).
+using Set0 = std::integral_constant<int, 0>;
+using Set1 = std::integral_constant<int, 1>;
+
 // Byte offset of a unit of zeros: beyond every plane's descriptor range.
 constexpr uint32_t kOOB = 0x80000000u;
 
@@ -667,6 +671,17 @@ struct P3Core {
   }
 };
 
+// Grid slice z's k range: its split (0 for a kZClass problem) covers [kbeg, kend) in nk stages.
+struct KRange {
+  int split, kbeg, kend, nk;
+};
+template <int BK, class P>
+__device__ __forceinline__ KRange k_range(const P& p, int z) {
+  const int split = HasZClass<P>::value ? 0 : z, kbeg = split * p.k_chunk;
+  const int kend = kbeg + p.k_chunk > p.K ? p.K : kbeg + p.k_chunk;
+  return KRange{split, kbeg, kend, kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0};
+}
+
 // Register-staged kernel: global -> VGPR -> LDS, two LDS stages; with DEEP two register
 // sets so a stage's loads are issued two stages before its compute.
 // (The block's work as a function of its placement, shared by gemm_p3_kernel and
@@ -684,11 +699,7 @@ __device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& b
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int m0 = bp.m0, n0 = bp.n0;
-  const int split = HasZClass<P>::value ? 0 : bp.z;
-  const int kbeg = split * p.k_chunk;
-  int kend = kbeg + p.k_chunk;
-  if (kend > p.K) kend = p.K;
-  const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+  const KRange kr = k_range<BK>(p, bp.z);
 
   typename P::ARow arow[PA::PER_THREAD];
   typename P::BRow brow[PB::PER_THREAD];
@@ -713,7 +724,7 @@ __device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& b
     for (int i = 0; i < PA::PER_THREAD; ++i) {
       const int u = tid + i * NT;
       const int kk = PA::kk_of(u);
-      const uint32_t off = (PA::owns(u) && k0 + kk < kend) ? p.a_off(arow[i], k0, kk) : kOOB;
+      const uint32_t off = (PA::owns(u) && k0 + kk < kr.kend) ? p.a_off(arow[i], k0, kk) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NPA; ++pl) {
         ra[set][i][pl] = load_a_unit<P>(srcA[pl], off);
@@ -723,7 +734,7 @@ __device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& b
     for (int i = 0; i < PB::PER_THREAD; ++i) {
       const int u = tid + i * NT;
       const int kk = PB::kk_of(u);
-      const uint32_t off = (PB::owns(u) && k0 + kk < kend) ? p.b_off(brow[i], k0, kk) : kOOB;
+      const uint32_t off = (PB::owns(u) && k0 + kk < kr.kend) ? p.b_off(brow[i], k0, kk) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NPB; ++pl)
         rb[set][i][pl] =
@@ -762,14 +773,12 @@ __device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& b
     C::mma(sa, sa + PA::BYTES, wm, wn, lane, acc, do_colsum);
   };
 
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
   if constexpr (DEEP) {
-    if (nk > 0) {
-      fetch(S0{}, kbeg);
-      stash(S0{}, 0);
+    if (kr.nk > 0) {
+      fetch(Set0{}, kr.kbeg);
+      stash(Set0{}, 0);
     }
-    if (nk > 1) fetch(S1{}, kbeg + BK);
+    if (kr.nk > 1) fetch(Set1{}, kr.kbeg + BK);
     __syncthreads();
     // Iteration kt: LDS buffer kt & 1 holds stage kt, register set (kt + 1) & 1 holds
     // stage kt + 1 (loaded during iteration kt - 1); stage kt + 2 is fetched into set
@@ -789,36 +798,36 @@ __device__ __forceinline__ void gemm_p3_block(const P& p_in, const BlockPlace& b
         const uint8_t* sa = smem + set * STAGE;
         C::template mma<0, 1>(sa, sa + PA::BYTES, wm, wn, lane, acc, do_colsum);
         stash(Other{}, set ^ 1);
-        fetch(S, kbeg + (kt + 2) * BK);
+        fetch(S, kr.kbeg + (kt + 2) * BK);
         C::template mma<1, 2>(sa, sa + PA::BYTES, wm, wn, lane, acc, do_colsum);
       } else {
         stash(Other{}, set ^ 1);
-        fetch(S, kbeg + (kt + 2) * BK);
+        fetch(S, kr.kbeg + (kt + 2) * BK);
         compute(set);
       }
       __syncthreads();
     };
     int kt = 0;
-    for (; kt + 1 < nk; kt += 2) {
-      iter(S0{}, kt);
-      iter(S1{}, kt + 1);
+    for (; kt + 1 < kr.nk; kt += 2) {
+      iter(Set0{}, kt);
+      iter(Set1{}, kt + 1);
     }
-    if (kt < nk) iter(S0{}, kt);
+    if (kt < kr.nk) iter(Set0{}, kt);
   } else {
-    if (nk > 0) {
-      fetch(S0{}, kbeg);
-      stash(S0{}, 0);
+    if (kr.nk > 0) {
+      fetch(Set0{}, kr.kbeg);
+      stash(Set0{}, 0);
     }
     __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool more = kt + 1 < nk;
-      if (more) fetch(S0{}, kbeg + (kt + 1) * BK);
+    for (int kt = 0; kt < kr.nk; ++kt) {
+      const bool more = kt + 1 < kr.nk;
+      if (more) fetch(Set0{}, kr.kbeg + (kt + 1) * BK);
       compute(kt & 1);
-      if (more) stash(S0{}, (kt + 1) & 1);
+      if (more) stash(Set0{}, (kt + 1) & 1);
       __syncthreads();
     }
   }
-  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, split, acc, do_colsum);
+  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, kr.split, acc, do_colsum);
 }
 
 template <int BM, int BN, int WM, int WN, int BK, bool DEEP, class P>
@@ -880,11 +889,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3g_kernel(const P p_in, in
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int m0 = bp.m0, n0 = bp.n0;
-  const int split = HasZClass<P>::value ? 0 : bp.z;
-  const int kbeg = split * p.k_chunk;
-  int kend = kbeg + p.k_chunk;
-  if (kend > p.K) kend = p.K;
-  const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+  const KRange kr = k_range<BK>(p, bp.z);
 
   // The unit each lane fetches for each of its wave's DMA blocks.
   typename P::ARow arow[PWA];
@@ -914,14 +919,14 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3g_kernel(const P p_in, in
   // DMA of stage `st` (k0 = kbeg + st * BK) into LDS buffer `buf`; stages past the end
   // fetch zeros (uniform instruction counts keep the vmcnt arithmetic exact).
   auto issue = [&](int st, int buf) {
-    const int k0 = kbeg + st * BK;
+    const int k0 = kr.kbeg + st * BK;
     uint8_t* sa = smem + buf * STAGE;
     uint8_t* sb = sa + PA::BYTES;
 #pragma unroll
     for (int j = 0; j < PWA; ++j) {
       const int b = wave + NW * j;
       const bool real = b < PA::BLOCKS;
-      const uint32_t off = (real && k0 + akk[j] < kend) ? p.a_off(arow[j], k0, akk[j]) : kOOB;
+      const uint32_t off = (real && k0 + akk[j] < kr.kend) ? p.a_off(arow[j], k0, akk[j]) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NPA; ++pl)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -932,7 +937,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3g_kernel(const P p_in, in
     for (int j = 0; j < PWB; ++j) {
       const int b = wave + NW * j;
       const bool real = b < PB::BLOCKS;
-      const uint32_t off = (real && k0 + bkk[j] < kend) ? p.b_off(brow[j], k0, bkk[j]) : kOOB;
+      const uint32_t off = (real && k0 + bkk[j] < kr.kend) ? p.b_off(brow[j], k0, bkk[j]) : kOOB;
 #pragma unroll
       for (int pl = 0; pl < NPB; ++pl)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -951,7 +956,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3g_kernel(const P p_in, in
 #pragma unroll
   for (int st = 0; st < STAGES - 1; ++st) issue(st, st);
   int buf = 0;
-  for (int kt = 0; kt < nk; ++kt) {
+  for (int kt = 0; kt < kr.nk; ++kt) {
     __builtin_amdgcn_s_waitcnt(kWaitStage);  // this wave's DMA of stage kt has landed
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();            // ... and every wave's; buffer kt-1 is free
@@ -965,7 +970,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3g_kernel(const P p_in, in
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, split, acc, do_colsum);
+  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, kr.split, acc, do_colsum);
 #endif
 }
 
@@ -992,13 +997,7 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
   const bool producer = __builtin_amdgcn_readfirstlane(tid) >= NT;
   const int lane = tid & 63;
   const int m0 = bp.m0, n0 = bp.n0;
-  const int split = HasZClass<P>::value ? 0 : bp.z;
-  const int kbeg = split * p.k_chunk;
-  int kend = kbeg + p.k_chunk;
-  if (kend > p.K) kend = p.K;
-  const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
+  const KRange kr = k_range<BK>(p, bp.z);
 
   if (producer) {
     const int pt = tid - NT;
@@ -1018,12 +1017,12 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
     u32x4 ra[2][PA::PER_THREAD][NPA], rb[2][PB::PER_THREAD][NPB];
     auto fetch = [&](auto S, int st) {
       constexpr int set = decltype(S)::value;
-      const int k0 = kbeg + st * BK;
+      const int k0 = kr.kbeg + st * BK;
 #pragma unroll
       for (int i = 0; i < PA::PER_THREAD; ++i) {
         const int u = pt + i * NT;
         const int kk = PA::kk_of(u);
-        const uint32_t off = (PA::owns(u) && k0 + kk < kend) ? p.a_off(arow[i], k0, kk) : kOOB;
+        const uint32_t off = (PA::owns(u) && k0 + kk < kr.kend) ? p.a_off(arow[i], k0, kk) : kOOB;
 #pragma unroll
         for (int pl = 0; pl < NPA; ++pl) ra[set][i][pl] = load_a_unit<P>(srcA[pl], off);
       }
@@ -1031,7 +1030,7 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
       for (int i = 0; i < PB::PER_THREAD; ++i) {
         const int u = pt + i * NT;
         const int kk = PB::kk_of(u);
-        const uint32_t off = (PB::owns(u) && k0 + kk < kend) ? p.b_off(brow[i], k0, kk) : kOOB;
+        const uint32_t off = (PB::owns(u) && k0 + kk < kr.kend) ? p.b_off(brow[i], k0, kk) : kOOB;
 #pragma unroll
         for (int pl = 0; pl < NPB; ++pl)
           rb[set][i][pl] =
@@ -1061,12 +1060,12 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
       }
     };
 
-    fetch(S0{}, 0);
-    fetch(S1{}, 1);
-    stash(S0{}, 0);
-    fetch(S0{}, 2);
-    stash(S1{}, 1);
-    fetch(S1{}, 3);
+    fetch(Set0{}, 0);
+    fetch(Set1{}, 1);
+    stash(Set0{}, 0);
+    fetch(Set0{}, 2);
+    stash(Set1{}, 1);
+    fetch(Set1{}, 3);
     __syncthreads();
     // Iteration kt: stage kt + 2 sits in set kt % 2 (loaded in iteration kt - 2, or the
     // prologue); store it to buffer (kt + 2) % 3, then load stage kt + 4 into that set.
@@ -1079,11 +1078,11 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
       __syncthreads();
     };
     int kt = 0;
-    for (; kt + 1 < nk; kt += 2) {
-      iter(S0{}, kt);
-      iter(S1{}, kt + 1);
+    for (; kt + 1 < kr.nk; kt += 2) {
+      iter(Set0{}, kt);
+      iter(Set1{}, kt + 1);
     }
-    if (kt < nk) iter(S0{}, kt);
+    if (kt < kr.nk) iter(Set0{}, kt);
     // The consumers' epilogue barriers.
     if constexpr (HasStore8<P>::value) {
 #pragma unroll
@@ -1119,8 +1118,8 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
     // 1's, so no MFMA waits on the LDS latency of its own reads.
     typename C::FragA fa0, fa1;
     typename C::FragB fb0, fb1;
-    if (nk > 0) C::read_frags(smem, smem + PA::BYTES, wm, wn, 0, lane, fa0, fb0);
-    for (int kt = 0; kt < nk; ++kt) {
+    if (kr.nk > 0) C::read_frags(smem, smem + PA::BYTES, wm, wn, 0, lane, fa0, fb0);
+    for (int kt = 0; kt < kr.nk; ++kt) {
       const uint8_t* sa = smem + rbuf * STAGE;
       rbuf = rbuf == RING - 1 ? 0 : rbuf + 1;
       const uint8_t* na = smem + rbuf * STAGE;
@@ -1139,7 +1138,7 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
       __syncthreads();
     }
   } else {
-    for (int kt = 0; kt < nk; ++kt) {
+    for (int kt = 0; kt < kr.nk; ++kt) {
       const uint8_t* sa = smem + rbuf * STAGE;
       C::mma(sa, sa + PA::BYTES, wm, wn, lane, acc, do_colsum);
       rbuf = rbuf == RING - 1 ? 0 : rbuf + 1;
@@ -1148,7 +1147,7 @@ __global__ void __launch_bounds__(128 * WM * WN) gemm_p3ws_kernel(const P p_in, 
   }
   if constexpr (HasStamps<P>::value)
     if (stamp) st_t2 = __builtin_amdgcn_s_memtime();
-  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, split, acc, do_colsum);
+  C::epilogue(p, smem, m0, n0, wave, wm, wn, lane, kr.split, acc, do_colsum);
   if constexpr (HasStamps<P>::value) {
     if (stamp) {
       const uint64_t t3 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();

@@ -26,6 +26,8 @@
 // Every sum keeps the separate kernels' order (32-k groups in k order, P3Core's terms), so x3,
 // and x2 where it is stored, are bit-identical to conv2_fwd / conv12_fwd followed by
 // conv3_fwd.  Where each region lies in each phase: gemm_p3i_geom.h C123Place / C23Place.
+// conv1 and conv2 of gemm_p3c12_kernel keep own rings and k loops (step-interleaved, whole stage
+// pairs), P3ImgPhase has gemm_p3i_kernel's (group-fenced): DESIGN 4.1 "five k loops".
 #pragma once
 
 #include "conv_p3.h"
@@ -176,10 +178,10 @@ struct P3ImgPhase {
     const int nk = (p.K + BK - 1) / BK;
     int kt = 0;
     for (; kt + 1 < nk; kt += 2) {
-      iter(std::integral_constant<int, 0>{}, kt);
-      iter(std::integral_constant<int, 1>{}, kt + 1);
+      iter(Set0{}, kt);
+      iter(Set1{}, kt + 1);
     }
-    if (kt < nk) iter(std::integral_constant<int, 0>{}, kt);
+    if (kt < nk) iter(Set0{}, kt);
   }
 };
 
@@ -261,8 +263,6 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int f = blockIdx.x;
   uint8_t* x1 = smem + Cfg::X1;
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
 
   // ---- Weight rings (one unit per owning thread per plane): thread tid owns unit
   // tid % UNITS of its stage's group tid / UNITS.
@@ -308,10 +308,10 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x4*>(s + pl * PB2::PLANE + PB2::offset(u2)) = r2[set][pl];
   };
-  fetch1(S0{}, 0);
-  fetch1(S1{}, BK1);
-  fetch2(S0{}, 0);
-  fetch2(S1{}, BK2);
+  fetch1(Set0{}, 0);
+  fetch1(Set1{}, BK1);
+  fetch2(Set0{}, 0);
+  fetch2(Set1{}, BK2);
 
   // ---- The frame image (f16 copy, pixel-pair units), each unit once; zero units.
   if constexpr (AU8<P1>::value) {  // the uint8 frame itself, widened exactly (gemm_p3i.h)
@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
     else if (tid < 16 + 16 * NP)
       *reinterpret_cast<u32x4*>(x1 + ((tid >> 4) - 1) * Cfg::PLANE2 + Cfg::ZERO2 + 16 * (tid & 15)) = zero_u4();
   }
-  stash1(S0{}, 0);
+  stash1(Set0{}, 0);
   __syncthreads();
 
   // ---- conv1: 8 waves x 64 rows.
@@ -400,8 +400,8 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
     };
     const int nk = p1.K / BK1;
     for (int kt = 0; kt < nk; kt += 2) {
-      iter(S0{}, kt);
-      iter(S1{}, kt + 1);
+      iter(Set0{}, kt);
+      iter(Set1{}, kt + 1);
     }
     typename Cfg::P1L q;
     q.M = (f + 1) * G1::OPIX < p1.M ? (f + 1) * G1::OPIX : p1.M;
@@ -412,7 +412,7 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
   }
 
   // ---- conv2 on the x1 image: 4 x 2 waves of 32 x 32.
-  stash2(S0{}, 0);
+  stash2(Set0{}, 0);
   __syncthreads();
   {
     const int wm = wave >> 1, wn = wave & 1;
@@ -449,8 +449,8 @@ __global__ void __launch_bounds__(512) gemm_p3c12_kernel(
     };
     const int nk = p2.K / BK2;
     for (int kt = 0; kt < nk; kt += 2) {
-      iter(S0{}, kt);
-      iter(S1{}, kt + 1);
+      iter(Set0{}, kt);
+      iter(Set1{}, kt + 1);
     }
     const int m2 = (f + 1) * I2::OPIX < p2.M ? (f + 1) * I2::OPIX : p2.M;
     if constexpr (!Cfg::C3) {

@@ -17,6 +17,8 @@
 // steps.  Within a stage the fragments are read in 32-k groups, each group's reads fenced
 // before its MFMAs, so the register count does not grow with BK and the k order -- hence
 // every sum -- is that of BK = 32.  The last stage is shorter when K % BK != 0.
+// Ring, fill and k loop are this kernel's own (group-fenced reads, short last stage); gemm_p3s.h
+// and gemm_p3c12.h hold four more: DESIGN 4.1 "five k loops" has how they differ and why.
 #pragma once
 
 #include "gemm_p3.h"
@@ -128,10 +130,8 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
     }
   };
 
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  fetch_b(S0{}, 0);
-  fetch_b(S1{}, BK);
+  fetch_b(Set0{}, 0);
+  fetch_b(Set1{}, BK);
 
   // ---- A: the block's frames, each unit of each plane loaded and stored once.
   constexpr int UB = 16;  // bytes per unit
@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
     if (tid < 16 * NPA)
       *reinterpret_cast<u32x4*>(smem + (tid >> 4) * PLANE + Cfg::ZERO + 16 * (tid & 15)) = zero_u4();
   }
-  stash_b(S0{}, 0);
+  stash_b(Set0{}, 0);
 
   // ---- This lane's GEMM rows (one per 32-row block of the wave's tile).
   typename GI::Lane ln[MT];
@@ -274,10 +274,10 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_p3i_kernel(const P p_in, in
   };
   int kt = 0;
   for (; kt + 1 < nk; kt += 2) {
-    iter(S0{}, kt);
-    iter(S1{}, kt + 1);
+    iter(Set0{}, kt);
+    iter(Set1{}, kt + 1);
   }
-  if (kt < nk) iter(S0{}, kt);
+  if (kt < nk) iter(Set0{}, kt);
 
   if constexpr (HasStamps<P>::value)
     if (stamp) st_t2 = __builtin_amdgcn_s_memtime();

@@ -11,6 +11,7 @@
 // through the two-stage register-staged ring (one 16-B unit per thread per plane).  The
 // epilogue is the problem's own (ReLU mask from the previous activation, plane stores).
 // Where the image's units lie and what each lane reads: gemm_p3i_geom.h ImgGeomSub.
+// Ring, fill and k loop: its own (step-interleaved, whole stage pairs; DESIGN 4.1 "five k loops").
 #pragma once
 
 #include "conv_p3.h"
@@ -103,10 +104,8 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
     for (int pl = 0; pl < NP; ++pl)
       *reinterpret_cast<u32x4*>(sb + pl * PB::PLANE + PB::offset(bu)) = rb[set][pl];
   };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  fetch_b(S0{}, 0);
-  fetch_b(S1{}, BK);
+  fetch_b(Set0{}, 0);
+  fetch_b(Set1{}, BK);
 
   // ---- A: the block's dZ images, each 16-B unit of each plane once.
   {
@@ -139,7 +138,7 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
     if (tid < 16 * NP)
       *reinterpret_cast<u32x4*>(smem + (tid >> 4) * PLANE + Cfg::ZERO + 16 * (tid & 15)) = zero_u4();
   }
-  stash_b(S0{}, 0);
+  stash_b(Set0{}, 0);
 
   // ---- This lane's rows of the class (their dZ anchors).
   typename GI::Lane ln[MT];
@@ -185,8 +184,8 @@ __global__ void __launch_bounds__(64 * 2 * G::S * G::S * FPB) gemm_p3s_kernel(
     __syncthreads();
   };
   for (int kt = 0; kt < nk; kt += 2) {
-    iter(S0{}, kt);
-    iter(S1{}, kt + 1);
+    iter(Set0{}, kt);
+    iter(Set1{}, kt + 1);
   }
 
   // Row m = m0 + half * 64 + i * 32 + r of class z; LDS staging region of this wave.
