@@ -139,6 +139,31 @@ class MPOOutputs(ctypes.Structure):
                 ("kl_mean_rel", c_vp), ("kl_stddev_rel", c_vp)]
 
 
+CRR_REDUCE = ("mean", "max", "min")      # ACME_CRR_REDUCE_*
+CRR_MODES = ("exp", "binary", "all")     # ACME_CRR_MODE_*
+
+
+class CRRConfig(ctypes.Structure):  # acme_crr_config
+    _fields_ = [("obs_dim", c_i32), ("act_dim", c_i32), ("max_batch", c_i32),
+                ("num_policy_layers", c_i32), ("policy_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("num_critic_layers", c_i32), ("critic_sizes", c_i32 * D4PG_MAX_LAYERS),
+                ("num_atoms", c_i32), ("vmin", c_f32), ("vmax", c_f32), ("discount", c_f32),
+                ("policy_learning_rate", c_f32), ("critic_learning_rate", c_f32),
+                ("adam_beta1", c_f32), ("adam_beta2", c_f32), ("adam_epsilon", c_f32),
+                ("clipping", c_i32), ("layer_norm_epsilon", c_f32),
+                ("init_scale", c_f32), ("min_scale", c_f32),
+                ("num_action_samples_td_learning", c_i32),
+                ("num_action_samples_policy_weight", c_i32),
+                ("baseline_reduce_function", c_i32), ("policy_improvement_modes", c_i32),
+                ("ratio_upper_bound", c_f32), ("beta", c_f32),
+                ("target_update_period", c_i32), ("sequence_length", c_i32),
+                ("seed", ctypes.c_uint64)]
+
+
+class CRROutputs(ctypes.Structure):
+    _fields_ = [("critic_loss", c_vp), ("policy_loss", c_vp), ("policy_loss_coef", c_vp)]
+
+
 IMPALA_TORSO_ATARI = 0
 IMPALA_TORSO_FLAT = 1
 
@@ -352,7 +377,8 @@ for _learner in (
         dict(prefix="d4pg", config=D4PGConfig, bind=5, actor_critic=(D4PGBatch, D4PGOutputs, 1)),
         dict(prefix="ddpg", config=DDPGConfig, bind=5, actor_critic=(D4PGBatch, D4PGOutputs, 1)),
         dict(prefix="mpo", config=MPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
-        dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2))):
+        dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
+        dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2))):
     _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -18,11 +18,11 @@
 // activate_final); policy head NearZeroInitializedLinear + TanhToSpec
 // (rescaling.py:55-74); critic head DiscreteValuedHead (distributional.py:36-67).
 //
-// One learner core, four handle types.  acme_d4pg, acme_ddpg, acme_mpo and acme_dmpo derive from
-// acme_actor_critic, whose Head says which step it takes; the flat-buffer layout, bind, the
-// step entry (checks, graph or eager, step count), the LayerNormMLP passes, the backward
-// launches, clip_and_adam and the debug-buffer lookup are written once over that core, and
-// the exports are one-line calls into them.
+// One learner core, five handle types.  acme_d4pg, acme_ddpg, acme_mpo, acme_dmpo and acme_crr
+// derive from acme_actor_critic, whose Head says which step it takes; the flat-buffer layout,
+// bind, the step entry (checks, graph or eager, step count), the LayerNormMLP passes, the
+// backward launches, clip_and_adam and the debug-buffer lookup are written once over that core,
+// and the exports are one-line calls into them.
 //
 // DDPG (acme_ddpg_*, acme/agents/tf/ddpg/learning.py:143-237) is Head::kScalar: the critic
 // is LayerNormMLP(critic_sizes + (1,)), and ddpg_head_td_kernel (head forward, TD loss
@@ -41,6 +41,12 @@
 // sampled rows and the bootstrap distribution of each state the mixture of its N sampled
 // distributions (dmpo_mix_loss_kernel, mpo_kernels.h).  Its step is dmpo_step_impl, built from
 // the blocks of mpo_step_impl and the categorical head's backward of d4pg_step_impl.
+//
+// CRR (acme_crr_*, acme/agents/tf/crr/recurrent_learning.py:197-377 with stateless networks) is
+// Head::kCrr: MPO's Gaussian policy head and DMPO's categorical critic without the duals, a
+// second set of sampled actions through the online critic for the value estimate, the
+// advantage-weighted behaviour-cloning loss and a target copy after the update.  Its kernels
+// are in crr_kernels.h, its step is crr_step_impl.
 //
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
@@ -101,14 +107,17 @@ enum class Head {
   kScalar,       // DDPG: one scalar, TD loss
   kMpo,          // MPO: scalar critic, Gaussian policy head, the dual variables
   kMpoCategorical,  // DMPO: MPO's policy side, D4PG's DiscreteValuedHead critic
+  kCrr,          // CRR: the Gaussian policy head, DMPO's critic, no duals
 };
 
 // The kinds with a Gaussian policy head, sampled actions and dual variables (MPO's policy side).
 constexpr bool has_duals(Head h) { return h == Head::kMpo || h == Head::kMpoCategorical; }
 // The kinds whose critic ends in a DiscreteValuedHead over the support `values`.
 constexpr bool is_categorical(Head h) {
-  return h == Head::kCategorical || h == Head::kMpoCategorical;
+  return h == Head::kCategorical || h == Head::kMpoCategorical || h == Head::kCrr;
 }
+// The kinds whose policy ends in a MultivariateNormalDiagHead.
+constexpr bool has_gauss_head(Head h) { return has_duals(h) || h == Head::kCrr; }
 
 }  // namespace
 
@@ -138,7 +147,7 @@ struct acme_actor_critic {
   float* ploss_part = nullptr;            // per-block dpg loss partials
   double* norm_part = nullptr;            // [2][kNormBlocks]
   float* norms = nullptr;                 // [2] global norms (policy, critic)
-  float* loss_tmp = nullptr;              // [2] critic / policy loss
+  float* loss_tmp = nullptr;              // [3] critic / policy loss, CRR's mean coefficient
   float* ce = nullptr;                    // [B] per-row cross-entropy (DDPG: 0.5 td^2)
   // Scalar heads (DDPG, MPO): the critic ends in one scalar, con.out / ctg.out hold q.
   float* td = nullptr;                    // [B] TD error
@@ -164,7 +173,17 @@ struct acme_actor_critic {
   // DMPO (acme_dmpo_create): the categorical head over the N B sampled rows (ctg.out holds
   // their logits, mb.sq their means) and the bootstrap mixture of each state.
   float* mixture = nullptr;               // [B][atoms] normalised mixture probabilities
-  // Captured step graphs, keyed by the batch / output pointers, B and the target copies.
+  // CRR (acme_crr_create): mb's policy-side buffers with both action sets in noise / act /
+  // tiled ([N_td R] rows for the target critic, then [N_pw R] for the online critic, whose
+  // logits follow the R rows of con.out), and the policy loss's per-state values.
+  acme_crr_config ccfg;
+  struct CrrBufs {
+    float *q_mean, *v_est, *adv, *coef, *logp;  // [B]
+    float* coef_part;                           // [ceil(B / 4)] per-block coefficient sums
+  } cb = {};
+  int64_t crr_rows = 0;                   // R of the last step (the debug buffers' packing)
+  // Captured step graphs, keyed by the batch / output pointers (MPO, DMPO, CRR: the noise
+  // pointer too), B and the target-copy flags (CRR's copy is the graph's last node).
   struct Graph {
     const void* key[kGraphKeys];
     int64_t B;
@@ -181,6 +200,7 @@ struct acme_d4pg : acme_actor_critic {};
 struct acme_ddpg : acme_actor_critic {};
 struct acme_mpo : acme_actor_critic {};
 struct acme_dmpo : acme_actor_critic {};
+struct acme_crr : acme_actor_critic {};
 
 namespace {
 
@@ -496,11 +516,13 @@ __device__ __forceinline__ RowSoftmax row_softmax(float x, bool on) {
 
 // The categorical loss of row `row` < B from the online critic's logits ql with their softmax
 // q and the target probabilities pj (lane = atom; D4PG: the target critic's softmax, DMPO: the
-// mixture over the sampled actions): l2_project, the cross entropy and dlogits.
+// mixture over the sampled actions): l2_project, the cross entropy and dlogits = (softmax -
+// target) / row_div (the batch size; CRR: R T / (T - 1)).
 __device__ __forceinline__ void categorical_loss_row(
     float ql, const RowSoftmax& q, float pj, float vi, int row, int lane,
     const float* __restrict__ r, const float* __restrict__ d, const float* __restrict__ values,
-    int B, int K, float discount, float* __restrict__ dlogits, float* __restrict__ ce_out) {
+    float row_div, int K, float discount, float* __restrict__ dlogits,
+    float* __restrict__ ce_out) {
   const bool on = lane < K;
   const float m2 = q.m, s2 = q.s, sm = q.p;
   const float vmin = values[0], vmax = values[K - 1];
@@ -523,7 +545,7 @@ __device__ __forceinline__ void categorical_loss_row(
   }
   const float logp = ql - m2 - logf(s2);
   const float ce = wave_sum(on ? -tgt * logp : 0.f);
-  if (on) dlogits[(size_t)row * K + lane] = (1.f / (float)B) * (sm - tgt);
+  if (on) dlogits[(size_t)row * K + lane] = (1.f / row_div) * (sm - tgt);
   if (lane == 0) ce_out[row] = ce;
 }
 
@@ -543,7 +565,8 @@ __device__ __forceinline__ void loss_row(float ql, float tl, int row, int lane,
     return;
   }
   const RowSoftmax t = row_softmax(tl, on);
-  categorical_loss_row(ql, q, t.p, vi, row, lane, r, d, values, B, K, discount, dlogits, ce_out);
+  categorical_loss_row(ql, q, t.p, vi, row, lane, r, d, values, (float)B, K, discount, dlogits,
+                       ce_out);
 }
 
 __global__ void __launch_bounds__(256) d4pg_loss_kernel(
@@ -644,6 +667,7 @@ __global__ void __launch_bounds__(256) ddpg_head_td_kernel(const HeadTdArgs a) {
 }
 
 #include "mpo_kernels.h"
+#include "crr_kernels.h"
 
 // ------------------------------------------------------------------ LayerNorm backward
 // Per row (kRows rows per block): dy = dLoss/d(LayerNorm output) (tanh' already
@@ -1183,9 +1207,9 @@ int ln_backward(acme_actor_critic* l, const NetDesc& d, const Acts& a, float* dy
 
 // Global-norm clipping + Adam (t = steps taken including this one) of the policy and critic
 // groups in the first `floats` floats.  The policy loss is the sum of ploss[0, n_ploss) over
-// div_ploss, the critic loss the mean of ce[0, B); a null output goes to loss_tmp.
+// div_ploss, the critic loss the sum of ce[0, B) over div_ce; a null output goes to loss_tmp.
 int clip_and_adam(acme_actor_critic* l, int64_t floats, const float* ploss, int n_ploss,
-                  float div_ploss, int B, float* policy_loss, float* critic_loss,
+                  float div_ploss, int B, float div_ce, float* policy_loss, float* critic_loss,
                   hipStream_t st) {
   ACME_PROF("d4pg_adam", st, 0.0, 7.0 * 4.0 * (double)floats);
   const int64_t n4 = floats / 4, pol4 = l->policy_flat / 4;
@@ -1200,7 +1224,7 @@ int clip_and_adam(acme_actor_critic* l, int64_t floats, const float* ploss, int 
   a.dev_step = l->dev_step; a.norms = l->norms;
   a.sum_a = ploss; a.n_a = n_ploss; a.div_a = div_ploss;
   a.out_a = policy_loss ? policy_loss : l->loss_tmp + 1;
-  a.sum_b = l->ce; a.n_b = B; a.div_b = (float)B;
+  a.sum_b = l->ce; a.n_b = B; a.div_b = div_ce;
   a.out_b = critic_loss ? critic_loss : l->loss_tmp;
   return launch_clip_adam(a, st);
 }
@@ -1292,7 +1316,8 @@ int d4pg_step_impl(acme_actor_critic* l, const acme_d4pg_batch* bt, const acme_d
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
   return clip_and_adam(l, l->flat, l->ploss_part, (int)ceil_div(2 * B, kRows), (float)B, B,
-                       out ? out->policy_loss : nullptr, out ? out->critic_loss : nullptr, st);
+                       (float)B, out ? out->policy_loss : nullptr,
+                       out ? out->critic_loss : nullptr, st);
 }
 
 // ------------------------------------------------------------------ MPO step
@@ -1431,11 +1456,12 @@ int mpo_loss_and_duals(acme_actor_critic* l, const acme_mpo_batch* bt, const acm
   return ACME_OK;
 }
 
-// Policy backward from dz[pL] (written by the loss kernel); leaves the first layer's weight
-// gradient in `g` for the critic's first backward launch.
-int mpo_policy_backward(acme_actor_critic* l, const acme_mpo_batch* bt, BwdGroup& g,
+// Policy backward from dz[pL] (written by the loss kernel) over the B rows `obs` the online
+// policy ran on; leaves the first layer's weight gradient in `g` for the critic's first
+// backward launch.
+int mpo_policy_backward(acme_actor_critic* l, int B, const float* obs, BwdGroup& g,
                         std::vector<LnReduce>& ln, hipStream_t st) {
-  const int B = (int)bt->batch, od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
   const NetDesc& pd = l->pol;
   const int pL = pd.nl - 1;
   auto& mb = l->mb;
@@ -1446,8 +1472,8 @@ int mpo_policy_backward(acme_actor_critic* l, const acme_mpo_batch* bt, BwdGroup
             Pm(l, l->grads, l->sb));
   if ((rc = lnmlp_backward_mlp(l, pd, l->pon, l->pdz, B, B, g, "mpo_bwd_phead", st, true)))
     return rc;
-  return ln_backward(l, pd, l->pon, l->pdz[0], B, B, false, bt->o_t, nullptr, od, 0, l->lnslab2,
-                     g, ln, st);
+  return ln_backward(l, pd, l->pon, l->pdz[0], B, B, false, obs, nullptr, od, 0, l->lnslab2, g,
+                     ln, st);
 }
 
 int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo_outputs* out,
@@ -1478,7 +1504,8 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
   }
   BwdGroup g;
   std::vector<LnReduce> ln;
-  if ((rc = mpo_loss_and_duals(l, bt, out, st)) || (rc = mpo_policy_backward(l, bt, g, ln, st)))
+  if ((rc = mpo_loss_and_duals(l, bt, out, st)) ||
+      (rc = mpo_policy_backward(l, B, bt->o_t, g, ln, st)))
     return rc;
   // Critic backward over the B TD rows; the head's weight gradient (one live column) and the
   // policy's first-layer weight gradient ride its first launch.
@@ -1490,7 +1517,8 @@ int mpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mpo
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
   // The duals' floats past critic_end are the finalize kernel's.
-  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, out ? out->policy_loss : nullptr,
+  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, (float)B,
+                       out ? out->policy_loss : nullptr,
                        out ? out->critic_loss : nullptr, st);
 }
 
@@ -1527,7 +1555,7 @@ int dmpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mp
     DmpoMixArgs a;
     a.c_logits = l->con.out; a.t_logits = l->ctg.out;
     a.r = bt->r_t; a.d = bt->d_t; a.values = l->values;
-    a.B = B; a.N = N; a.K = K; a.discount = l->cfg.discount;
+    a.B = B; a.N = N; a.K = K; a.discount = l->cfg.discount; a.row_div = (float)B;
     a.sq = mb.sq; a.mix = l->mixture; a.dlogits = l->dlogits; a.ce = l->ce;
     dmpo_mix_loss_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, st>>>(a);
     ACME_LAUNCH_CHECK();
@@ -1535,7 +1563,8 @@ int dmpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mp
   BwdGroup g;
   std::vector<LnReduce> ln;
   // The policy's backward first, as in MPO: no launch carries more than kZ weight gradients.
-  if ((rc = mpo_loss_and_duals(l, bt, out, st)) || (rc = mpo_policy_backward(l, bt, g, ln, st)))
+  if ((rc = mpo_loss_and_duals(l, bt, out, st)) ||
+      (rc = mpo_policy_backward(l, B, bt->o_t, g, ln, st)))
     return rc;
   // Critic backward over the B rows: the head's launch (its weight and input gradients) also
   // carries the policy's first-layer weight gradient.
@@ -1548,13 +1577,143 @@ int dmpo_step_impl(acme_actor_critic* l, const acme_mpo_batch* bt, const acme_mp
                         l->lnslab, g, ln, st)) ||
       (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
     return rc;
-  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, out ? out->policy_loss : nullptr,
+  return clip_and_adam(l, l->critic_end, mb.ploss, 1, 1.f, B, (float)B,
+                       out ? out->policy_loss : nullptr,
                        out ? out->critic_loss : nullptr, st);
 }
 
+// RCRRLearner._step (acme/agents/tf/crr/recurrent_learning.py:197-377) for stateless networks
+// on one stream, over the R = B (T - 1) transitions its loop over t unrolls into; every batch
+// mean of the reference is sum_rows / row_div with row_div = R T / (T - 1) (:327-334).
+//   online policy on o_tm1, target policy on o_t, the Gaussian head of both        (:250, :279)
+//   crr_sample_kernel: N_td actions per state from the target policy at o_t and N_pw from the
+//     online policy at o_tm1, the observations tiled beside them          (:253-257, :285-290)
+//   online critic on [o_tm1, a_tm1 ; tiled o_tm1, online samples] (R + N_pw R rows), target
+//     critic on the N_td R target samples, the DiscreteValuedHead of both   (:248, :262, :291)
+//   dmpo_mix_loss_kernel: the bootstrap mixture, the categorical loss, dlogits     (:265-276)
+//   crr_policy_loss_kernel: V, the advantage, the coefficient, -log pi(a_tm1) coef with its
+//     backward into the policy head                                                (:293-323)
+//   policy backward as MPO's, critic backward as DMPO's over the first R rows (no gradient
+//     through the sampled rows), clipping, two Adams                               (:337-359)
+//   target <- online AFTER the update when num_steps % period == 0                 (:361-371)
+// Launches at R = 256, policy 256x3, critic 512/512/256, no target copy: policy 3 + 1, sample 1,
+// critic 3 + 1 head, mixture loss 1, policy loss 1, policy backward 2 + 1, critic backward
+// 1 + 2 + 1 + 1, the coefficient's mean 1, clipping and Adam 2: 22, as DMPO (the one-wave mean
+// where mpo_finalize_kernel stands).
+int crr_step_impl(acme_actor_critic* l, const acme_crr_batch* bt, const acme_crr_outputs* out,
+                  bool copy_target, hipStream_t st) {
+  const acme_crr_config& cc = l->ccfg;
+  const int R = (int)bt->batch;
+  const int Ntd = cc.num_action_samples_td_learning, Npw = cc.num_action_samples_policy_weight;
+  const int od = l->cfg.obs_dim, ad = l->cfg.act_dim;
+  const NetDesc& pd = l->pol;
+  const NetDesc& cd = l->cri;
+  const int pL = pd.nl - 1, cL = cd.nl - 1, K = cd.nout;
+  const float row_div =
+      (float)((double)R * cc.sequence_length / (double)(cc.sequence_length - 1));
+  auto& mb = l->mb;
+  auto& cb = l->cb;
+  // The online samples' rows of the concatenated noise / actions / tiled buffers.
+  const float* act_on = mb.act + (size_t)Ntd * R * ad;
+  const float* tiled_on = mb.tiled + (size_t)Ntd * R * od;
+  int rc;
+  {
+    const NetIn pin[2] = {{l->params, bt->o_tm1, nullptr, bt->o_tm1, nullptr, R, R, &l->pon},
+                          {l->target, bt->o_t, nullptr, bt->o_t, nullptr, R, R, &l->ptg}};
+    if ((rc = lnmlp_forward_pair(l, pd, pin, od, 0, "crr_policy_ln", st))) return rc;
+    ACME_PROF("crr_gauss_head", st, 2.0 * 2.0 * 2.0 * R * (double)pd.sizes[pL] * ad, 0.0);
+    GaussHeadPair h;
+    set_gauss_head(l, h, 0, l->params, l->pon.h[pL], R, l->pon.out, l->pon.t, mb.sd_on);
+    set_gauss_head(l, h, 1, l->target, l->ptg.h[pL], R, l->ptg.out, l->ptg.t, mb.sd_t);
+    gauss_head_kernel<<<dim3((unsigned)ceil_div(R, 4), 2), 256, 0, st>>>(h);
+    ACME_LAUNCH_CHECK();
+  }
+  {
+    const int rows = (Ntd + Npw) * R;
+    ACME_PROF("crr_sample", st, 0.0, 4.0 * rows * (3.0 * ad + od));
+    CrrSampleArgs a;
+    a.mean_t = l->ptg.out; a.sd_t = mb.sd_t; a.mean_on = l->pon.out; a.sd_on = mb.sd_on;
+    a.noise_in = bt->noise; a.o_t = bt->o_t; a.o_tm1 = bt->o_tm1;
+    a.dev_step = l->dev_step; a.seed = cc.seed;
+    a.R = R; a.Ntd = Ntd; a.Npw = Npw; a.A = ad; a.od = od;
+    a.noise = mb.noise; a.act = mb.act; a.tiled = mb.tiled;
+    // One thread per tiled observation element as well: at rows = 1,280 a grid sized by the
+    // rows alone leaves the tiling's grid-stride loop 24 serial passes on five blocks.
+    const int64_t threads = (int64_t)rows * od;
+    crr_sample_kernel<<<(unsigned)ceil_div(threads, 256), 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+  }
+  {
+    const NetIn cin[2] = {
+        {l->params, bt->o_tm1, bt->a_tm1, tiled_on, act_on, R, R + Npw * R, &l->con},
+        {l->target, mb.tiled, mb.act, mb.tiled, mb.act, Ntd * R, Ntd * R, &l->ctg}};
+    if ((rc = critic_forward_pair(l, cin, st))) return rc;
+  }
+  {
+    ACME_PROF("crr_mix_loss", st, 0.0, 4.0 * (double)K * (Ntd * R + 3.0 * R));
+    DmpoMixArgs a;
+    a.c_logits = l->con.out; a.t_logits = l->ctg.out;
+    a.r = bt->r_t; a.d = bt->d_t; a.values = l->values;
+    a.B = R; a.N = Ntd; a.K = K; a.discount = l->cfg.discount; a.row_div = row_div;
+    a.sq = mb.sq; a.mix = l->mixture; a.dlogits = l->dlogits; a.ce = l->ce;
+    dmpo_mix_loss_kernel<<<(unsigned)ceil_div(R, 4), 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+  }
+  const int nblk = (int)ceil_div(R, 4);
+  {
+    ACME_PROF("crr_policy_loss", st, 0.0, 4.0 * (double)K * (Npw * R + R));
+    CrrLossArgs a;
+    a.logits = l->con.out; a.values = l->values;
+    a.a_tm1 = bt->a_tm1; a.mu = l->pon.out; a.sd = mb.sd_on; a.pre = l->pon.t;
+    a.R = R; a.N = Npw; a.K = K; a.A = ad; a.H = pd.sizes[pL]; a.act_fn = act_of_layer(pL);
+    a.reduce = cc.baseline_reduce_function; a.mode = cc.policy_improvement_modes;
+    a.beta = cc.beta; a.bound = cc.ratio_upper_bound; a.scale_mul = mpo_scale_mul(l);
+    a.row_div = row_div;
+    a.h = l->pon.h[pL]; a.wm = P(l, l->params, pd.ow); a.ws = P(l, l->params, l->sw);
+    a.q_mean = cb.q_mean; a.v_est = cb.v_est; a.adv = cb.adv; a.coef = cb.coef; a.logp = cb.logp;
+    a.dmean = mb.dmean; a.dpre = mb.dpre; a.dz = l->pdz[pL];
+    a.loss_part = l->ploss_part; a.coef_part = cb.coef_part;
+    crr_policy_loss_kernel<<<(unsigned)nblk, 256, 0, st>>>(a);
+    ACME_LAUNCH_CHECK();
+  }
+  BwdGroup g;
+  std::vector<LnReduce> ln;
+  // The policy's backward first, as in MPO: no launch carries more than kZ weight gradients.
+  if ((rc = mpo_policy_backward(l, R, bt->o_tm1, g, ln, st))) return rc;
+  // Critic backward as DMPO's over the first R rows of the online critic's activations.
+  add_wgrad(g, l->con.h[cL], R, cd.sizes[cL], l->dlogits, K, Pm(l, l->grads, cd.ow),
+            Pm(l, l->grads, cd.ob));
+  add_dgrad(g, l->dlogits, R, K, P(l, l->params, cd.ow), cd.sizes[cL], l->con.h[cL],
+            act_of_layer(cL), l->cdz[cL]);
+  if ((rc = lnmlp_backward_mlp(l, cd, l->con, l->cdz, R, R, g, "crr_bwd_chead", st, false)) ||
+      (rc = ln_backward(l, cd, l->con, l->cdz[0], R, R, false, bt->o_tm1, bt->a_tm1, od, ad,
+                        l->lnslab, g, ln, st)) ||
+      (rc = launch_bwd_last("d4pg_wgrad_first", g, ln, st)))
+    return rc;
+  {
+    // The logged mean coefficient (clip_adam's logged-loss path has room for two sums: the
+    // policy loss's block partials and ce go there).
+    ACME_PROF("crr_coef_mean", st, 0.0, 0.0);
+    float* dst = out && out->policy_loss_coef ? out->policy_loss_coef : l->loss_tmp + 2;
+    crr_coef_mean_kernel<<<1, 64, 0, st>>>(cb.coef_part, nblk, row_div, dst);
+    ACME_LAUNCH_CHECK();
+  }
+  if ((rc = clip_and_adam(l, l->critic_end, l->ploss_part, nblk, row_div, R, row_div,
+                          out ? out->policy_loss : nullptr, out ? out->critic_loss : nullptr,
+                          st)))
+    return rc;
+  if (copy_target) {
+    ACME_PROF("crr_target_copy", st, 0.0, 2.0 * 4.0 * (double)l->critic_end);
+    ACME_HIP_TRY(hipMemcpyAsync(l->target, l->params, (size_t)l->critic_end * sizeof(float),
+                                hipMemcpyDeviceToDevice, st));
+  }
+  return ACME_OK;
+}
+
 // ------------------------------------------------------------------ step graphs
-// The 20 launches of a step (18 for DDPG) are captured once per (batch pointers, outputs, B,
-// target copy) into a hipGraph on a private capture stream and replayed with one
+// The launches of a step (D4PG and MPO 20, DDPG 18, DMPO and CRR 22 and, on CRR's period, the
+// memcpy node of its post-update target copy) are captured once per (batch pointers, outputs,
+// B, target copy) into a hipGraph on a private capture stream and replayed with one
 // hipGraphLaunch on the caller's stream: the launch cost leaves the host critical path.
 // ACME_NO_GRAPH=1 disables capture; the section profiler also bypasses it (its event
 // records belong to individual launches).
@@ -1629,7 +1788,7 @@ int run_step(acme_actor_critic* l, const char* api, const Batch* batch,
 }
 
 // ------------------------------------------------------------------ the shared learner
-// The bodies behind the acme_d4pg_*, acme_ddpg_*, acme_mpo_* and acme_dmpo_* exports.
+// The bodies behind the acme_d4pg_*, acme_ddpg_*, acme_mpo_*, acme_dmpo_* and acme_crr_* exports.
 
 int ac_destroy(acme_actor_critic* l) {
   if (!l) return ACME_OK;
@@ -1668,15 +1827,16 @@ int check_config(const acme_d4pg_config* cfg, Head head) {
 
 // Lays out the tensors and allocates the workspaces of a fresh learner.  Head::kScalar and
 // Head::kMpo come with cfg->num_atoms = 1 (the support unused); Head::kMpo and
-// Head::kMpoCategorical with `mpo`.
+// Head::kMpoCategorical with `mpo`, Head::kCrr with `crr`.
 int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
-                 const acme_mpo_config* mpo) {
+                 const acme_mpo_config* mpo, const acme_crr_config* crr = nullptr) {
   l->cfg = *cfg;
   l->head = head;
+  const bool gauss = mpo || crr;
   add_net(l, l->pol, "policy", cfg->obs_dim, cfg->num_policy_layers, cfg->policy_sizes,
           cfg->act_dim,
-          mpo ? "multivariate_normal_diag_head/linear" : "near_zero_initialized_linear");
-  if (mpo) {
+          gauss ? "multivariate_normal_diag_head/linear" : "near_zero_initialized_linear");
+  if (gauss) {
     const int64_t hl = cfg->policy_sizes[cfg->num_policy_layers - 1];
     l->sw = add_tensor(l, "policy/multivariate_normal_diag_head/linear_1/w", {hl, cfg->act_dim});
     l->sb = add_tensor(l, "policy/multivariate_normal_diag_head/linear_1/b", {cfg->act_dim});
@@ -1695,8 +1855,21 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
     if (mpo->action_penalization) l->t_ptemp = add_tensor(l, "mpo/log_penalty_temperature", {1});
   }
   const int B = cfg->max_batch;
-  // MPO: the online critic sees the B TD rows only, the target critic the N B samples.
-  const int con_rows = mpo ? B : 2 * B, ctg_rows = mpo ? B * mpo->num_samples : B;
+  if (crr) {
+    // The Gaussian head's constants and the noise key live where MPO's kernels' setup reads them.
+    l->ccfg = *crr;
+    memset(&l->mcfg, 0, sizeof(l->mcfg));
+    l->mcfg.init_scale = crr->init_scale;
+    l->mcfg.min_scale = crr->min_scale;
+    l->mcfg.seed = crr->seed;
+    l->crr_rows = B;
+  }
+  const int ntd = crr ? crr->num_action_samples_td_learning : 0;
+  const int npw = crr ? crr->num_action_samples_policy_weight : 0;
+  // MPO: the online critic sees the B TD rows only, the target critic the N B samples.  CRR:
+  // the online critic the B rows and its N_pw B samples, the target critic its N_td B samples.
+  const int con_rows = crr ? B * (1 + npw) : mpo ? B : 2 * B;
+  const int ctg_rows = crr ? B * ntd : mpo ? B * mpo->num_samples : B;
   int rc;
   int hmax = 0;
   for (int i = 0; i < cfg->num_policy_layers; ++i) hmax = std::max(hmax, cfg->policy_sizes[i]);
@@ -1728,6 +1901,21 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
          (rc = dev_alloc(l, &l->mixture, (int64_t)B * cfg->num_atoms))))
       return rc;
   }
+  if (crr) {
+    const int64_t A = cfg->act_dim, NR = (int64_t)B * (ntd + npw);
+    auto& mb = l->mb;
+    auto& cb = l->cb;
+    if ((rc = dev_alloc(l, &mb.sd_on, B * A)) || (rc = dev_alloc(l, &mb.sd_t, B * A)) ||
+        (rc = dev_alloc(l, &mb.noise, NR * A)) || (rc = dev_alloc(l, &mb.act, NR * A)) ||
+        (rc = dev_alloc(l, &mb.tiled, NR * cfg->obs_dim)) ||
+        (rc = dev_alloc(l, &mb.dmean, B * A)) || (rc = dev_alloc(l, &mb.dpre, B * A)) ||
+        (rc = dev_alloc(l, &mb.sq, (int64_t)B * ntd)) ||
+        (rc = dev_alloc(l, &l->mixture, (int64_t)B * cfg->num_atoms)) ||
+        (rc = dev_alloc(l, &cb.q_mean, B)) || (rc = dev_alloc(l, &cb.v_est, B)) ||
+        (rc = dev_alloc(l, &cb.adv, B)) || (rc = dev_alloc(l, &cb.coef, B)) ||
+        (rc = dev_alloc(l, &cb.logp, B)) || (rc = dev_alloc(l, &cb.coef_part, ceil_div(B, 4))))
+      return rc;
+  }
   for (int i = 0; i < l->cri.nl; ++i)
     if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return rc;
   for (int i = 0; i < l->pol.nl; ++i)
@@ -1743,7 +1931,7 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
       (rc = dev_alloc(l, &l->lnslab2, nblk * 2 * hmax)) ||
       (rc = dev_alloc(l, &l->ploss_part, nblk)) ||
       (rc = dev_alloc(l, &l->norm_part, 2 * kNormBlocks)) ||
-      (rc = dev_alloc(l, &l->norms, 2)) || (rc = dev_alloc(l, &l->loss_tmp, 2)) ||
+      (rc = dev_alloc(l, &l->norms, 2)) || (rc = dev_alloc(l, &l->loss_tmp, 3)) ||
       (rc = dev_alloc(l, &l->ce, B)) || (rc = dev_alloc(l, &l->dev_step, 1)))
     return rc;
   if (!is_categorical(head) &&
@@ -1765,13 +1953,15 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
   return ACME_OK;
 }
 
-// A learner of handle type L (acme_d4pg, acme_ddpg, acme_mpo, acme_dmpo) with the given head kind.
+// A learner of handle type L (acme_d4pg, acme_ddpg, acme_mpo, acme_dmpo, acme_crr) with the
+// given head kind.
 template <class L>
-int create_learner(const acme_d4pg_config* cfg, Head head, const acme_mpo_config* mpo, L** out) {
+int create_learner(const acme_d4pg_config* cfg, Head head, const acme_mpo_config* mpo, L** out,
+                   const acme_crr_config* crr = nullptr) {
   int rc = check_config(cfg, head);
   if (rc != ACME_OK) return rc;
   L* l = new L();
-  if ((rc = init_learner(l, cfg, head, mpo)) != ACME_OK) return (ac_destroy(l), rc);
+  if ((rc = init_learner(l, cfg, head, mpo, crr)) != ACME_OK) return (ac_destroy(l), rc);
   *out = l;
   return ACME_OK;
 }
@@ -1839,6 +2029,7 @@ int d4pg_step(acme_actor_critic* l, const acme_d4pg_batch* batch, const acme_d4p
   ACME_CHECK_ARG(l && batch, "null argument");
   ACME_CHECK_ARG(l->head != Head::kMpo, "an MPO learner steps through acme_mpo_step");
   ACME_CHECK_ARG(l->head != Head::kMpoCategorical, "a DMPO learner steps through acme_dmpo_step");
+  ACME_CHECK_ARG(l->head != Head::kCrr, "a CRR learner steps through acme_crr_step");
   const bool copy = l->num_steps % l->cfg.target_update_period == 0;
   const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
                                  batch->o_t, out ? out->critic_loss : nullptr,
@@ -1893,8 +2084,29 @@ int ac_debug_buffer(const acme_actor_critic* l, const char* name, const float** 
     };
     return find_debug_buffer(items, name, out, count);
   }
-  const int64_t NB = B * l->mcfg.num_samples;
   const auto& mb = l->mb;
+  if (l->head == Head::kCrr) {
+    // The step packs the R rows of the last batch densely: the online samples follow R rows.
+    const int64_t R = l->crr_rows;
+    const int64_t Ntd = l->ccfg.num_action_samples_td_learning;
+    const int64_t Npw = l->ccfg.num_action_samples_policy_weight;
+    const auto& cb = l->cb;
+    const DebugItem items[] = {
+        {"mean_on", l->pon.out, R * A}, {"std_on", mb.sd_on, R * A}, {"pre_on", l->pon.t, R * A},
+        {"mean_t", l->ptg.out, R * A},  {"std_t", mb.sd_t, R * A},
+        {"noise", mb.noise, (Ntd + Npw) * R * A}, {"actions", mb.act, (Ntd + Npw) * R * A},
+        {"logits_tm1", l->con.out, R * K}, {"sampled_logits", l->ctg.out, Ntd * R * K},
+        {"policy_sampled_logits", l->con.out + R * K, Npw * R * K},
+        {"sampled_q", mb.sq, Ntd * R},  {"mixture", l->mixture, R * K},
+        {"ce", l->ce, R},               {"dlogits", l->dlogits, R * K},
+        {"q_tm1_mean", cb.q_mean, R},   {"v_estimate", cb.v_est, R},
+        {"advantage", cb.adv, R},       {"coef", cb.coef, R},        {"logp", cb.logp, R},
+        {"dmean", mb.dmean, R * A},     {"dpre", mb.dpre, R * A},
+        {"norms", l->norms, 2},         {"losses", l->loss_tmp, 3},
+    };
+    return find_debug_buffer(items, name, out, count);
+  }
+  const int64_t NB = B * l->mcfg.num_samples;
   if (l->head == Head::kMpoCategorical) {
     for (const char* scalar_only : {"q_tm1", "q_t", "td", "dq"})
       if (strcmp(name, scalar_only) == 0) {
@@ -1978,6 +2190,7 @@ int mpo_step(acme_actor_critic* l, Head head, const acme_mpo_batch* batch,
   if (l->head != head) {
     set_error(l->head == Head::kMpo               ? "an MPO learner steps through acme_mpo_step"
               : l->head == Head::kMpoCategorical ? "a DMPO learner steps through acme_dmpo_step"
+              : l->head == Head::kCrr            ? "a CRR learner steps through acme_crr_step"
               : head == Head::kMpo                ? "not an MPO learner"
                                                   : "not a DMPO learner");
     return ACME_ERR_INVALID;
@@ -2001,7 +2214,7 @@ int mpo_step(acme_actor_critic* l, Head head, const acme_mpo_batch* batch,
 int mpo_policy(acme_actor_critic* l, const float* obs, int64_t rows, int32_t use_target,
                float* mean_out, float* stddev_out, void* stream) {
   ACME_CHECK_ARG(l && obs && mean_out && stddev_out, "null argument");
-  ACME_CHECK_ARG(has_duals(l->head), "not an MPO or DMPO learner");
+  ACME_CHECK_ARG(has_gauss_head(l->head), "not a learner with a Gaussian policy head");
   ACME_CHECK_ARG(l->params, "acme_mpo_bind must be called first");
   ACME_CHECK_ARG(rows >= 0, "negative row count");
   hipStream_t st = as_stream(stream);
@@ -2023,6 +2236,84 @@ int mpo_policy(acme_actor_critic* l, const float* obs, int64_t rows, int32_t use
     ACME_LAUNCH_CHECK();
   }
   return ACME_OK;
+}
+
+// The bodies behind the acme_crr_* exports that only that kind has.
+
+// What acme_crr_create checks of the fields that CRR adds to the shared configuration.
+int check_crr_config(const acme_crr_config* cfg) {
+  const int ntd = cfg->num_action_samples_td_learning;
+  const int npw = cfg->num_action_samples_policy_weight;
+  ACME_CHECK_ARG(ntd >= 1 && ntd <= ACME_MPO_MAX_SAMPLES,
+                 "num_action_samples_td_learning must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
+  ACME_CHECK_ARG(npw >= 1 && npw <= ACME_MPO_MAX_SAMPLES,
+                 "num_action_samples_policy_weight must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
+  // The online critic runs max_batch * (1 + N_pw) rows, the target critic max_batch * N_td.
+  ACME_CHECK_ARG(cfg->max_batch >= 1 &&
+                     (int64_t)cfg->max_batch * (1 + std::max(ntd, npw)) <= ACME_MPO_MAX_ROWS,
+                 "max_batch * (1 + max(num_action_samples_td_learning, "
+                 "num_action_samples_policy_weight)) must be in [1, %d]", ACME_MPO_MAX_ROWS);
+  ACME_CHECK_ARG(cfg->baseline_reduce_function >= ACME_CRR_REDUCE_MEAN &&
+                     cfg->baseline_reduce_function <= ACME_CRR_REDUCE_MIN,
+                 "baseline_reduce_function must be mean (0), max (1) or min (2)");
+  ACME_CHECK_ARG(cfg->policy_improvement_modes >= ACME_CRR_MODE_EXP &&
+                     cfg->policy_improvement_modes <= ACME_CRR_MODE_ALL,
+                 "policy_improvement_modes must be exp (0), binary (1) or all (2)");
+  ACME_CHECK_ARG(cfg->beta > 0.f && cfg->ratio_upper_bound > 0.f,
+                 "beta and ratio_upper_bound must be positive");
+  ACME_CHECK_ARG(cfg->sequence_length >= 2, "sequence_length must be >= 2");
+  ACME_CHECK_ARG(cfg->init_scale > 0.f && cfg->min_scale >= 0.f,
+                 "init_scale must be positive and min_scale non-negative");
+  return ACME_OK;
+}
+
+// The learner configuration of a CRR config: the categorical critic, the action range unused.
+acme_d4pg_config crr_core_config(const acme_crr_config* cfg) {
+  acme_d4pg_config c;
+  memset(&c, 0, sizeof(c));
+  c.obs_dim = cfg->obs_dim; c.act_dim = cfg->act_dim; c.max_batch = cfg->max_batch;
+  c.num_policy_layers = cfg->num_policy_layers;
+  c.num_critic_layers = cfg->num_critic_layers;
+  memcpy(c.policy_sizes, cfg->policy_sizes, sizeof(c.policy_sizes));
+  memcpy(c.critic_sizes, cfg->critic_sizes, sizeof(c.critic_sizes));
+  c.num_atoms = cfg->num_atoms; c.vmin = cfg->vmin; c.vmax = cfg->vmax;
+  for (int j = 0; j < ACME_D4PG_MAX_ACT; ++j) {
+    c.action_min[j] = -1.f;
+    c.action_max[j] = 1.f;
+  }
+  c.discount = cfg->discount; c.target_update_period = cfg->target_update_period;
+  c.policy_learning_rate = cfg->policy_learning_rate;
+  c.critic_learning_rate = cfg->critic_learning_rate;
+  c.adam_beta1 = cfg->adam_beta1; c.adam_beta2 = cfg->adam_beta2;
+  c.adam_epsilon = cfg->adam_epsilon; c.clipping = cfg->clipping;
+  c.layer_norm_epsilon = cfg->layer_norm_epsilon;
+  return c;
+}
+
+int crr_step(acme_actor_critic* l, const acme_crr_batch* batch, const acme_crr_outputs* out,
+             void* stream) {
+  ACME_CHECK_ARG(l && batch, "null argument");
+  if (l->head != Head::kCrr) {
+    set_error(l->head == Head::kMpo               ? "an MPO learner steps through acme_mpo_step"
+              : l->head == Head::kMpoCategorical ? "a DMPO learner steps through acme_dmpo_step"
+                                                 : "not a CRR learner");
+    return ACME_ERR_INVALID;
+  }
+  const int T = l->ccfg.sequence_length;
+  ACME_CHECK_ARG(batch->batch % (T - 1) == 0,
+                 "batch %lld is not a multiple of sequence_length - 1 = %d",
+                 (long long)batch->batch, T - 1);
+  // The copy follows the update; the flag keys the graph as the other kinds' does.
+  const bool copy = l->num_steps % l->cfg.target_update_period == 0;
+  const void* key[kGraphKeys] = {batch->o_tm1, batch->a_tm1, batch->r_t, batch->d_t,
+                                 batch->o_t, batch->noise,
+                                 out ? out->critic_loss : nullptr,
+                                 out ? out->policy_loss : nullptr,
+                                 out ? out->policy_loss_coef : nullptr};
+  const int rc = run_step(l, "acme_crr", batch, key, copy ? 1 : 0, stream,
+                          [&](hipStream_t s) { return crr_step_impl(l, batch, out, copy, s); });
+  if (rc == ACME_OK) l->crr_rows = batch->batch;
+  return rc;
 }
 
 }  // namespace
@@ -2178,6 +2469,45 @@ int64_t acme_dmpo_num_steps(const acme_dmpo* l) { return ac_num_steps(l); }
 int acme_dmpo_set_num_steps(acme_dmpo* l, int64_t n) { return ac_set_num_steps(l, n); }
 int acme_dmpo_debug_buffer(const acme_dmpo* l, const char* name, const float** out,
                            int64_t* count) {
+  return ac_debug_buffer(l, name, out, count);
+}
+
+// ------------------------------------------------------------------ CRR
+// The shared learner with the Gaussian policy head, DMPO's categorical critic and the
+// advantage-weighted behaviour-cloning loss (RCRRLearner._step with stateless networks,
+// acme/agents/tf/crr/recurrent_learning.py:197-377).
+
+int acme_crr_create(const acme_crr_config* cfg, acme_crr** out) {
+  ACME_CHECK_ARG(cfg && out, "null argument");
+  const int rc = check_crr_config(cfg);
+  if (rc != ACME_OK) return rc;
+  const acme_d4pg_config c = crr_core_config(cfg);
+  return create_learner(&c, Head::kCrr, nullptr, out, cfg);
+}
+int acme_crr_destroy(acme_crr* l) { return ac_destroy(l); }
+int64_t acme_crr_flat_size(const acme_crr* l) { return ac_flat_size(l); }
+int64_t acme_crr_policy_size(const acme_crr* l) { return ac_policy_size(l); }
+int32_t acme_crr_num_tensors(const acme_crr* l) { return ac_num_tensors(l); }
+int acme_crr_tensor_info(const acme_crr* l, int32_t i, int64_t* offset, int64_t* numel,
+                         int32_t* ndim, int64_t* shape4, const char** name) {
+  return tensor_info<acme_actor_critic>(l, i, offset, numel, ndim, shape4, name);
+}
+int acme_crr_bind(acme_crr* l, float* params, float* target, float* grads, float* adam_m,
+                  float* adam_v) {
+  return ac_bind(l, params, target, grads, adam_m, adam_v);
+}
+int acme_crr_step(acme_crr* l, const acme_crr_batch* batch, const acme_crr_outputs* out,
+                  void* stream) {
+  return crr_step(l, batch, out, stream);
+}
+int acme_crr_policy(acme_crr* l, const float* obs, int64_t rows, int32_t use_target,
+                    float* mean_out, float* stddev_out, void* stream) {
+  return mpo_policy(l, obs, rows, use_target, mean_out, stddev_out, stream);
+}
+int64_t acme_crr_num_steps(const acme_crr* l) { return ac_num_steps(l); }
+int acme_crr_set_num_steps(acme_crr* l, int64_t n) { return ac_set_num_steps(l, n); }
+int acme_crr_debug_buffer(const acme_crr* l, const char* name, const float** out,
+                          int64_t* count) {
   return ac_debug_buffer(l, name, out, count);
 }
 

@@ -69,6 +69,8 @@ constexpr uint32_t kSampleTag = 0x534D504Cu;  // "SMPL"
 constexpr uint32_t kFillTag = 0x46494C4Cu;    // "FILL"
 // MPO's action-sampling noise (d4pg.hip): counter (element / 4, step lo, step hi, tag).
 constexpr uint32_t kMpoNoiseTag = 0x4D504F4Eu;  // "MPON"
+// CRR's two action sets (d4pg.hip): the same counter layout under a tag of its own.
+constexpr uint32_t kCrrNoiseTag = 0x4352524Eu;  // "CRRN"
 
 ACME_HD double sample_uniform(uint64_t seed, uint64_t step, uint32_t j) {
   u32x4 c = {j, (uint32_t)step, (uint32_t)(step >> 32), kSampleTag};

@@ -71,8 +71,8 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   z1 = rad * sn;
 }
 __device__ __forceinline__ void philox_normals(uint64_t seed, uint64_t step, uint32_t idx,
-                                               float (&z)[4]) {
-  const u32x4 c = {idx, (uint32_t)step, (uint32_t)(step >> 32), kMpoNoiseTag};
+                                               float (&z)[4], uint32_t tag = kMpoNoiseTag) {
+  const u32x4 c = {idx, (uint32_t)step, (uint32_t)(step >> 32), tag};
   const u32x4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   box_muller(r.x, r.y, z[0], z[1]);
   box_muller(r.z, r.w, z[2], z[3]);
@@ -380,6 +380,7 @@ struct DmpoMixArgs {
   const float *r, *d, *values;
   int B, N, K;
   float discount;
+  float row_div;          // what the row gradients divide by (DMPO: B; CRR: R T / (T - 1))
   float *sq, *mix;        // [N B], [B][K]
   float *dlogits, *ce;    // [B][K], [B]
 };
@@ -418,7 +419,7 @@ __global__ void __launch_bounds__(256) dmpo_mix_loss_kernel(const DmpoMixArgs a)
   const float pj = acc / wave_sum(acc);
   if (on) a.mix[(size_t)b * a.K + lane] = pj;
   const RowSoftmax q = row_softmax(ql, on);
-  categorical_loss_row(ql, q, pj, vi, b, lane, a.r, a.d, a.values, a.B, a.K, a.discount,
+  categorical_loss_row(ql, q, pj, vi, b, lane, a.r, a.d, a.values, a.row_div, a.K, a.discount,
                        a.dlogits, a.ce);
 }
 

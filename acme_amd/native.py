@@ -920,8 +920,9 @@ class _NativeActorCritic(_NativeLearner):
                              (act_dim,))
         hi = np.broadcast_to(np.asarray(1.0 if action_max is None else action_max, np.float32),
                              (act_dim,))
-        for j in range(act_dim):
-            cfg.action_min[j], cfg.action_max[j] = float(lo[j]), float(hi[j])
+        if hasattr(cfg, "action_min"):  # acme_crr_config has no action range
+            for j in range(act_dim):
+                cfg.action_min[j], cfg.action_max[j] = float(lo[j]), float(hi[j])
         for k, v in extra.items():  # the fields only this learner has
             setattr(cfg, k, v)
         cfg.discount = discount
@@ -1147,6 +1148,101 @@ class NativeDMPO(NativeMPO):
         """The support: tf.linspace(vmin, vmax, num_atoms), as the learner computes it."""
         step = (np.float64(self.vmax) - np.float64(self.vmin)) / (self.num_atoms - 1)
         return (np.float64(self.vmin) + np.arange(self.num_atoms) * step).astype(np.float32)
+
+
+class NativeCRR(_NativeActorCritic):
+    """acme_crr learner (offline actor-critic: NativeMPO's Gaussian policy, NativeDMPO's
+    categorical critic, the advantage-weighted behaviour-cloning loss, no duals) + its flat
+    buffers: policy tensors, then critic tensors.  A step takes R = B (T - 1) transitions
+    (`flatten_sequences`); `sequence_length` T is the reference's loss divisor.  The step's
+    outputs are the device scalars `critic_loss`, `policy_loss` and `policy_loss_coef`."""
+
+    _prefix, _tag, _config = "acme_crr", "crr", _lib.CRRConfig
+
+    def __init__(self, *, obs_dim: int, act_dim: int, max_batch: int, sequence_length: int,
+                 policy_sizes: Sequence[int] = (256, 256, 256),
+                 critic_sizes: Sequence[int] = (512, 512, 256), num_atoms: int = 51,
+                 vmin: float = -150.0, vmax: float = 150.0, discount: float = 0.99,
+                 target_update_period: int = 100, num_action_samples_td_learning: int = 1,
+                 num_action_samples_policy_weight: int = 4,
+                 baseline_reduce_function: str = "mean", policy_improvement_modes: str = "exp",
+                 ratio_upper_bound: float = 20.0, beta: float = 1.0,
+                 policy_learning_rate: float = 1e-4, critic_learning_rate: float = 1e-4,
+                 clipping: bool = True, init_scale: float = 0.3, min_scale: float = 1e-6,
+                 seed: int = 0, adam_beta1: float = 0.9, adam_beta2: float = 0.999,
+                 adam_epsilon: float = 1e-8, layer_norm_epsilon: float = 1e-5, device=None):
+        for name, n in (("num_action_samples_td_learning", num_action_samples_td_learning),
+                        ("num_action_samples_policy_weight", num_action_samples_policy_weight)):
+            if not 1 <= n <= _lib.MPO_MAX_SAMPLES:
+                raise ValueError(f"{name} must be in [1, {_lib.MPO_MAX_SAMPLES}]")
+        if baseline_reduce_function not in _lib.CRR_REDUCE:
+            raise ValueError(f"baseline_reduce_function must be one of {_lib.CRR_REDUCE}")
+        if policy_improvement_modes not in _lib.CRR_MODES:
+            raise ValueError(f"policy_improvement_modes must be one of {_lib.CRR_MODES}")
+        if sequence_length < 2:
+            raise ValueError("sequence_length must be >= 2")
+        self.num_samples_td = int(num_action_samples_td_learning)
+        self.num_samples_pw = int(num_action_samples_policy_weight)
+        self.sequence_length = int(sequence_length)
+        self.num_atoms, self.vmin, self.vmax = int(num_atoms), float(vmin), float(vmax)
+        self._setup(obs_dim=obs_dim, act_dim=act_dim, max_batch=max_batch,
+                    policy_sizes=policy_sizes, critic_sizes=critic_sizes, action_min=None,
+                    action_max=None, discount=discount,
+                    target_update_period=target_update_period,
+                    policy_learning_rate=policy_learning_rate,
+                    critic_learning_rate=critic_learning_rate, clipping=clipping,
+                    adam_beta1=adam_beta1, adam_beta2=adam_beta2, adam_epsilon=adam_epsilon,
+                    layer_norm_epsilon=layer_norm_epsilon, device=device,
+                    num_atoms=self.num_atoms, vmin=self.vmin, vmax=self.vmax,
+                    init_scale=init_scale, min_scale=min_scale,
+                    num_action_samples_td_learning=self.num_samples_td,
+                    num_action_samples_policy_weight=self.num_samples_pw,
+                    baseline_reduce_function=_lib.CRR_REDUCE.index(baseline_reduce_function),
+                    policy_improvement_modes=_lib.CRR_MODES.index(policy_improvement_modes),
+                    ratio_upper_bound=ratio_upper_bound, beta=beta,
+                    sequence_length=self.sequence_length,
+                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self.policy_loss_coef = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    values = NativeDMPO.values
+
+    @staticmethod
+    def flatten_sequences(observation, action, reward, discount):
+        """[B, T, ...] sequences as the R = B (T - 1) transitions of the reference's loop over
+        t (recurrent_learning.py:229-234), row b (T - 1) + (t - 1): (o_tm1, a_tm1, r_t, d_t,
+        o_t) = (o[:, :-1], a[:, :-1], r[:, :-1], d[:, :-1], o[:, 1:])."""
+        B, T = int(action.shape[0]), int(action.shape[1])
+        R = B * (T - 1)
+        o = observation.reshape(B, T, -1)
+        flat = lambda x: x.reshape(R, -1).to(torch.float32).contiguous()  # noqa: E731
+        return (flat(o[:, :-1]), flat(action.reshape(B, T, -1)[:, :-1]),
+                flat(reward.reshape(B, T)[:, :-1]).reshape(R),
+                flat(discount.reshape(B, T)[:, :-1]).reshape(R), flat(o[:, 1:]))
+
+    def step(self, o_tm1, a_tm1, r_t, d_t, o_t, noise=None, stream=None):
+        """One learner step over R transitions (a multiple of sequence_length - 1).  `noise`:
+        eps [N_td + N_pw, R, act_dim] for the two action sets (tests); None: generated on the
+        device from (seed, step)."""
+        R = self._check_batch(o_tm1, a_tm1, r_t, d_t, o_t)
+        b = _lib.MPOBatch()
+        b.o_tm1, b.a_tm1, b.r_t, b.d_t, b.o_t = (ptr(o_tm1), ptr(a_tm1), ptr(r_t), ptr(d_t),
+                                                 ptr(o_t))
+        b.batch = R
+        n = self.num_samples_td + self.num_samples_pw
+        if noise is not None:
+            if not (isinstance(noise, torch.Tensor) and noise.is_cuda and noise.is_contiguous()
+                    and noise.dtype == torch.float32 and noise.numel() == n * R * self.act_dim):
+                raise ValueError(f"noise must be a contiguous float32 device tensor of shape "
+                                 f"[{n}, {R}, {self.act_dim}]")
+            b.noise = ptr(noise)
+        out = _lib.CRROutputs()
+        out.critic_loss, out.policy_loss = ptr(self.critic_loss), ptr(self.policy_loss)
+        out.policy_loss_coef = ptr(self.policy_loss_coef)
+        check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(out), stream_ptr(stream)),
+              "crr step")
+
+    policy_distribution = NativeMPO.policy_distribution
+    policy = NativeMPO.policy
 
 
 class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):

@@ -914,6 +914,104 @@ int acme_dmpo_set_num_steps(acme_dmpo* l, int64_t n);
 int acme_dmpo_debug_buffer(const acme_dmpo* l, const char* name, const float** out,
                            int64_t* count);
 
+/* ------------------------------------------------------------------- CRR -- */
+/* Replaces RCRRLearner._step (acme/agents/tf/crr/recurrent_learning.py:197-377) for stateless
+ * networks, where the loop over t carries nothing and the [B, T] sequences unroll into
+ * R = B (T - 1) independent transitions: policy = MPO's (LayerNormMLP ->
+ * MultivariateNormalDiagHead), critic = D4PG's (DiscreteValuedHead), identity observation
+ * network, no dual variables.  An offline learner: it has no actor of its own.
+ *
+ * Flat buffers: DMPO's layout without the dual group: policy tensors, then critic tensors
+ * ending in "critic/discrete_valued_head/linear/{w,b}".
+ *
+ * The step: the online policy on o_tm1 and the target policy on o_t; N_td actions per state
+ * from the target policy at o_t through the target critic, whose mixture (as DMPO's) is the
+ * bootstrap distribution of the categorical critic loss; N_pw actions per state from the online
+ * policy at o_tm1 through the online critic, whose means reduce (mean / max / min) to the value
+ * estimate V; advantage = mean(q_tm1) - V; coefficient f(advantage) (exp: min(exp(adv / beta),
+ * ratio_upper_bound); binary: adv > 0; all: 1), behind a stop-gradient; policy loss
+ * -log pi(a_tm1 | o_tm1) * coefficient.  The reference sums its per-t batch means and divides
+ * by the sequence length T, not by the T - 1 transitions, so every batch mean here is
+ * sum_rows * (T - 1) / (R T).  Global-norm clip 40 per network, two Adams; AFTER the update
+ * target <- online when num_steps % target_update_period == 0, then num_steps += 1 (so step 0
+ * ends with target == online).
+ *
+ * Sampling noise: eps [N_td + N_pw, R, act_dim], element e = (n R + b) act_dim + d; rows
+ * n < N_td sample the target policy at o_t, the others the online policy at o_tm1.  Generated
+ * as MPO's (above) with the counter's tag 0x4352524E. */
+#define ACME_CRR_REDUCE_MEAN 0
+#define ACME_CRR_REDUCE_MAX 1
+#define ACME_CRR_REDUCE_MIN 2
+#define ACME_CRR_MODE_EXP 0
+#define ACME_CRR_MODE_BINARY 1
+#define ACME_CRR_MODE_ALL 2
+
+typedef struct acme_crr acme_crr;
+
+typedef struct acme_crr_config {
+  int32_t obs_dim;              /* flat observation size (<= 64 - act_dim) */
+  int32_t act_dim;              /* <= ACME_D4PG_MAX_ACT */
+  int32_t max_batch;            /* rows R; max_batch (1 + max(N_td, N_pw)) <= ACME_MPO_MAX_ROWS */
+  int32_t num_policy_layers;    /* LayerNormMLP sizes, 1..ACME_D4PG_MAX_LAYERS */
+  int32_t policy_sizes[ACME_D4PG_MAX_LAYERS];
+  int32_t num_critic_layers;
+  int32_t critic_sizes[ACME_D4PG_MAX_LAYERS];
+  int32_t num_atoms;            /* in [2, ACME_D4PG_MAX_ATOMS] */
+  float vmin, vmax;             /* vmax > vmin */
+  float discount;
+  float policy_learning_rate, critic_learning_rate;
+  float adam_beta1, adam_beta2, adam_epsilon;
+  int32_t clipping;             /* global-norm clip 40 of the policy and of the critic gradients */
+  float layer_norm_epsilon;
+  float init_scale, min_scale;  /* MultivariateNormalDiagHead */
+  int32_t num_action_samples_td_learning;    /* N_td in [1, ACME_MPO_MAX_SAMPLES] */
+  int32_t num_action_samples_policy_weight;  /* N_pw in [1, ACME_MPO_MAX_SAMPLES] */
+  int32_t baseline_reduce_function;          /* ACME_CRR_REDUCE_* */
+  int32_t policy_improvement_modes;          /* ACME_CRR_MODE_* */
+  float ratio_upper_bound, beta;             /* of ACME_CRR_MODE_EXP; beta > 0 */
+  int32_t target_update_period;
+  int32_t sequence_length;      /* T >= 2: the loss divisor; batch must be a multiple of T - 1 */
+  uint64_t seed;                /* key of the generated sampling noise */
+} acme_crr_config;
+
+/* R transitions; noise [N_td + N_pw, R, act_dim] or null. */
+typedef acme_mpo_batch acme_crr_batch;
+
+typedef struct acme_crr_outputs {
+  float* critic_loss;       /* [1] device (optional) */
+  float* policy_loss;       /* [1] (optional) */
+  float* policy_loss_coef;  /* [1] the mean coefficient, as the reference logs it (optional) */
+} acme_crr_outputs;
+
+int acme_crr_create(const acme_crr_config* cfg, acme_crr** out);
+int acme_crr_destroy(acme_crr* l);
+int64_t acme_crr_flat_size(const acme_crr* l);
+/* Floats [0, policy_size) are the policy's, the rest the critic's. */
+int64_t acme_crr_policy_size(const acme_crr* l);
+int32_t acme_crr_num_tensors(const acme_crr* l);
+int acme_crr_tensor_info(const acme_crr* l, int32_t i, int64_t* offset, int64_t* numel,
+                         int32_t* ndim, int64_t* shape4, const char** name);
+int acme_crr_bind(acme_crr* l, float* params, float* target, float* grads, float* adam_m,
+                  float* adam_v);
+/* One learner step (above).  batch->batch not a multiple of sequence_length - 1, or a handle of
+ * another kind: ACME_ERR_INVALID, nothing stepped. */
+int acme_crr_step(acme_crr* l, const acme_crr_batch* batch, const acme_crr_outputs* out,
+                  void* stream);
+/* Policy forward: the distribution's parameters, [rows, act_dim] each. */
+int acme_crr_policy(acme_crr* l, const float* obs, int64_t rows, int32_t use_target,
+                    float* mean_out, float* stddev_out, void* stream);
+int64_t acme_crr_num_steps(const acme_crr* l);
+int acme_crr_set_num_steps(acme_crr* l, int64_t n);
+/* Internal device workspaces (tests); the step packs the R rows of the last batch densely
+ * (max_batch before the first step): "mean_on" "std_on" "pre_on" (online policy at o_tm1)
+ * "mean_t" "std_t" (target policy at o_t) (R x act_dim), "noise" "actions" ((N_td + N_pw) R x
+ * act_dim), "logits_tm1" (R x num_atoms), "sampled_logits" (target critic, N_td R x num_atoms),
+ * "policy_sampled_logits" (online critic, N_pw R x num_atoms), "sampled_q" (N_td R), "mixture"
+ * "dlogits" (R x num_atoms), "ce" "q_tm1_mean" "v_estimate" "advantage" "coef" "logp" (R),
+ * "dmean" "dpre" (R x act_dim), "norms" (2), "losses" (critic, policy, coefficient). */
+int acme_crr_debug_buffer(const acme_crr* l, const char* name, const float** out,
+                          int64_t* count);
+
 /* ---------------------------------------------------------------- IMPALA -- */
 /* Replaces IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with
  * IMPALAAtariNetwork (acme/tf/networks/atari.py:115-144): OAREmbedding(AtariTorso) ->
