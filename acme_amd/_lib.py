@@ -168,6 +168,30 @@ IMPALA_TORSO_ATARI = 0
 IMPALA_TORSO_FLAT = 1
 
 
+AZ_MAX_WIDTH = 1024
+AZ_MAX_ACTIONS = 64
+AZ_MAX_ROWS = 4096
+AZ_FUSED_MAX_ROWS = 32
+AZ_FUSED_MAX_WIDTH = 256
+
+
+class AZConfig(ctypes.Structure):  # acme_az_config
+    _fields_ = [("obs_dim", c_i32), ("num_actions", c_i32), ("max_batch", c_i32),
+                ("max_eval_rows", c_i32), ("num_hidden", c_i32),
+                ("hidden", c_i32 * MAX_MLP_LAYERS), ("activate_final", c_i32),
+                ("discount", c_f32), ("learning_rate", c_f32), ("adam_beta1", c_f32),
+                ("adam_beta2", c_f32), ("adam_epsilon", c_f32)]
+
+
+class AZBatch(ctypes.Structure):
+    _fields_ = [("o_t", c_vp), ("r_t", c_vp), ("d_t", c_vp), ("o_tp1", c_vp), ("pi", c_vp),
+                ("batch", c_i64)]
+
+
+class AZOutputs(ctypes.Structure):
+    _fields_ = [("loss", c_vp), ("value_loss", c_vp), ("policy_loss", c_vp)]
+
+
 class IMPALAConfig(ctypes.Structure):
     _fields_ = [("torso", c_i32), ("obs_dim", c_i32), ("num_actions", c_i32),
                 ("max_batch", c_i32), ("max_sequence_length", c_i32), ("lstm_size", c_i32),
@@ -317,6 +341,8 @@ _SIGS = {
     "acme_mpo_init_duals": (c_i32, [c_vp]),
     "acme_dmpo_dual_offset": (c_i64, [c_vp]),
     "acme_dmpo_init_duals": (c_i32, [c_vp]),
+    "acme_az_step": (c_i32, [c_vp, ctypes.POINTER(AZBatch), ctypes.POINTER(AZOutputs), c_vp]),
+    "acme_az_evaluate": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),
@@ -378,7 +404,8 @@ for _learner in (
         dict(prefix="ddpg", config=DDPGConfig, bind=5, actor_critic=(D4PGBatch, D4PGOutputs, 1)),
         dict(prefix="mpo", config=MPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
         dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
-        dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2))):
+        dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2)),
+        dict(prefix="az", config=AZConfig, bind=4)):  # no target
     _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1245,6 +1245,80 @@ class NativeCRR(_NativeActorCritic):
     policy = NativeMPO.policy
 
 
+class NativeAZ(_NativeLearner):
+    """acme_az learner (policy-value MLP, soft-label cross-entropy + TD value loss, Adam) + its
+    flat buffers, and the network evaluation the MCTS actor calls once per tree node.  The
+    step's losses are the device scalars `loss`, `value_loss`, `policy_loss`."""
+
+    _prefix, _tag = "acme_az", "az"
+    _has_target = False
+
+    def __init__(self, *, obs_dim: int, hidden: Sequence[int], num_actions: int, max_batch: int,
+                 max_eval_rows: int = 1, activate_final: bool = False, discount: float = 1.0,
+                 learning_rate: float = 1e-3, adam_beta1: float = 0.9,
+                 adam_beta2: float = 0.999, adam_epsilon: float = 1e-8, device=None):
+        cfg = _lib.AZConfig()
+        if not 1 <= len(hidden) <= _lib.MAX_MLP_LAYERS:
+            raise ValueError(f"hidden needs 1..{_lib.MAX_MLP_LAYERS} layer sizes")
+        cfg.obs_dim, cfg.num_actions = int(obs_dim), int(num_actions)
+        cfg.max_batch, cfg.max_eval_rows = int(max_batch), int(max_eval_rows)
+        cfg.num_hidden = len(hidden)
+        for i, s in enumerate(hidden):
+            cfg.hidden[i] = int(s)
+        cfg.activate_final = 1 if activate_final else 0
+        cfg.discount, cfg.learning_rate = float(discount), float(learning_rate)
+        cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
+        self.obs_dim, self.num_actions = int(obs_dim), int(num_actions)
+        self.max_batch, self.max_eval_rows = int(max_batch), int(max_eval_rows)
+        self.learning_rate = float(learning_rate)
+        _lib.require_gpu()
+        self._create(cfg, device)
+        d = self.device
+        self._losses = torch.zeros(3, dtype=torch.float32, device=d)
+        self.loss, self.value_loss, self.policy_loss = (self._losses[i:i + 1] for i in range(3))
+        self._out = _lib.AZOutputs()
+        self._out.loss, self._out.value_loss, self._out.policy_loss = (
+            ptr(self.loss), ptr(self.value_loss), ptr(self.policy_loss))
+
+    def _check_batch(self, o_t, r_t, d_t, o_tp1, pi) -> int:
+        B = int(r_t.shape[0])
+        for name, t, cols in (("o_t", o_t, self.obs_dim), ("r_t", r_t, 1), ("d_t", d_t, 1),
+                              ("o_tp1", o_tp1, self.obs_dim), ("pi", pi, self.num_actions)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
+                    and t.dtype == torch.float32):
+                raise ValueError(f"{name} must be a contiguous float32 device tensor")
+            if t.shape[0] != B or t.numel() != B * cols:
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [{B}, {cols}]")
+        return B
+
+    def step(self, o_t, r_t, d_t, o_tp1, pi, stream=None):
+        b = _lib.AZBatch()
+        b.batch = self._check_batch(o_t, r_t, d_t, o_tp1, pi)
+        b.o_t, b.r_t, b.d_t, b.o_tp1, b.pi = ptr(o_t), ptr(r_t), ptr(d_t), ptr(o_tp1), ptr(pi)
+        check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(self._out),
+                               stream_ptr(stream)), "az step")
+
+    def evaluate_packed(self, obs: torch.Tensor, stream=None) -> torch.Tensor:
+        """probs [rows, A] then value [rows] of device observations [rows, obs_dim], packed in
+        one device buffer of rows (A + 1) floats (one copy brings both to the host)."""
+        rows, A = int(obs.shape[0]), self.num_actions
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
+                and obs.numel() == rows * self.obs_dim):
+            raise ValueError(f"observations must be contiguous float32 [rows, {self.obs_dim}] "
+                             "on the device")
+        out = torch.empty(rows * (A + 1), dtype=torch.float32, device=self.device)
+        check(self._fn("evaluate")(self._h, ptr(obs), rows, ptr(out),
+                                   out.data_ptr() + 4 * rows * A, stream_ptr(stream)),
+              "az evaluate")
+        return out
+
+    def evaluate(self, obs: torch.Tensor, stream=None):
+        """(probs [rows, A], value [rows]) as device tensors (views of one buffer)."""
+        rows, A = int(obs.shape[0]), self.num_actions
+        out = self.evaluate_packed(obs, stream)
+        return out[:rows * A].view(rows, A), out[rows * A:]
+
+
 class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):
     """acme_impala learner + its flat buffers (no target network)."""
 

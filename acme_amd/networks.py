@@ -136,6 +136,64 @@ class MLP:
         return dict(variables)
 
 
+@dataclasses.dataclass(frozen=True)
+class PolicyValueMLP:
+    """snt.Sequential([snt.Flatten(), snt.nets.MLP(hidden, activate_final),
+    PolicyValueHead(num_actions)]) (acme/agents/tf/mcts/agent_test.py:45-49,
+    acme/tf/networks/policy_value.py): ReLU between the trunk layers, after the last one only
+    with activate_final; then two linear heads on the trunk output, logits [A] and a value."""
+
+    obs_dim: int
+    hidden: Tuple[int, ...]
+    num_actions: int
+    activate_final: bool = False
+    obs_dtype: str = "float32"
+    kind: str = dataclasses.field(default="policy_value_mlp", init=False)
+
+    def __init__(self, obs_dim: int, hidden: Sequence[int], num_actions: int,
+                 activate_final: bool = False):
+        object.__setattr__(self, "obs_dim", int(obs_dim))
+        object.__setattr__(self, "hidden", tuple(int(h) for h in hidden))
+        object.__setattr__(self, "num_actions", int(num_actions))
+        object.__setattr__(self, "activate_final", bool(activate_final))
+        object.__setattr__(self, "obs_dtype", "float32")
+        object.__setattr__(self, "kind", "policy_value_mlp")
+        if not self.hidden:
+            raise ValueError("PolicyValueMLP needs at least one trunk layer")
+
+    def tensor_shapes(self):
+        out, d = [], self.obs_dim
+        for i, h in enumerate(self.hidden):
+            out.append((f"mlp/linear_{i}/w", (d, h)))
+            out.append((f"mlp/linear_{i}/b", (h,)))
+            d = h
+        out += [("policy_value_network/linear/w", (d, self.num_actions)),
+                ("policy_value_network/linear/b", (self.num_actions,)),
+                ("policy_value_network/linear_1/w", (d, 1)),
+                ("policy_value_network/linear_1/b", (1,))]
+        return out
+
+    @property
+    def obs_shape(self) -> Tuple[int, ...]:
+        return (self.obs_dim,)
+
+    def init(self, seed: int = 0) -> Dict[str, np.ndarray]:
+        rng = np.random.default_rng(seed)
+        out = {}
+        for name, shape in self.tensor_shapes():
+            if name.endswith("/b"):
+                out[name] = np.zeros(shape, np.float32)
+            else:
+                out[name] = truncated_normal(rng, shape, 1.0 / np.sqrt(shape[0]))
+        return out
+
+    def to_sonnet(self, params):
+        return dict(params)
+
+    def from_sonnet(self, variables):
+        return dict(variables)
+
+
 # ------------------------------------------------------------------ D4PG (control suite)
 
 

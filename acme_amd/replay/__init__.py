@@ -152,8 +152,10 @@ class Table:
         from acme_amd.native import NativeReplay
         self._structure = structure
         self._fields = fields
+        # (A nested element with one leaf, e.g. extras {'pi': ...}, keeps the count but is no leaf.)
         self._flat_tuple = (isinstance(structure, tuple) and not hasattr(structure, "_fields")
-                            and len(structure) == len(fields))
+                            and len(structure) == len(fields)
+                            and not any(isinstance(x, (tuple, list, dict)) for x in structure))
         self._pend = [np.zeros((self._flush_every, f.row_bytes), np.uint8) for f in fields]
         self._fill = 0
         self._native = NativeReplay(self.max_size, [f.row_bytes for f in fields],

@@ -1232,6 +1232,88 @@ int acme_r2d2_debug_buffer(const acme_r2d2* l, const char* name, const float** o
 int acme_epsilon_greedy(const float* q, int64_t rows, int32_t num_actions, double epsilon,
                         uint64_t seed, uint64_t step_counter, int32_t* actions, void* stream);
 
+/* -------------------------------------------------------------- MCTS / AZ -- */
+/* Replaces AZLearner._step (acme/agents/tf/mcts/learning.py:53-82) and the network call of
+ * MCTSActor._forward (acting.py:67-77).  Network: snt.Sequential([snt.Flatten(),
+ * snt.nets.MLP(hidden, activate_final), PolicyValueHead(num_actions)]): ReLU between the
+ * trunk layers (after the last one only with activate_final), then two linear heads on the
+ * trunk output, logits [A] and a scalar value.  Flat buffer: mlp/linear_i/{w,b}, then
+ * policy_value_network/linear/{w,b} ([H, A], [A]) and policy_value_network/linear_1/{w,b}
+ * ([H, 1], [1]).  No target network, no gradient clipping, no replay write-back.
+ *
+ * Limits (acme_az_create refuses anything else, naming the field):
+ *   num_hidden in [1, ACME_MAX_MLP_LAYERS];
+ *   obs_dim and every hidden[i] in [1, ACME_AZ_MAX_WIDTH] (any value: widths that are not a
+ *     multiple of 4 take the dense engine's scalar loaders);
+ *   num_actions in [1, ACME_AZ_MAX_ACTIONS] (the head kernels hold one action per lane);
+ *   max_batch in [1, ACME_AZ_MAX_ROWS], max_eval_rows in [1, ACME_AZ_MAX_ROWS]. */
+#define ACME_AZ_MAX_WIDTH 1024
+#define ACME_AZ_MAX_ACTIONS 64
+#define ACME_AZ_MAX_ROWS 4096
+/* acme_az_evaluate runs the whole network in one launch (activations in LDS) when
+ * rows <= ACME_AZ_FUSED_MAX_ROWS and obs_dim and every hidden[i] <= ACME_AZ_FUSED_MAX_WIDTH;
+ * otherwise one dense launch per trunk layer and a head / softmax launch. */
+#define ACME_AZ_FUSED_MAX_ROWS 32
+#define ACME_AZ_FUSED_MAX_WIDTH 256
+
+typedef struct acme_az acme_az;
+
+typedef struct acme_az_config {
+  int32_t obs_dim;              /* flat observation size */
+  int32_t num_actions;
+  int32_t max_batch;            /* largest B of acme_az_step */
+  int32_t max_eval_rows;        /* largest rows of acme_az_evaluate */
+  int32_t num_hidden;           /* trunk layers */
+  int32_t hidden[ACME_MAX_MLP_LAYERS];
+  int32_t activate_final;       /* ReLU after the last trunk layer (snt.nets.MLP's flag) */
+  float discount;
+  float learning_rate;          /* snt.optimizers.Adam */
+  float adam_beta1, adam_beta2, adam_epsilon;
+} acme_az_config;
+
+/* Device f32 tensors; the transition's action is not read. */
+typedef struct acme_az_batch {
+  const float* o_t;    /* [B, obs_dim] */
+  const float* r_t;    /* [B] */
+  const float* d_t;    /* [B] */
+  const float* o_tp1;  /* [B, obs_dim] */
+  const float* pi;     /* [B, num_actions] search policy (any non-negative labels) */
+  int64_t batch;       /* 1 <= B <= max_batch */
+} acme_az_batch;
+
+/* Device scalars (each optional): loss = value_loss + policy_loss, value_loss =
+ * mean_b (r + discount d v' - v)^2, policy_loss = mean_b -sum_a pi log_softmax(logits). */
+typedef struct acme_az_outputs {
+  float* loss;
+  float* value_loss;
+  float* policy_loss;
+} acme_az_outputs;
+
+int acme_az_create(const acme_az_config* cfg, acme_az** out);
+int acme_az_destroy(acme_az* l);
+int64_t acme_az_flat_size(const acme_az* l);
+int32_t acme_az_num_tensors(const acme_az* l);
+int acme_az_tensor_info(const acme_az* l, int32_t i, int64_t* offset, int64_t* numel,
+                        int32_t* ndim, int64_t* shape4, const char** name);
+/* Flat device buffers of acme_az_flat_size floats each (gradients and moments zeroed). */
+int acme_az_bind(acme_az* l, float* params, float* grads, float* adam_m, float* adam_v);
+/* One learner step on `stream`, no host synchronisation: the trunk over the 2B rows
+ * [o_t; o_tp1], the head / loss kernel, the backward over the B o_t rows, Adam with
+ * t = num_steps + 1.  2 num_hidden + 2 launches. */
+int acme_az_step(acme_az* l, const acme_az_batch* batch, const acme_az_outputs* out,
+                 void* stream);
+/* probs [rows, A] = softmax(logits), value [rows] of obs [rows, obs_dim] (device f32) under
+ * the current parameters; 1 <= rows <= max_eval_rows.  Changes no learner state. */
+int acme_az_evaluate(acme_az* l, const float* obs, int64_t rows, float* probs, float* value,
+                     void* stream);
+int64_t acme_az_num_steps(const acme_az* l);
+int acme_az_set_num_steps(acme_az* l, int64_t n);
+/* Internal device workspaces (tests) of the last step over B rows: "h" (trunk output,
+ * [2B, H]), "logits" [B, A], "v" [2B] (values of the o_t rows, then of the o_tp1 rows),
+ * "td" [B], "dlogits" [B, A], "dv" [B], "dh" (gradient at the last trunk layer's
+ * pre-activation, [B, H]). */
+int acme_az_debug_buffer(const acme_az* l, const char* name, const float** out, int64_t* count);
+
 /* ------------------------------------------------------------- profiling -- */
 /* Section profiler: when enabled, every kernel section records a HIP event pair on the
  * stream it is launched on, tagged with its algorithmic FLOPs / HBM bytes. */
