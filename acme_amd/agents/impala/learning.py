@@ -183,7 +183,7 @@ class IMPALALearner(_learner.PlaneLearner):
 
 class _PipelinedPolicy:
     """IMPALALearner.pipelined_policy: two networks bound to the learner's parameter
-    snapshots (as actor_policy), one high-priority stream, and packed transfer blocks: the
+    snapshots (as actor_policy), one stream of its own, and packed transfer blocks: the
     small inputs (previous actions and rewards, LSTM state) go to the device in one copy and
     the outputs (logits, values, LSTM state) come back in one, next to the observation copy
     (straight from page-locked memory when the caller has it there)."""
@@ -192,10 +192,9 @@ class _PipelinedPolicy:
         n = learner.native
         self._l = learner
         self._nets = _actor_networks(learner, rows)
-        try:  # the actors' policy ahead of the learner's kernels where both are queued
-            self._stream = torch.cuda.Stream(device=n.device, priority=-1)
-        except (RuntimeError, TypeError):
-            self._stream = torch.cuda.Stream(device=n.device)
+        # Default priority: a raised one is not safe on every machine this runs on
+        # (virtualised cards), and what the policy computes does not depend on it.
+        self._stream = torch.cuda.Stream(device=n.device)
         A, H, dev = n.num_actions, n.lstm_size, n.device
         net = learner._network  # noqa: SLF001
         F = 84 * 84 * 4 if net.torso == "atari" else net.obs_dim

@@ -303,14 +303,25 @@ class ProcessActorPool:
 
     def register_pinned(self) -> None:
         """Page-locks the observation block (the policy's host-to-device copies then read it
-        directly); call after the parent has initialised the GPU."""
+        directly); call after the parent has initialised the GPU.  The block is shared memory
+        the workers have mapped already, so it cannot be allocated pinned instead: where the
+        runtime cannot page-lock memory the process already has (a virtualised card), the
+        block stays as it is, obs_pinned stays False and the policy stages the observations
+        through its own pinned block, with the same results."""
         import ctypes
-        from acme_amd._lib import check, lib
+        import warnings
+        from acme_amd._lib import ACME_ERR_HIP, check, lib
         if getattr(self, "_pinned", None):
             return
         obs = self.S["obs"]
         p = obs.ctypes.data
-        check(lib().acme_host_register(ctypes.c_void_p(p), obs.nbytes), "host register")
+        rc = lib().acme_host_register(ctypes.c_void_p(p), obs.nbytes)
+        if rc == ACME_ERR_HIP:
+            warnings.warn("the observation block could not be page-locked ("
+                          + lib().acme_last_error().decode(errors="replace")
+                          + "): the policy stages observations through pinned memory")
+            return
+        check(rc, "host register")
         self._pinned = p
 
     def _unregister(self) -> None:

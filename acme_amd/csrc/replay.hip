@@ -1324,7 +1324,15 @@ int acme_replay_commit(acme_replay* r, int64_t n, const double* priorities, uint
 
 int acme_host_register(void* p, int64_t bytes) {
   ACME_CHECK_ARG(p && bytes > 0, "bad host range");
-  ACME_HIP_TRY(hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault));
+  const hipError_t e = hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault);
+  if (e != hipSuccess) {
+    // Not every machine can page-lock memory the process already has (a virtualised card
+    // refuses with hipErrorInvalidValue).  The runtime keeps the refusal as its last error:
+    // take it back, or the next launch check would report it as its own.
+    (void)hipGetLastError();
+    set_error("hipHostRegister of %lld bytes failed: %s", (long long)bytes, hipGetErrorString(e));
+    return ACME_ERR_HIP;
+  }
   return ACME_OK;
 }
 

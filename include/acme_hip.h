@@ -138,7 +138,9 @@ int acme_replay_commit(acme_replay* r, int64_t n, const double* priorities, uint
 int acme_replay_sync_inserts(acme_replay* r);
 /* Page-locks caller memory (hipHostRegister) so copies from it are DMA without staging,
  * e.g. the shared-memory blocks actor processes write observations into; unregister
- * before the memory is unmapped. */
+ * before the memory is unmapped.  Where the runtime cannot page-lock memory the process
+ * already has (a virtualised card), _register returns ACME_ERR_HIP and leaves no pending
+ * runtime error behind: the caller then copies through memory that was allocated pinned. */
 int acme_host_register(void* p, int64_t bytes);
 int acme_host_unregister(void* p);
 

@@ -191,8 +191,6 @@ def test_pipelined_policy_equals_actor_policy(rows):
     page-locked observation source, issue / result) returns exactly actor_policy's
     logits, values and LSTM state for the same inputs, at 64 rows on the one-launch LSTM
     step too; and two calls in flight on their own policies do not disturb each other."""
-    import ctypes
-    from acme_amd import _lib
     from acme_amd.agents.impala import IMPALALearner
     from acme_amd.networks import IMPALAAtariNetwork
     A, H = 18, 256
@@ -206,17 +204,41 @@ def test_pipelined_policy_equals_actor_policy(rows):
             (0.3 * rng.standard_normal((rows, H))).astype(np.float32)) for _ in range(2)]
     ref = [learner.actor_policy(max_rows=rows)(*x) for x in ins]
     pols = [learner.pipelined_policy(rows) for _ in range(2)]
-    # The first call's observations from page-locked memory, the second's staged.
-    obs0 = np.empty_like(ins[0][0])
+    # The first call's observations from page-locked memory, the second's staged.  The memory
+    # is allocated page-locked: not every machine can page-lock memory it already has.
+    pinned = torch.empty(ins[0][0].shape, dtype=torch.uint8, pin_memory=True)
+    assert pinned.is_pinned()
+    obs0 = pinned.numpy()
     obs0[...] = ins[0][0]
-    L = _lib.lib()
-    _lib.check(L.acme_host_register(ctypes.c_void_p(obs0.ctypes.data), obs0.nbytes))
-    try:
-        pols[0].issue(obs0, *ins[0][1:], observation_pinned=True)
-        pols[1].issue(*ins[1])
-        got = [pols[0].result(), pols[1].result()]
-    finally:
-        L.acme_host_unregister(ctypes.c_void_p(obs0.ctypes.data))
+    pols[0].issue(obs0, *ins[0][1:], observation_pinned=True)
+    pols[1].issue(*ins[1])
+    got = [pols[0].result(), pols[1].result()]
     for g, r in zip(got, ref):
         for a, b in zip(g, r):
             np.testing.assert_array_equal(a, b)
+
+
+def test_host_register_page_locks_or_refuses_cleanly():
+    """acme_host_register either page-locks the caller's memory (a copy from it arrives intact,
+    and it unregisters) or, where the runtime cannot page-lock memory the process already has,
+    returns ACME_ERR_HIP with the runtime's reason; in both cases it leaves no pending runtime
+    error, so the next native launch (a replay table's fill, insert and draw) succeeds."""
+    import ctypes
+    from acme_amd import _lib
+    from acme_amd.native import NativeReplay
+    L = _lib.lib()
+    src = np.arange(1 << 16, dtype=np.uint8)
+    p = ctypes.c_void_p(src.ctypes.data)
+    rc = L.acme_host_register(p, src.nbytes)
+    if rc == _lib.ACME_OK:
+        dev = torch.empty(src.size, dtype=torch.uint8, device="cuda")
+        dev.copy_(torch.from_numpy(src), non_blocking=True)
+        torch.cuda.synchronize()
+        assert L.acme_host_unregister(p) == _lib.ACME_OK
+        np.testing.assert_array_equal(dev.cpu().numpy(), src)
+    else:
+        assert rc == _lib.ACME_ERR_HIP
+        assert b"hipHostRegister" in L.acme_last_error()
+    r = NativeReplay(64, [4], prioritized=False, priority_exponent=0.6, seed=1)
+    r.insert([np.arange(64, dtype=np.int32)], np.ones(64))
+    assert r.sample(8, 0)["slots"].cpu().numpy().shape == (8,)

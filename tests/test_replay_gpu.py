@@ -341,6 +341,9 @@ def test_pipelined_sample_gather(prioritized, fields):
     assert L.acme_replay_pipe_open(r.handle, ctypes.byref(pid)) == 0
     st = torch.cuda.Stream()
     sets = [_pipe_buffers(r, bmax, fields) for _ in range(3)]
+    # The buffers were zero-filled on the current stream, and st is not ordered after it by
+    # itself: without this, a late fill can overwrite rows the pipe has already copied.
+    st.wait_stream(torch.cuda.current_stream())
     plan = [(0, 257, 11), (1, 257, 12), (2, 300, 13), (0, 64, 14), (1, 257, 15)]
     if wide:
         plan = [(0, 9, 11), (1, 9, 12), (2, 12, 13), (0, 4, 14), (1, 9, 15)]
