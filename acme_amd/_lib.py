@@ -224,6 +224,25 @@ class SequenceBatch(ctypes.Structure):
                 ("state_stride", c_i64), ("batch", c_i64), ("sequence_length", c_i64)]
 
 
+MLP_MODEL_MAX_WIDTH = 256
+MLP_MODEL_MAX_ACTIONS = 64
+MLP_MODEL_MAX_HIDDEN = 3
+MLP_MODEL_MAX_ROWS = 1024
+MLP_MODEL_MAX_GROUPS = 8
+
+
+class MLPModelConfig(ctypes.Structure):  # acme_mlp_model_config
+    _fields_ = [("obs_dim", c_i32), ("num_actions", c_i32), ("max_batch", c_i32),
+                ("max_rows", c_i32), ("num_hidden", c_i32),
+                ("hidden", c_i32 * MLP_MODEL_MAX_HIDDEN), ("learning_rate", c_f32),
+                ("adam_beta1", c_f32), ("adam_beta2", c_f32), ("adam_epsilon", c_f32)]
+
+
+class MLPModelOutputs(ctypes.Structure):
+    _fields_ = [("loss", c_vp), ("state_loss", c_vp), ("reward_loss", c_vp),
+                ("discount_loss", c_vp)]
+
+
 _SIGS = {
     "acme_last_error": (ctypes.c_char_p, []),
     "acme_tune_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),
@@ -343,6 +362,9 @@ _SIGS = {
     "acme_dmpo_init_duals": (c_i32, [c_vp]),
     "acme_az_step": (c_i32, [c_vp, ctypes.POINTER(AZBatch), ctypes.POINTER(AZOutputs), c_vp]),
     "acme_az_evaluate": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "acme_mlp_model_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                    ctypes.POINTER(MLPModelOutputs), c_vp]),
+    "acme_mlp_model_predict": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),
@@ -405,7 +427,8 @@ for _learner in (
         dict(prefix="mpo", config=MPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
         dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
         dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2)),
-        dict(prefix="az", config=AZConfig, bind=4)):  # no target
+        dict(prefix="az", config=AZConfig, bind=4),  # no target
+        dict(prefix="mlp_model", config=MLPModelConfig, bind=4)):  # no target
     _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

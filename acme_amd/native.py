@@ -1319,6 +1319,88 @@ class NativeAZ(_NativeLearner):
         return out[:rows * A].view(rows, A), out[rows * A:]
 
 
+class NativeMLPModel(_NativeLearner):
+    """acme_mlp_model: the MCTS agent's learned transition model (three MLP towers on
+    [o, onehot(a)]: next state, reward, discount logit) + its flat buffers.  `step` is one SGD
+    step in two launches on rows of a device transition ring picked by device indices;
+    `predict_packed` is the whole model in one launch.  The step's losses are the device
+    scalars `loss`, `state_loss`, `reward_loss`, `discount_loss`."""
+
+    _prefix, _tag = "acme_mlp_model", "mlp_model"
+    _has_target = False
+
+    def __init__(self, *, obs_dim: int, hidden: Sequence[int], num_actions: int, max_batch: int,
+                 max_rows: int = 1, learning_rate: float = 1e-3, adam_beta1: float = 0.9,
+                 adam_beta2: float = 0.999, adam_epsilon: float = 1e-8, device=None):
+        cfg = _lib.MLPModelConfig()
+        if not 1 <= len(hidden) <= _lib.MLP_MODEL_MAX_HIDDEN:
+            raise ValueError(f"num_hidden must be in [1, {_lib.MLP_MODEL_MAX_HIDDEN}], got "
+                             f"{len(hidden)}")
+        cfg.obs_dim, cfg.num_actions = int(obs_dim), int(num_actions)
+        cfg.max_batch, cfg.max_rows = int(max_batch), int(max_rows)
+        cfg.num_hidden = len(hidden)
+        for i, s in enumerate(hidden):
+            cfg.hidden[i] = int(s)
+        cfg.learning_rate = float(learning_rate)
+        cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
+        self.obs_dim, self.num_actions = int(obs_dim), int(num_actions)
+        self.max_batch, self.max_rows = int(max_batch), int(max_rows)
+        self.learning_rate = float(learning_rate)
+        self.row_floats = 2 * self.obs_dim + 3  # o_t[D], a, r, d, o_tp1[D]
+        _lib.require_gpu()
+        self._create(cfg, device)
+        self._losses = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self.loss, self.state_loss, self.reward_loss, self.discount_loss = (
+            self._losses[i:i + 1] for i in range(4))
+        self._out = _lib.MLPModelOutputs()
+        self._out.loss, self._out.state_loss = ptr(self.loss), ptr(self.state_loss)
+        self._out.reward_loss, self._out.discount_loss = (ptr(self.reward_loss),
+                                                          ptr(self.discount_loss))
+
+    def step(self, ring: torch.Tensor, idx: torch.Tensor, stream=None) -> None:
+        """One SGD step on the rows idx (device int32 [B], each a row of ring) of the device
+        transition ring [capacity, >= 2 D + 3] float32: o_t, a, r, d, o_tp1 per row."""
+        if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dtype == torch.float32
+                and ring.dim() == 2 and ring.stride(1) == 1
+                and ring.shape[1] >= self.row_floats):
+            raise ValueError(f"ring must be a float32 device tensor [capacity, >= "
+                             f"{self.row_floats}] with unit inner stride")
+        if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int32
+                and idx.dim() == 1 and idx.is_contiguous()):
+            raise ValueError("idx must be a contiguous int32 device vector")
+        check(self._fn("step")(self._h, ptr(ring), int(ring.shape[0]), int(ring.stride(0)), ptr(idx),
+                               int(idx.shape[0]), ctypes.byref(self._out), stream_ptr(stream)),
+              "mlp_model step")
+
+    def predict_packed(self, state: torch.Tensor, actions=None, out: Optional[torch.Tensor] = None,
+                       stream=None) -> torch.Tensor:
+        """out [rows, D + 2] = next state, reward, discount logit of state [rows, >= D] (float32
+        on the device, unit inner stride; an earlier `out` may be the state) under `actions`: a
+        device int32 [rows], or a Python int for one row (passed by value, nothing uploaded)."""
+        if not (state.is_cuda and state.dtype == torch.float32 and state.dim() == 2
+                and state.stride(1) == 1 and state.shape[1] >= self.obs_dim):
+            raise ValueError(f"state must be float32 [rows, >= {self.obs_dim}] on the device "
+                             "with unit inner stride")
+        rows = int(state.shape[0])
+        if out is None:
+            out = torch.empty(rows, self.obs_dim + 2, dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.numel() == rows * (self.obs_dim + 2)):
+            raise ValueError(f"out must be contiguous float32 [rows, {self.obs_dim + 2}]")
+        if isinstance(actions, torch.Tensor):
+            if not (actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
+                    and actions.numel() == rows):
+                raise ValueError("actions must be a contiguous int32 device vector of rows")
+            a_ptr, a0 = ptr(actions), 0
+        else:
+            if rows != 1:
+                raise ValueError("an action by value serves one row")
+            a_ptr, a0 = None, int(actions)
+        check(self._fn("predict")(self._h, ptr(state), int(state.stride(0)), a_ptr, a0, rows,
+                                  ptr(out), stream_ptr(stream)), "mlp_model predict")
+        return out
+
+
 class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):
     """acme_impala learner + its flat buffers (no target network)."""
 

@@ -194,6 +194,43 @@ class PolicyValueMLP:
         return dict(variables)
 
 
+@dataclasses.dataclass(frozen=True)
+class MLPTransitionModel:
+    """The MCTS agent's learned model (acme/agents/tf/mcts/models/mlp.py:33-75): three
+    snt.nets.MLP(hidden + (out,)) towers on [flatten(o), onehot(a)]: next state (out = the
+    flat observation size), reward (1) and discount logit (1)."""
+
+    obs_shape: Tuple[int, ...]
+    num_actions: int
+    hidden: Tuple[int, ...]
+    kind: str = dataclasses.field(default="mlp_transition_model", init=False)
+
+    def __init__(self, obs_shape: Sequence[int], num_actions: int, hidden: Sequence[int]):
+        object.__setattr__(self, "obs_shape", tuple(int(s) for s in obs_shape))
+        object.__setattr__(self, "num_actions", int(num_actions))
+        object.__setattr__(self, "hidden", tuple(int(h) for h in hidden))
+        object.__setattr__(self, "kind", "mlp_transition_model")
+        if not self.hidden:
+            raise ValueError("MLPTransitionModel needs at least one hidden layer")
+
+    @property
+    def obs_dim(self) -> int:
+        return int(np.prod(self.obs_shape))
+
+    def tensor_shapes(self):
+        out = []
+        for tower, last in (("state_network", self.obs_dim), ("reward_network", 1),
+                            ("discount_network", 1)):
+            d = self.obs_dim + self.num_actions
+            for i, h in enumerate(self.hidden + (last,)):
+                out.append((f"{tower}/linear_{i}/w", (d, h)))
+                out.append((f"{tower}/linear_{i}/b", (h,)))
+                d = h
+        return out
+
+    init = MLP.init
+
+
 # ------------------------------------------------------------------ D4PG (control suite)
 
 

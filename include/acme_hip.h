@@ -1316,6 +1316,86 @@ int acme_az_set_num_steps(acme_az* l, int64_t n);
  * pre-activation, [B, H]). */
 int acme_az_debug_buffer(const acme_az* l, const char* name, const float** out, int64_t* count);
 
+/* ------------------------------------------------- MCTS / learned MLP model -- */
+/* The MCTS agent's learned environment model (acme/agents/tf/mcts/models/mlp.py,
+ * MLPTransitionModel + MLPModel._step).  Three towers share one input
+ * e = [flatten(o) (+) onehot(a, A)] of width D + A; each is snt.nets.MLP(hidden + (out,))
+ * with ReLU between the layers and none at the end: next state (out = D), reward (out = 1)
+ * and discount logit (out = 1).  Flat buffer: state_network/linear_i/{w,b}, then
+ * reward_network/linear_i/{w,b}, then discount_network/linear_i/{w,b}.
+ *
+ * Limits (acme_mlp_model_create refuses anything else, naming the field; they keep every
+ * layer of a 16-row tile in LDS, so one fused path serves everything accepted):
+ *   obs_dim in [1, ACME_MLP_MODEL_MAX_WIDTH], every hidden[i] in [1, ACME_MLP_MODEL_MAX_WIDTH]
+ *   (any value); num_actions in [1, ACME_MLP_MODEL_MAX_ACTIONS];
+ *   num_hidden in [1, ACME_MLP_MODEL_MAX_HIDDEN];
+ *   max_batch and max_rows in [1, ACME_MLP_MODEL_MAX_ROWS]. */
+#define ACME_MLP_MODEL_MAX_WIDTH 256
+#define ACME_MLP_MODEL_MAX_ACTIONS 64
+#define ACME_MLP_MODEL_MAX_HIDDEN 3
+#define ACME_MLP_MODEL_MAX_ROWS 1024
+/* Row groups per tower of the training launch: each owns one slot of the gradient slab
+ * [groups][flat] and takes its 16-row tiles in ascending order. */
+#define ACME_MLP_MODEL_MAX_GROUPS 8
+
+typedef struct acme_mlp_model acme_mlp_model;
+
+typedef struct acme_mlp_model_config {
+  int32_t obs_dim;              /* D: flat observation size */
+  int32_t num_actions;          /* A */
+  int32_t max_batch;            /* largest B of acme_mlp_model_step */
+  int32_t max_rows;             /* largest rows of acme_mlp_model_predict */
+  int32_t num_hidden;
+  int32_t hidden[ACME_MLP_MODEL_MAX_HIDDEN];
+  float learning_rate;          /* snt.optimizers.Adam */
+  float adam_beta1, adam_beta2, adam_epsilon;
+} acme_mlp_model_config;
+
+/* Device scalars (each optional): loss = state_loss + reward_loss + discount_loss,
+ * state_loss = mean_{b,k} (s_hat - o_tp1)^2, reward_loss = mean_b (r_hat - r)^2,
+ * discount_loss = mean_b [max(x, 0) - x d + log1p(exp(-|x|))] for the discount logit x. */
+typedef struct acme_mlp_model_outputs {
+  float* loss;
+  float* state_loss;
+  float* reward_loss;
+  float* discount_loss;
+} acme_mlp_model_outputs;
+
+int acme_mlp_model_create(const acme_mlp_model_config* cfg, acme_mlp_model** out);
+int acme_mlp_model_destroy(acme_mlp_model* l);
+int64_t acme_mlp_model_flat_size(const acme_mlp_model* l);
+int32_t acme_mlp_model_num_tensors(const acme_mlp_model* l);
+int acme_mlp_model_tensor_info(const acme_mlp_model* l, int32_t i, int64_t* offset,
+                               int64_t* numel, int32_t* ndim, int64_t* shape4,
+                               const char** name);
+/* Flat device buffers of acme_mlp_model_flat_size floats each (gradients and moments zeroed). */
+int acme_mlp_model_bind(acme_mlp_model* l, float* params, float* grads, float* adam_m,
+                        float* adam_v);
+/* One SGD step on `stream` in two launches, no host synchronisation.  `ring` is the
+ * transition ring, ring_rows f32 rows of ld_ring >= 2 D + 3 floats holding o_t[D], a, r, d,
+ * o_tp1[D]; `idx` is a device int32[B] of ring rows (duplicates allowed; an entry outside
+ * [0, ring_rows) is clamped into it by the kernel, so it reads a wrong row, never outside
+ * the ring).  Launch 1 gathers the rows, runs each tower forward and backward through LDS and
+ * writes the row groups' gradient partials; launch 2 sums them in group order into the grads
+ * buffer, applies Adam at t = num_steps + 1 and writes the losses. */
+int acme_mlp_model_step(acme_mlp_model* l, const float* ring, int64_t ring_rows,
+                        int64_t ld_ring, const int32_t* idx, int64_t B, const acme_mlp_model_outputs* out,
+                        void* stream);
+/* The whole model in one launch: out [rows, D + 2] = next state, reward, discount logit of
+ * state [rows, ld_state] (the first D floats of a row are read, so an earlier `out` can be
+ * the next `state`; the two ranges must not overlap) and actions (device int32[rows]).  With
+ * actions == NULL and rows == 1 the action is action0.  Changes no learner state. */
+int acme_mlp_model_predict(acme_mlp_model* l, const float* state, int64_t ld_state,
+                           const int32_t* actions, int32_t action0, int64_t rows, float* out,
+                           void* stream);
+int64_t acme_mlp_model_num_steps(const acme_mlp_model* l);
+int acme_mlp_model_set_num_steps(acme_mlp_model* l, int64_t n);
+/* Internal device workspaces (tests) of the last step over B rows, in idx order: "pred"
+ * [B, D + 2] (next state, reward, discount logit) and "dout" [B, D + 2] (the loss gradient
+ * at those outputs). */
+int acme_mlp_model_debug_buffer(const acme_mlp_model* l, const char* name, const float** out,
+                                int64_t* count);
+
 /* ------------------------------------------------------------- profiling -- */
 /* Section profiler: when enabled, every kernel section records a HIP event pair on the
  * stream it is launched on, tagged with its algorithmic FLOPs / HBM bytes. */

@@ -1,0 +1,120 @@
+"""Numpy float64 restatement of the MCTS agent's learned model
+(acme/agents/tf/mcts/models/mlp.py): the three-tower forward, the losses and their gradients,
+snt.Adam, and the model's update / step / reset / checkpoint logic on given batch indices."""
+
+from __future__ import annotations
+
+import numpy as np
+
+from acme_amd.networks import MLPTransitionModel
+from tests.az_oracle import AZConfig as Config  # obs_dim, hidden, num_actions; lr, b1, b2, eps
+from tests.az_oracle import adam_update
+
+TOWERS = ("state_network", "reward_network", "discount_network")
+MID, LAST = 1, 2  # dm_env.StepType
+
+
+def tensor_shapes(cfg: Config):
+    return MLPTransitionModel((cfg.obs_dim,), cfg.num_actions, cfg.hidden).tensor_shapes()
+
+
+def forward(cfg: Config, params, obs, actions, f=np.float64):
+    """(next state [rows, D], reward [rows], discount logit [rows], acts): acts[tower] lists the
+    inputs of the tower's layers, starting with e = [obs, onehot(actions)]."""
+    obs = np.asarray(obs, f).reshape(len(actions), -1)
+    e = np.concatenate([obs, np.eye(cfg.num_actions, dtype=f)[np.asarray(actions, int)]], axis=1)
+    outs, acts = [], {}
+    L = len(cfg.hidden) + 1
+    for tower in TOWERS:
+        x, acts[tower] = e, [e]
+        for i in range(L):
+            x = x @ params[f"{tower}/linear_{i}/w"].astype(f) + params[f"{tower}/linear_{i}/b"].astype(f)
+            if i + 1 < L:
+                x = np.maximum(x, 0)
+                acts[tower].append(x)
+        outs.append(x)
+    return outs[0], outs[1][:, 0], outs[2][:, 0], acts
+
+
+def batch_of(cfg: Config, ring, idx):
+    D, rows = cfg.obs_dim, np.asarray(ring, np.float64)[np.asarray(idx, int)]
+    return dict(o_t=rows[:, :D], a=rows[:, D].astype(int), r=rows[:, D + 1], d=rows[:, D + 2],
+                o_tp1=rows[:, D + 3:2 * D + 3])
+
+
+def loss_and_grads(cfg: Config, params, batch):
+    B, D, L = len(batch["r"]), cfg.obs_dim, len(cfg.hidden) + 1
+    s, r, x, acts = forward(cfg, params, batch["o_t"], batch["a"])
+    d = batch["d"]
+    losses = [np.mean((s - batch["o_tp1"]) ** 2), np.mean((r - batch["r"]) ** 2),
+              np.mean(np.maximum(x, 0) - x * d + np.log1p(np.exp(-np.abs(x))))]
+    dout = [2 * (s - batch["o_tp1"]) / (B * D), (2 * (r - batch["r"]) / B)[:, None],
+            ((1 / (1 + np.exp(-x)) - d) / B)[:, None]]
+    grads = {}
+    for tower, dz in zip(TOWERS, dout):
+        for i in range(L - 1, -1, -1):
+            grads[f"{tower}/linear_{i}/w"] = acts[tower][i].T @ dz
+            grads[f"{tower}/linear_{i}/b"] = dz.sum(axis=0)
+            if i > 0:
+                dz = (dz @ params[f"{tower}/linear_{i}/w"].astype(np.float64).T) * (acts[tower][i] > 0)
+    out = dict(loss=sum(losses), state_loss=losses[0], reward_loss=losses[1],
+               discount_loss=losses[2], pred=np.column_stack([s, r, x]), dout=np.column_stack(dout),
+               acts=acts)
+    return out, grads
+
+
+def step(cfg: Config, state: dict, batch: dict):
+    out, grads = loss_and_grads(cfg, state["params"], batch)
+    t = state["num_steps"] + 1
+    new = dict(params={}, m={}, v={}, num_steps=t)
+    for k in state["params"]:
+        new["params"][k], new["m"][k], new["v"][k] = adam_update(
+            state["params"][k], grads[k], state["m"][k], state["v"][k], t, cfg)
+    return out, grads, new
+
+
+class Model:
+    """MLPModel's logic (mlp.py:139-221) on the oracle's network; a timestep is the tuple
+    (step type, reward, observation).  `indices` of update() are the batch's ring rows."""
+
+    def __init__(self, cfg: Config, state: dict, capacity: int, batch_size: int,
+                 terminal_tol: float = 1e-3, sigmoid: bool = False):
+        self.cfg, self.state = cfg, state
+        self.ring = np.zeros((capacity, 2 * cfg.obs_dim + 3))
+        self.num_added, self.batch_size = 0, batch_size
+        self.tol, self.sigmoid = terminal_tol, sigmoid
+        self.needs_reset = True
+
+    def step(self, action):
+        assert not self.needs_reset
+        s, r, x, _ = forward(self.cfg, self.state["params"], self._state[None], [action])
+        self._state = s[0]
+        discount = 1 / (1 + np.exp(-x[0])) if self.sigmoid else 1.0  # softmax of one logit is 1
+        if discount < self.tol:
+            self.needs_reset = True
+            return LAST, r[0], self._state.copy()
+        return MID, r[0], self._state.copy()
+
+    def reset(self, initial_state):
+        self._state = np.asarray(initial_state, np.float64).reshape(-1).copy()
+        self.needs_reset = False
+
+    def update(self, o_t, action, reward, discount, o_tp1, last: bool, indices):
+        o_t, o_tp1 = (np.asarray(o, np.float64).reshape(-1) for o in (o_t, o_tp1))
+        self.ring[self.num_added % len(self.ring)] = np.concatenate(
+            [o_t, [action, reward, discount], o_tp1])
+        self.num_added += 1
+        ts = self.step(action)
+        self._state = o_tp1.copy()
+        if ts[0] == LAST or last:
+            self.needs_reset = True
+        if min(self.num_added, len(self.ring)) >= self.batch_size:
+            _, _, self.state = step(self.cfg, self.state, batch_of(self.cfg, self.ring, indices))
+        return ts
+
+    def save_checkpoint(self):
+        assert not self.needs_reset
+        self._checkpoint = self._state.copy()
+
+    def load_checkpoint(self):
+        self.needs_reset, self._state = False, self._checkpoint.copy()
