@@ -590,11 +590,13 @@ int acme_mlp_model_bind(acme_mlp_model* l, float* params, float* grads, float* a
 int acme_mlp_model_step(acme_mlp_model* l, const float* ring, int64_t ring_rows, int64_t ld_ring,
                         const int32_t* idx, int64_t B, const acme_mlp_model_outputs* out,
                         void* stream) {
-  ACME_CHECK_ARG(l && ring && idx, "null argument");
+  ACME_CHECK_ARG(l, "null learner");
   ACME_CHECK_ARG(l->params, "acme_mlp_model_step before acme_mlp_model_bind");
+  // Before the pointers: an empty batch's idx is a null pointer, and the batch is what is wrong.
   ACME_CHECK_ARG(B >= 1 && B <= l->cfg.max_batch,
                  "batch must be in [1, max_batch = %d], got %lld", l->cfg.max_batch,
                  (long long)B);
+  ACME_CHECK_ARG(ring && idx, "null argument");
   ACME_CHECK_ARG(ld_ring >= 2 * (int64_t)l->cfg.obs_dim + 3,
                  "ld_ring must be >= 2 obs_dim + 3 = %d, got %lld", 2 * l->cfg.obs_dim + 3,
                  (long long)ld_ring);

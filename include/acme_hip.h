@@ -1375,7 +1375,8 @@ int acme_mlp_model_bind(acme_mlp_model* l, float* params, float* grads, float* a
  * transition ring, ring_rows f32 rows of ld_ring >= 2 D + 3 floats holding o_t[D], a, r, d,
  * o_tp1[D]; `idx` is a device int32[B] of ring rows (duplicates allowed; an entry outside
  * [0, ring_rows) is clamped into it by the kernel, so it reads a wrong row, never outside
- * the ring).  Launch 1 gathers the rows, runs each tower forward and backward through LDS and
+ * the ring).  A row's action outside [0, A) sets no one-hot column: its e is [o_t, 0].
+ * Launch 1 gathers the rows, runs each tower forward and backward through LDS and
  * writes the row groups' gradient partials; launch 2 sums them in group order into the grads
  * buffer, applies Adam at t = num_steps + 1 and writes the losses. */
 int acme_mlp_model_step(acme_mlp_model* l, const float* ring, int64_t ring_rows,
@@ -1384,7 +1385,8 @@ int acme_mlp_model_step(acme_mlp_model* l, const float* ring, int64_t ring_rows,
 /* The whole model in one launch: out [rows, D + 2] = next state, reward, discount logit of
  * state [rows, ld_state] (the first D floats of a row are read, so an earlier `out` can be
  * the next `state`; the two ranges must not overlap) and actions (device int32[rows]).  With
- * actions == NULL and rows == 1 the action is action0.  Changes no learner state. */
+ * actions == NULL and rows == 1 the action is action0.  An action outside [0, A) sets no
+ * one-hot column, as in the step.  Changes no learner state. */
 int acme_mlp_model_predict(acme_mlp_model* l, const float* state, int64_t ld_state,
                            const int32_t* actions, int32_t action0, int64_t rows, float* out,
                            void* stream);

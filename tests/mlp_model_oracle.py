@@ -20,9 +20,11 @@ def tensor_shapes(cfg: Config):
 
 def forward(cfg: Config, params, obs, actions, f=np.float64):
     """(next state [rows, D], reward [rows], discount logit [rows], acts): acts[tower] lists the
-    inputs of the tower's layers, starting with e = [obs, onehot(actions)]."""
+    inputs of the tower's layers, starting with e = [obs, onehot(actions)].  An action outside
+    [0, A) sets no one-hot column, as in the kernels."""
     obs = np.asarray(obs, f).reshape(len(actions), -1)
-    e = np.concatenate([obs, np.eye(cfg.num_actions, dtype=f)[np.asarray(actions, int)]], axis=1)
+    onehot = (np.asarray(actions, int)[:, None] == np.arange(cfg.num_actions)[None, :]).astype(f)
+    e = np.concatenate([obs, onehot], axis=1)
     outs, acts = [], {}
     L = len(cfg.hidden) + 1
     for tower in TOWERS:
@@ -36,8 +38,12 @@ def forward(cfg: Config, params, obs, actions, f=np.float64):
     return outs[0], outs[1][:, 0], outs[2][:, 0], acts
 
 
-def batch_of(cfg: Config, ring, idx):
-    D, rows = cfg.obs_dim, np.asarray(ring, np.float64)[np.asarray(idx, int)]
+def batch_of(cfg: Config, ring, idx, clamp=False):
+    """The batch of ring rows idx; clamp: idx is first clipped into the ring, as the kernel does."""
+    idx = np.asarray(idx, int)
+    if clamp:
+        idx = np.clip(idx, 0, len(ring) - 1)
+    D, rows = cfg.obs_dim, np.asarray(ring, np.float64)[idx]
     return dict(o_t=rows[:, :D], a=rows[:, D].astype(int), r=rows[:, D + 1], d=rows[:, D + 2],
                 o_tp1=rows[:, D + 3:2 * D + 3])
 

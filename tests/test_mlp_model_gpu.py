@@ -63,12 +63,14 @@ def _check_pred(cfg, params, got, ref, acts, tag):
         _close(got[:, col], ref[:, col], name=f"{tower}{tag}", scale=scale)
 
 
-def _check_step(n, cfg, state, ring, idx, tag=""):
-    """One native step on ring rows idx from `state` (which the learner holds)."""
+def _check_step(n, cfg, state, ring, idx, tag="", dev=None, clamp=False):
+    """One native step on ring rows idx from `state` (which the learner holds).  dev: the device
+    tensor that holds `ring` (a view of a larger one, say), else ring is uploaded; clamp: the
+    oracle clips idx into the ring, as the kernel does."""
     B = len(idx)
-    n.step(torch.as_tensor(ring).cuda(), torch.as_tensor(idx).cuda())
+    n.step(torch.as_tensor(ring).cuda() if dev is None else dev, torch.as_tensor(idx).cuda())
     torch.cuda.synchronize()
-    out, grads, new = O.step(cfg, state, O.batch_of(cfg, ring, idx))
+    out, grads, new = O.step(cfg, state, O.batch_of(cfg, ring, idx, clamp=clamp))
     for k in ("loss", "state_loss", "reward_loss", "discount_loss"):
         got = getattr(n, k).item()
         assert np.isfinite(got), k
