@@ -243,6 +243,17 @@ class MLPModelOutputs(ctypes.Structure):
                 ("discount_loss", c_vp)]
 
 
+MCTS_SEARCH_MAX_WIDTH = 256
+MCTS_SEARCH_LDS_BYTES = 163840
+MCTS_SEARCH_FIXED_BYTES = 16384
+MCTS_SEARCH_TREE_BYTES = 131072
+
+
+class MCTSSearchConfig(ctypes.Structure):  # acme_mcts_search_config
+    _fields_ = [("az", c_vp), ("model", c_vp), ("max_simulations", c_i32),
+                ("stream_weights", c_i32)]
+
+
 _SIGS = {
     "acme_last_error": (ctypes.c_char_p, []),
     "acme_tune_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),
@@ -365,6 +376,13 @@ _SIGS = {
     "acme_mlp_model_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                     ctypes.POINTER(MLPModelOutputs), c_vp]),
     "acme_mlp_model_predict": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
+    "acme_mcts_search_create": (c_i32, [ctypes.POINTER(MCTSSearchConfig),
+                                        ctypes.POINTER(c_vp)]),
+    "acme_mcts_search_destroy": (c_i32, [c_vp]),
+    "acme_mcts_search_run": (c_i32, [c_vp, c_vp, c_i32, c_f32, c_i32, c_f32, c_u64, c_u64, c_vp,
+                                     c_vp]),
+    "acme_mcts_search_debug_buffer": (c_i32, [c_vp, ctypes.c_char_p, ctypes.POINTER(c_vp),
+                                              ctypes.POINTER(c_i64)]),
     "acme_profile_enable": (c_i32, [c_i32]),
     "acme_profile_reset": (c_i32, []),
     "acme_profile_num_sections": (c_i32, []),

@@ -1,6 +1,7 @@
 """MCTS agent — drop-in for acme/agents/tf/mcts/agent.py:33-100: an MCTSActor planning on
 `model` with the learner's policy-value network, and an AZLearner trained on the stored
-transitions and search policies.  Same constructor; the replay table lives in GPU memory."""
+transitions and search policies.  Same constructor; the replay table lives in GPU memory.
+search="native" runs the actor's tree search on the device (acting.MCTSActor)."""
 
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ class MCTS(agent.Agent):
 
     def __init__(self, network: PolicyValueMLP, model, optimizer, n_step: int, discount: float,
                  replay_capacity: int, num_simulations: int,
-                 environment_spec: specs.EnvironmentSpec, batch_size: int, seed: int = 0):
+                 environment_spec: specs.EnvironmentSpec, batch_size: int, seed: int = 0,
+                 search: str = "host"):
         if not isinstance(network, PolicyValueMLP):
             raise ValueError("acme_amd's MCTS agent takes a networks.PolicyValueMLP, not a "
                              f"{type(network).__name__}")
@@ -45,6 +47,6 @@ class MCTS(agent.Agent):
                                      discount=discount, batch_size=batch_size, seed=seed)
         actor = acting.MCTSActor(environment_spec=environment_spec, model=model, network=learner,
                                  discount=discount, adder=adder,
-                                 num_simulations=num_simulations)
+                                 num_simulations=num_simulations, search=search, seed=seed)
         super().__init__(actor=actor, learner=learner, min_observations=10,
                          observations_per_step=1)

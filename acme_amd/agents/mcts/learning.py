@@ -83,6 +83,11 @@ class AZLearner(Learner):
         probs, values = np.concatenate(probs), np.concatenate(values)
         return (probs[0], float(values[0])) if single else (probs, values)
 
+    @property
+    def native(self) -> NativeAZ:
+        """The native learner, whose parameters the device search reads in place."""
+        return self._native
+
     def get_variables(self, names: List[str]) -> List[Dict[str, np.ndarray]]:
         # As the TF learner: the online network's variables whatever the names.
         del names

@@ -164,3 +164,20 @@ class MLPModel(base.Model):
     @property
     def native(self) -> NativeMLPModel:
         return self._native
+
+    @property
+    def state_row(self) -> torch.Tensor:
+        """The current state on the device, float32 [D]: a read-only view of the current
+        prediction buffer's row (the device search reads its root from it in place)."""
+        if self._needs_reset:
+            raise ValueError("Model must be reset with an initial timestep.")
+        return self._bufs[self._cur, :self._D]
+
+    @property
+    def sigmoid_discount(self) -> bool:
+        """discount_activation == 'sigmoid': step() can return a termination."""
+        return self._sigmoid
+
+    @property
+    def terminal_tol(self) -> float:
+        return self._terminal_tol

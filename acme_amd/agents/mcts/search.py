@@ -117,7 +117,12 @@ def puct(node: Node, ucb_scaling: float = 1.0,
 def visit_count_policy(root: Node, temperature: float = 1.0) -> types.Probs:
     """Probabilities proportional to visits^(1 / temperature); uniform when nothing was
     visited."""
-    visits = root.children_visits
+    return visits_policy(root.children_visits, temperature)
+
+
+def visits_policy(visits: np.ndarray, temperature: float = 1.0) -> types.Probs:
+    """visit_count_policy on the root's visit counts themselves (the device search returns
+    them without a tree)."""
     if np.sum(visits) == 0:
         visits = visits + 1
     scaled = visits ** (1 / temperature)

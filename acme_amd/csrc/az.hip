@@ -33,6 +33,7 @@
 #include "dense_launch.h"
 #include "kernels.h"
 #include "learner_common.h"
+#include "net_views.h"
 #include "profiler.h"
 
 using namespace acme;
@@ -557,3 +558,23 @@ int acme_az_debug_buffer(const acme_az* l, const char* name, const float** out, 
 }
 
 }  // extern "C"
+
+// The network as mcts_search.hip reads it (net_views.h).
+void acme::az_view(const acme_az* l, AzView* out) {
+  const acme_az_config& c = l->cfg;
+  out->params = l->params;
+  out->flat = l->flat;
+  out->obs_dim = c.obs_dim;
+  out->num_actions = c.num_actions;
+  out->nl = l->nl;
+  out->relu_final = c.activate_final;
+  for (int i = 0; i < ACME_MAX_MLP_LAYERS; ++i) {
+    out->sizes[i] = i < l->nl ? c.hidden[i] : 0;
+    out->w[i] = i < l->nl ? (int)l->tensors[l->w[i]].offset : 0;
+    out->b[i] = i < l->nl ? (int)l->tensors[l->b[i]].offset : 0;
+  }
+  out->pw = (int)l->tensors[l->pw].offset;
+  out->pb = (int)l->tensors[l->pb].offset;
+  out->vw = (int)l->tensors[l->vw].offset;
+  out->vb = (int)l->tensors[l->vb].offset;
+}

@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "learner_common.h"
+#include "net_views.h"
 #include "profiler.h"
 
 using namespace acme;
@@ -658,3 +659,17 @@ int acme_mlp_model_debug_buffer(const acme_mlp_model* l, const char* name, const
 }
 
 }  // extern "C"
+
+// The model as mcts_search.hip reads it (net_views.h).
+void acme::mlp_model_view(const acme_mlp_model* l, MlpModelView* out) {
+  static_assert(sizeof(out->width) == sizeof(l->tw.width) && sizeof(out->woff) == sizeof(l->tw.woff),
+                "MlpModelView mirrors Towers");
+  out->params = l->params;
+  out->flat = l->flat;
+  out->obs_dim = l->cfg.obs_dim;
+  out->num_actions = l->cfg.num_actions;
+  out->L = l->tw.L;
+  std::memcpy(out->width, l->tw.width, sizeof(out->width));
+  std::memcpy(out->woff, l->tw.woff, sizeof(out->woff));
+  std::memcpy(out->boff, l->tw.boff, sizeof(out->boff));
+}

@@ -1401,6 +1401,69 @@ class NativeMLPModel(_NativeLearner):
         return out
 
 
+class NativeMCTSSearch:
+    """acme_mcts_search: the whole tree search of search.mcts + search.puct on the learned model
+    in one launch.  It reads the parameters of `az` (NativeAZ) and `model` (NativeMLPModel) in
+    place and keeps both alive.  `run` returns the packed device row [3 A + 4]: root visits,
+    root child values, root prior, root value, nodes used, deepest path, status."""
+
+    def __init__(self, az: "NativeAZ", model: "NativeMLPModel", max_simulations: int,
+                 stream_weights: bool = False):
+        if az.device != model.device:
+            raise ValueError(f"the network is on {az.device}, the model on {model.device}")
+        self._az, self._model = az, model
+        self.device, self.num_actions = az.device, az.num_actions
+        self.max_simulations = int(max_simulations)
+        cfg = _lib.MCTSSearchConfig()
+        cfg.az, cfg.model = az._h.value, model._h.value  # noqa: SLF001
+        cfg.max_simulations, cfg.stream_weights = self.max_simulations, int(bool(stream_weights))
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib().acme_mcts_search_create(ctypes.byref(cfg), ctypes.byref(h)),
+                  "mcts_search create")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                lib().acme_mcts_search_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def run(self, root_state: torch.Tensor, num_simulations: int, discount: float = 1.0,
+            sigmoid: bool = False, terminal_tol: float = 1e-3, seed: int = 0,
+            call_counter: int = 0, out: Optional[torch.Tensor] = None,
+            stream=None) -> torch.Tensor:
+        """One search from root_state (float32 [obs_dim] on the device, read in place)."""
+        D, n = self._model.obs_dim, 3 * self.num_actions + 4
+        if not (isinstance(root_state, torch.Tensor) and root_state.is_cuda
+                and root_state.dtype == torch.float32 and root_state.is_contiguous()
+                and root_state.numel() == D):
+            raise ValueError(f"root_state must be contiguous float32 [{D}] on the device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.numel() == n):
+            raise ValueError(f"out must be contiguous float32 [{n}] on the device")
+        check(lib().acme_mcts_search_run(self._h, ptr(root_state), int(num_simulations),
+                                         float(discount), int(bool(sigmoid)), float(terminal_tol),
+                                         int(seed), int(call_counter), ptr(out),
+                                         stream_ptr(stream)), "mcts_search run")
+        return out
+
+    def unpack(self, row: np.ndarray) -> Dict[str, np.ndarray]:
+        """The fields of a host copy of the packed row."""
+        A = self.num_actions
+        return dict(visits=row[:A].astype(np.int64), values=row[A:2 * A], prior=row[2 * A:3 * A],
+                    root_value=float(row[3 * A]), nodes=int(row[3 * A + 1]),
+                    deepest=int(row[3 * A + 2]), status=int(row[3 * A + 3]))
+
+    def debug_buffer(self, name: str) -> np.ndarray:
+        return _debug_buffer(lib().acme_mcts_search_debug_buffer, self._h, name, self.device)
+
+
 class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):
     """acme_impala learner + its flat buffers (no target network)."""
 

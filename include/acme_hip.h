@@ -1398,6 +1398,62 @@ int acme_mlp_model_set_num_steps(acme_mlp_model* l, int64_t n);
 int acme_mlp_model_debug_buffer(const acme_mlp_model* l, const char* name, const float** out,
                                 int64_t* count);
 
+/* --------------------------------------------------- MCTS / device search -- */
+/* The whole tree search of search.mcts + search.puct (acme/agents/tf/mcts/search.py) on the
+ * learned model, for the configuration MCTSActor uses (exploration_fraction = 0, so no
+ * Dirichlet draw; ucb_scaling = 1): ONE launch of one workgroup per call.  It reads the
+ * parameters of an acme_az and an acme_mlp_model in place, keeps the tree's statistics in LDS
+ * and every node's model state in a device workspace, and runs one model forward and one
+ * network forward per simulation (the model is deterministic, so a node's state is cached).
+ * All arithmetic is f32; every sum has a fixed order, so a call repeats bit for bit.
+ *
+ * Limits (acme_mcts_search_create refuses anything else, naming the field):
+ *   az and model non-null, with equal obs_dim and equal num_actions;
+ *   az obs_dim and every az hidden[i] <= ACME_MCTS_SEARCH_MAX_WIDTH (one row's activations
+ *     and a column per thread of a 256-thread group; wider networks are not served);
+ *   max_simulations >= 1 with the tree inside its LDS share:
+ *     (20 num_actions + 8) (max_simulations + 1) <= ACME_MCTS_SEARCH_TREE_BYTES
+ *     (per node prior, N, W, R, child per action, and one (node, action) path entry);
+ *   stream_weights 0 or 1.
+ * Weights: with stream_weights = 0 both flat parameter buffers are staged into LDS once per
+ * call when 4 (az flat + model flat) <= ACME_MCTS_SEARCH_LDS_BYTES -
+ * ACME_MCTS_SEARCH_FIXED_BYTES - the tree's bytes, all or nothing; otherwise, or with
+ * stream_weights = 1, they are read from global memory / L2. */
+#define ACME_MCTS_SEARCH_MAX_WIDTH 256
+#define ACME_MCTS_SEARCH_LDS_BYTES 163840
+#define ACME_MCTS_SEARCH_FIXED_BYTES 16384
+#define ACME_MCTS_SEARCH_TREE_BYTES 131072
+
+typedef struct acme_mcts_search acme_mcts_search;
+
+typedef struct acme_mcts_search_config {
+  const acme_az* az;            /* the policy-value network; must outlive the search */
+  const acme_mlp_model* model;  /* the learned model; must outlive the search */
+  int32_t max_simulations;      /* largest num_simulations of acme_mcts_search_run */
+  int32_t stream_weights;       /* 1: never stage the weights into LDS */
+} acme_mcts_search_config;
+
+int acme_mcts_search_create(const acme_mcts_search_config* cfg, acme_mcts_search** out);
+int acme_mcts_search_destroy(acme_mcts_search* h);
+/* One search of num_simulations in [1, max_simulations] simulations from root_state (device
+ * f32 [obs_dim], e.g. the model's current prediction row) on `stream`, under the parameters
+ * both networks hold when the launch runs.  sigmoid = 1: an edge whose discount logit x has
+ * sigmoid(x) < terminal_tol is terminal (value 0, never expanded); sigmoid = 0: no edge is.
+ * Ties of the PUCT maximum: selection k = 0, 1, ... of the call (tied or not) draws
+ * r = Philox4x32-10(counter (k, call_counter lo, call_counter hi, 0x4D435453 "MCTS"),
+ * key = seed) and takes the ((u64(r.x) * n) >> 32)-th of the n tied actions in ascending order.
+ * out (device f32 [3 A + 4]): root visit counts [A]; root child values W / N [A], 0 where
+ * unvisited; root prior [A]; root value; nodes used; deepest path (edges); status (0, or 1:
+ * a PUCT score was NaN or Inf and the search ended there).  Changes neither network. */
+int acme_mcts_search_run(acme_mcts_search* h, const float* root_state, int32_t num_simulations,
+                         float discount, int32_t sigmoid, float terminal_tol, uint64_t seed,
+                         uint64_t call_counter, float* out, void* stream);
+/* Internal device workspaces (tests) of the last call: "visits", [num_simulations + 1][A]
+ * edge visit counts per node in order of expansion (the root is node 0; rows past the nodes
+ * used are zero). */
+int acme_mcts_search_debug_buffer(const acme_mcts_search* h, const char* name,
+                                  const float** out, int64_t* count);
+
 /* ------------------------------------------------------------- profiling -- */
 /* Section profiler: when enabled, every kernel section records a HIP event pair on the
  * stream it is launched on, tagged with its algorithmic FLOPs / HBM bytes. */
