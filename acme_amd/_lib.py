@@ -192,6 +192,28 @@ class AZOutputs(ctypes.Structure):
     _fields_ = [("loss", c_vp), ("value_loss", c_vp), ("policy_loss", c_vp)]
 
 
+BC_MAX_WIDTH = 1024
+BC_MAX_ACTIONS = 1024
+BC_MAX_ROWS = 4096
+BC_FUSED_MAX_ROWS = 32
+BC_FUSED_MAX_WIDTH = 128
+
+
+class BCConfig(ctypes.Structure):  # acme_bc_config
+    _fields_ = [("obs_dim", c_i32), ("num_actions", c_i32), ("max_batch", c_i32),
+                ("max_act_rows", c_i32), ("num_hidden", c_i32),
+                ("hidden", c_i32 * MAX_MLP_LAYERS), ("learning_rate", c_f32),
+                ("adam_beta1", c_f32), ("adam_beta2", c_f32), ("adam_epsilon", c_f32)]
+
+
+class BCBatch(ctypes.Structure):
+    _fields_ = [("o_tm1", c_vp), ("a_tm1", c_vp), ("batch", c_i64)]
+
+
+class BCOutputs(ctypes.Structure):
+    _fields_ = [("loss", c_vp), ("gradient_norm", c_vp)]
+
+
 class IMPALAConfig(ctypes.Structure):
     _fields_ = [("torso", c_i32), ("obs_dim", c_i32), ("num_actions", c_i32),
                 ("max_batch", c_i32), ("max_sequence_length", c_i32), ("lstm_size", c_i32),
@@ -373,6 +395,8 @@ _SIGS = {
     "acme_dmpo_init_duals": (c_i32, [c_vp]),
     "acme_az_step": (c_i32, [c_vp, ctypes.POINTER(AZBatch), ctypes.POINTER(AZOutputs), c_vp]),
     "acme_az_evaluate": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "acme_bc_step": (c_i32, [c_vp, ctypes.POINTER(BCBatch), ctypes.POINTER(BCOutputs), c_vp]),
+    "acme_bc_act": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_u64, c_u64, c_vp, c_vp, c_vp]),
     "acme_mlp_model_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                     ctypes.POINTER(MLPModelOutputs), c_vp]),
     "acme_mlp_model_predict": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
@@ -446,6 +470,7 @@ for _learner in (
         dict(prefix="dmpo", config=DMPOConfig, bind=5, actor_critic=(MPOBatch, MPOOutputs, 2)),
         dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2)),
         dict(prefix="az", config=AZConfig, bind=4),  # no target
+        dict(prefix="bc", config=BCConfig, bind=4),  # no target
         dict(prefix="mlp_model", config=MLPModelConfig, bind=4)):  # no target
     _SIGS.update(_learner_sigs(**_learner))
 

@@ -1319,6 +1319,77 @@ class NativeAZ(_NativeLearner):
         return out[:rows * A].view(rows, A), out[rows * A:]
 
 
+class NativeBC(_NativeLearner):
+    """acme_bc learner (networks.MLP, sparse-label softmax cross-entropy, Adam) + its flat
+    buffers, and the acting call that runs the network and the epsilon-greedy selection on the
+    device.  The step's `loss` and `gradient_norm` are device scalars."""
+
+    _prefix, _tag = "acme_bc", "bc"
+    _has_target = False
+
+    def __init__(self, *, obs_dim: int, hidden: Sequence[int], num_actions: int, max_batch: int,
+                 max_act_rows: int = 1, learning_rate: float = 1e-3, adam_beta1: float = 0.9,
+                 adam_beta2: float = 0.999, adam_epsilon: float = 1e-8, device=None):
+        cfg = _lib.BCConfig()
+        if len(hidden) > _lib.MAX_MLP_LAYERS:
+            raise ValueError(f"hidden takes at most {_lib.MAX_MLP_LAYERS} layer sizes")
+        cfg.obs_dim, cfg.num_actions = int(obs_dim), int(num_actions)
+        cfg.max_batch, cfg.max_act_rows = int(max_batch), int(max_act_rows)
+        cfg.num_hidden = len(hidden)
+        for i, s in enumerate(hidden):
+            cfg.hidden[i] = int(s)
+        cfg.learning_rate = float(learning_rate)
+        cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
+        self.obs_dim, self.num_actions = int(obs_dim), int(num_actions)
+        self.max_batch, self.max_act_rows = int(max_batch), int(max_act_rows)
+        self.learning_rate = float(learning_rate)
+        _lib.require_gpu()
+        self._create(cfg, device)
+        self._scalars = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self.loss, self.gradient_norm = self._scalars[0:1], self._scalars[1:2]
+        self._out = _lib.BCOutputs()
+        self._out.loss, self._out.gradient_norm = ptr(self.loss), ptr(self.gradient_norm)
+
+    def step(self, o_tm1, a_tm1, stream=None):
+        B = int(a_tm1.shape[0])
+        for name, t, dt, n in (("o_tm1", o_tm1, torch.float32, B * self.obs_dim),
+                               ("a_tm1", a_tm1, torch.int32, B)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()
+                    and t.dtype == dt):
+                raise ValueError(f"{name} must be a contiguous {dt} device tensor")
+            if t.numel() != n:
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {n} elements")
+        b = _lib.BCBatch()
+        b.o_tm1, b.a_tm1, b.batch = ptr(o_tm1), ptr(a_tm1), B
+        check(self._fn("step")(self._h, ctypes.byref(b), ctypes.byref(self._out),
+                               stream_ptr(stream)), "bc step")
+
+    def act_packed(self, obs: torch.Tensor, epsilon: float = 0.0, seed: int = 0, step: int = 0,
+                   with_logits: bool = True, stream=None) -> torch.Tensor:
+        """Actions of device observations [rows, obs_dim] in one int32 device buffer: the
+        logits' bits [rows, A] first when with_logits, then the actions [rows] (one copy
+        brings both to the host)."""
+        rows, A = int(obs.shape[0]), self.num_actions
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
+                and obs.numel() == rows * self.obs_dim):
+            raise ValueError(f"observations must be contiguous float32 [rows, {self.obs_dim}] "
+                             "on the device")
+        n = rows * A if with_logits else 0
+        out = torch.empty(n + rows, dtype=torch.int32, device=self.device)
+        check(self._fn("act")(self._h, ptr(obs), rows, float(epsilon), int(seed) & (2 ** 64 - 1),
+                              int(step) & (2 ** 64 - 1), ptr(out) if with_logits else None,
+                              out.data_ptr() + 4 * n, stream_ptr(stream)), "bc act")
+        return out
+
+    def act(self, obs: torch.Tensor, epsilon: float = 0.0, seed: int = 0, step: int = 0,
+            stream=None):
+        """(logits [rows, A] float32, actions [rows] int32) as device tensors (views of one
+        buffer)."""
+        rows, A = int(obs.shape[0]), self.num_actions
+        out = self.act_packed(obs, epsilon, seed, step, True, stream)
+        return out[:rows * A].view(torch.float32).view(rows, A), out[rows * A:]
+
+
 class NativeMLPModel(_NativeLearner):
     """acme_mlp_model: the MCTS agent's learned transition model (three MLP towers on
     [o, onehot(a)]: next state, reward, discount logit) + its flat buffers.  `step` is one SGD

@@ -1316,6 +1316,84 @@ int acme_az_set_num_steps(acme_az* l, int64_t n);
  * pre-activation, [B, H]). */
 int acme_az_debug_buffer(const acme_az* l, const char* name, const float** out, int64_t* count);
 
+/* ------------------------------------------------------------------- BC -- */
+/* Replaces BCLearner._step (acme/agents/tf/bc/learning.py) and the evaluator network of
+ * examples/bsuite/run_bc.py.  Network: snt.Sequential([snt.Flatten(),
+ * snt.nets.MLP([*hidden, num_actions])]): ReLU between the layers, none after the last.  Flat
+ * buffer: mlp/linear_i/{w,b}, i = 0 .. num_hidden (networks.MLP.tensor_shapes()).  Loss: Keras
+ * SparseCategoricalCrossentropy(from_logits=True), default reduction:
+ * mean_b(logsumexp(z_b) - z_b[a_b]).  No target network, no gradient clipping.
+ *
+ * An action outside [0, num_actions) is never used as an index: such a row adds nothing to the
+ * loss or to any gradient, and the mean still divides by B.
+ *
+ * Limits (acme_bc_create refuses anything else, naming the field):
+ *   num_hidden in [0, ACME_MAX_MLP_LAYERS] (0: a linear model);
+ *   obs_dim and every hidden[i] in [1, ACME_BC_MAX_WIDTH] (any value);
+ *   num_actions in [1, ACME_BC_MAX_ACTIONS] (acme_epsilon_greedy's range);
+ *   max_batch in [1, ACME_BC_MAX_ROWS], max_act_rows in [1, ACME_BC_MAX_ROWS]. */
+#define ACME_BC_MAX_WIDTH 1024
+#define ACME_BC_MAX_ACTIONS 1024
+#define ACME_BC_MAX_ROWS 4096
+/* acme_bc_act runs the whole network and the selection in one launch (activations in LDS) when
+ * rows <= ACME_BC_FUSED_MAX_ROWS and obs_dim, every hidden[i] and num_actions are all
+ * <= ACME_BC_FUSED_MAX_WIDTH; otherwise one dense launch per layer and the epsilon-greedy
+ * launch. */
+#define ACME_BC_FUSED_MAX_ROWS 32
+#define ACME_BC_FUSED_MAX_WIDTH 128
+
+typedef struct acme_bc acme_bc;
+
+typedef struct acme_bc_config {
+  int32_t obs_dim;              /* flat observation size */
+  int32_t num_actions;
+  int32_t max_batch;            /* largest B of acme_bc_step */
+  int32_t max_act_rows;         /* largest rows of acme_bc_act */
+  int32_t num_hidden;
+  int32_t hidden[ACME_MAX_MLP_LAYERS];
+  float learning_rate;          /* snt.optimizers.Adam */
+  float adam_beta1, adam_beta2, adam_epsilon;
+} acme_bc_config;
+
+/* Device tensors: the demonstration's observation and action. */
+typedef struct acme_bc_batch {
+  const float* o_tm1;    /* [B, obs_dim] f32 */
+  const int32_t* a_tm1;  /* [B] int32 */
+  int64_t batch;         /* 1 <= B <= max_batch */
+} acme_bc_batch;
+
+/* Device scalars (each optional): the loss above and global_norm(grads). */
+typedef struct acme_bc_outputs {
+  float* loss;
+  float* gradient_norm;
+} acme_bc_outputs;
+
+int acme_bc_create(const acme_bc_config* cfg, acme_bc** out);
+int acme_bc_destroy(acme_bc* l);
+int64_t acme_bc_flat_size(const acme_bc* l);
+int32_t acme_bc_num_tensors(const acme_bc* l);
+int acme_bc_tensor_info(const acme_bc* l, int32_t i, int64_t* offset, int64_t* numel,
+                        int32_t* ndim, int64_t* shape4, const char** name);
+/* Flat device buffers of acme_bc_flat_size floats each (gradients and moments zeroed). */
+int acme_bc_bind(acme_bc* l, float* params, float* grads, float* adam_m, float* adam_v);
+/* One learner step on `stream`, no host synchronisation: the hidden layers forward, the output
+ * layer / loss kernel, the backward, Adam with t = num_steps + 1 (which also writes
+ * gradient_norm).  2 num_hidden + 2 launches; 3 for num_hidden = 0. */
+int acme_bc_step(acme_bc* l, const acme_bc_batch* batch, const acme_bc_outputs* out,
+                 void* stream);
+/* Actions [rows] (int32) of obs [rows, obs_dim] (device f32) under the current parameters:
+ * acme_epsilon_greedy's selection, bit for bit, on the network's logits, drawn from
+ * (seed, step_counter, row).  logits_out [rows, num_actions] is optional.  epsilon in [0, 1],
+ * 1 <= rows <= max_act_rows.  Changes no learner state. */
+int acme_bc_act(acme_bc* l, const float* obs, int64_t rows, double epsilon, uint64_t seed,
+                uint64_t step_counter, float* logits_out, int32_t* actions_out, void* stream);
+int64_t acme_bc_num_steps(const acme_bc* l);
+int acme_bc_set_num_steps(acme_bc* l, int64_t n);
+/* Internal device workspaces (tests) of the last step over B rows: "logits" [B, A],
+ * "dlogits" [B, A], "dh" (gradient at the last hidden layer's pre-activation, [B, H]; empty
+ * without a hidden layer). */
+int acme_bc_debug_buffer(const acme_bc* l, const char* name, const float** out, int64_t* count);
+
 /* ------------------------------------------------- MCTS / learned MLP model -- */
 /* The MCTS agent's learned environment model (acme/agents/tf/mcts/models/mlp.py,
  * MLPTransitionModel + MLPModel._step).  Three towers share one input
