@@ -128,7 +128,8 @@ __device__ ACME_NO_PK_F32 __forceinline__ void dense_row(const float* x, const f
     float s = part[n];
     for (int q = 1; q < G; ++q) s += part[q * NP + n];
     s += b[n];
-    y[n] = relu ? (s > 0.f ? s : 0.f) : s;
+    // NaN passes (search.check_numerics must see it in the scores); the same bits otherwise.
+    y[n] = relu ? (s <= 0.f ? 0.f : s) : s;
   }
   block_sync();
 }

@@ -7,23 +7,19 @@ Counts (root visits, every node's edge visits, nodes used, deepest path) must be
 prior, value and child values meet tests/test_az_gpu.py::_close (rtol 1e-5 + 2e-6 max|ref|).
 A float32 search may choose differently from float64 where two scores are within rounding
 (~1e-6 |score|), so each case fixes a seed for which the reference's smallest gap between the
-best and the best non-tied score is >= 1e-3 of its largest |score|, and asserts that."""
-
-import functools
+best and the best non-tied score is >= 1e-3 of its largest |score|, and asserts that.  The
+reference is tests/mcts_search_oracle.py; the kernel's edges are in
+tests/test_mcts_native_search_edges_gpu.py."""
 
 import numpy as np
 import pytest
 import torch
 
-from acme_amd import dm_env
-from acme_amd.agents.mcts import search
-from tests import _oracle, az_oracle as AO, mlp_model_oracle as MO
+from tests import az_oracle as AO
+from tests.mcts_search_oracle import _reference, _setup
 from tests.test_az_gpu import _close, _params as _az_params
-from tests.test_mlp_model_gpu import _params as _model_params
 
 pytestmark = pytest.mark.gpu
-
-TAG, M32 = 0x4D435453, 0xFFFFFFFF  # "MCTS"
 
 # (D, model hidden, net hidden, A, S, activation, discount, stream_weights, seed).  The wide
 # case's 280 KB of weights cannot be staged.  TOL = 0.5: terminal where the logit is negative.
@@ -35,91 +31,6 @@ CASES = [(1, (1,), (1,), 1, 3, "softmax", 1.0, False, 0),
          (7, (36,), (36,), 64, 8, "softmax", 0.99, False, 2),
          (64, (256,), (256, 256), 4, 12, "softmax", 0.99, False, 0)]
 TOL = 0.5
-
-
-class _Rng:
-    """search.argmax's rng: selection k of the call picks the ((r.x n) >> 32)-th maximum."""
-
-    def __init__(self, seed, call_counter):
-        self.k, self.seed, self.cc = 0, seed, call_counter
-
-    dirichlet = staticmethod(lambda alpha: np.zeros(len(alpha)))  # drawn, then multiplied by 0
-
-    def choice(self, best):
-        r = _oracle.philox([self.k, self.cc & M32, self.cc >> 32, TAG],
-                           [self.seed & M32, self.seed >> 32])
-        self.k += 1
-        return best[(int(r[0]) * len(best)) >> 32]
-
-
-class _Model:
-    """step / checkpoint / reload on the float64 model forward; counts what the test asserts."""
-    def __init__(self, cfg, params, state, sigmoid):
-        self.cfg, self.params, self.sigmoid = cfg, params, sigmoid
-        self.state, self.actions = np.asarray(state, np.float64), []
-        self.deepest, self.terminal_edges, self.revisits = 0, set(), 0
-
-    def save_checkpoint(self):
-        self.ckpt = self.state.copy()
-
-    def load_checkpoint(self):
-        self.deepest = max(self.deepest, len(self.actions))
-        self.state, self.actions = self.ckpt.copy(), []
-
-    def step(self, action):
-        s, r, x, _ = MO.forward(self.cfg, self.params, self.state[None], [action])
-        self.state = s[0]
-        self.actions.append(int(action))
-        if self.sigmoid and 1 / (1 + np.exp(-x[0])) < TOL:
-            self.revisits += tuple(self.actions) in self.terminal_edges
-            self.terminal_edges.add(tuple(self.actions))
-            return dm_env.termination(reward=r[0], observation=s[0])
-        return dm_env.transition(reward=r[0], observation=s[0])
-
-
-def _setup(D, mh, zh, A, seed, zero=False):
-    mcfg, zcfg = MO.Config(D, tuple(mh), A), AO.AZConfig(D, tuple(zh), A)
-    mp, zp = _model_params(mcfg, seed + 1), _az_params(zcfg, seed + 2)
-    if zero:
-        mp, zp = ({k: np.zeros_like(v) for k, v in p.items()} for p in (mp, zp))
-    root = np.random.default_rng(seed + 3).standard_normal(D).astype(np.float32)
-    return mcfg, zcfg, mp, zp, root
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(D, mh, zh, A, S, activation, discount, seed, call_counter=0, zero=False):
-    mcfg, zcfg, mp, zp, root_state = _setup(D, mh, zh, A, seed, zero)
-    model = _Model(mcfg, mp, root_state, activation == "sigmoid")
-    order, log = [], dict(gap=np.inf, scale=0.0)
-
-    def evaluation(obs):
-        p, v = AO.evaluate(zcfg, zp, np.asarray(obs)[None])
-        order.append(tuple(model.actions))  # nodes in order of expansion, by their action path
-        return p[0], float(v[0])
-
-    def puct(node, rng):
-        ch = list(node.children.values())
-        scores = np.array([c.value for c in ch]) + 1.0 * np.array([c.prior for c in ch]) * \
-            np.array([np.sqrt(node.visit_count) / (c.visit_count + 1) for c in ch])
-        rest = scores[scores < scores.max()]
-        if rest.size:
-            log["gap"] = min(log["gap"], scores.max() - rest.max())
-        log["scale"] = max(log["scale"], np.abs(scores).max())
-        return search.argmax(scores, rng=rng)
-
-    root = search.mcts(root_state.astype(np.float64), model, puct, evaluation, S, A, discount,
-                       rng=_Rng(seed, call_counter))
-    tree = []
-    for path in order:
-        node = root
-        for a in path:
-            node = node.children[a]
-        tree.append(node.children_visits)
-    prior, value = AO.evaluate(zcfg, zp, root_state[None].astype(np.float64))
-    return dict(visits=root.children_visits, values=root.children_values, prior=prior[0],
-                root_value=value[0], tree=np.array(tree), nodes=len(order),
-                deepest=model.deepest, gap=log["gap"], scale=log["scale"],
-                terminal_edges=len(model.terminal_edges), revisits=model.revisits)
 
 
 def _native(D, mh, zh, A, S, seed, stream=False, zero=False):
