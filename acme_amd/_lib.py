@@ -192,6 +192,18 @@ class AZOutputs(ctypes.Structure):
     _fields_ = [("loss", c_vp), ("value_loss", c_vp), ("policy_loss", c_vp)]
 
 
+EXPQ_FUSED_MAX_WIDTH = 128
+EXPQ_FUSED_MAX_ROWS = 256
+
+
+class ExpqActArgs(ctypes.Structure):  # acme_expq_act_args
+    _fields_ = [("obs", c_vp), ("rows", c_i64), ("num_samples", c_i32), ("beta", c_f32),
+                ("use_target", c_i32), ("reserved", c_i32), ("seed", c_u64), ("step", c_u64),
+                ("noise", c_vp), ("uniform", c_vp), ("action", c_vp),
+                ("sampled_actions", c_vp), ("q", c_vp), ("probs", c_vp), ("index", c_vp),
+                ("noise_out", c_vp)]
+
+
 BC_MAX_WIDTH = 1024
 BC_MAX_ACTIONS = 1024
 BC_MAX_ROWS = 4096
@@ -396,6 +408,9 @@ _SIGS = {
     "acme_az_step": (c_i32, [c_vp, ctypes.POINTER(AZBatch), ctypes.POINTER(AZOutputs), c_vp]),
     "acme_az_evaluate": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "acme_bc_step": (c_i32, [c_vp, ctypes.POINTER(BCBatch), ctypes.POINTER(BCOutputs), c_vp]),
+    "acme_mpo_act": (c_i32, [c_vp, ctypes.POINTER(ExpqActArgs), c_vp]),
+    "acme_dmpo_act": (c_i32, [c_vp, ctypes.POINTER(ExpqActArgs), c_vp]),
+    "acme_crr_act": (c_i32, [c_vp, ctypes.POINTER(ExpqActArgs), c_vp]),
     "acme_bc_act": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_u64, c_u64, c_vp, c_vp, c_vp]),
     "acme_mlp_model_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                     ctypes.POINTER(MLPModelOutputs), c_vp]),

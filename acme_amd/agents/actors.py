@@ -1,5 +1,6 @@
-"""Actors (acme/agents/tf/actors.py:35-94 FeedForwardActor, :95-172 RecurrentActor) and the
-epsilon-greedy DQN policy (trfl.epsilon_greedy used at acme/agents/tf/dqn/agent.py:118-124)."""
+"""Actors (acme/agents/tf/actors.py:35-94 FeedForwardActor, :95-172 RecurrentActor), the
+epsilon-greedy DQN policy (trfl.epsilon_greedy used at acme/agents/tf/dqn/agent.py:118-124) and
+the exponentially Q-weighted policy (acme/tf/networks/stochastic.py:49-104)."""
 
 from __future__ import annotations
 
@@ -105,3 +106,37 @@ class EpsilonGreedyPolicy:
             probs[greedy] += (1.0 - self.epsilon) / len(greedy)
             out[i] = self._rng.choice(self._A, p=probs / probs.sum())
         return out
+
+
+class ExpQWeightedPolicy:
+    """a ~ softmax(q(o, a_n) / beta) over N actions a_n sampled from the learner's policy
+    (acme/tf/networks/stochastic.py:49-104), the whole selection on the device in one native
+    call (acme_crr_act / acme_mpo_act / acme_dmpo_act).  `learner` is a CRRLearner, MPOLearner
+    or DistributionalMPOLearner; the online networks are used, as the reference's evaluator
+    does.  Callable on batched observations [rows, obs_dim]; every call advances the step
+    counter that, with `seed`, keys the generated noise.  FeedForwardActor(ExpQWeightedPolicy(
+    learner)) is an evaluation actor."""
+
+    def __init__(self, learner, beta: float = 1.0, num_action_samples: int = 16, seed: int = 0):
+        from acme_amd import _lib
+        if not beta > 0.0:
+            raise ValueError("beta must be positive")
+        if not 1 <= num_action_samples <= _lib.MPO_MAX_SAMPLES:
+            raise ValueError(f"num_action_samples must be in [1, {_lib.MPO_MAX_SAMPLES}]")
+        from acme_amd.agents.crr.learning import CRRLearner
+        from acme_amd.agents.mpo.learning import MPOLearner
+        if not isinstance(learner, (CRRLearner, MPOLearner)):
+            raise ValueError("ExpQWeightedPolicy takes a CRRLearner, MPOLearner or "
+                             f"DistributionalMPOLearner, not a {type(learner).__name__}")
+        self._native = learner._native  # noqa: SLF001
+        self.beta, self.num_action_samples = float(beta), int(num_action_samples)
+        self._seed, self._step = int(seed), 0
+
+    def __call__(self, batched_obs):
+        import torch
+        n = self._native
+        obs = torch.as_tensor(np.asarray(batched_obs, np.float32)).reshape(-1, n.obs_dim)
+        buf, views = n.act_packed(obs.to(n.device).contiguous(), self.num_action_samples,
+                                  self.beta, False, self._seed, self._step)
+        self._step += 1
+        return buf.cpu().numpy()[:views["action"].numel()].reshape(views["action"].shape)

@@ -1,2 +1,3 @@
 """CRR learner (drop-in for acme.agents.tf.crr, which exports the learner only)."""
 from acme_amd.agents.crr.learning import CRRLearner, RCRRLearner  # noqa: F401
+from acme_amd.agents.actors import ExpQWeightedPolicy  # noqa: F401

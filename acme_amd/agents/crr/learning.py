@@ -1,7 +1,9 @@
 """CRRLearner — drop-in for acme/agents/tf/crr/recurrent_learning.py:36-409 with stateless
 (feed-forward) networks.
 
-An offline learner: it trains from a fixed dataset of sequences and has no actor.  Same
+An offline learner: it trains from a fixed dataset of sequences and has no actor; to evaluate
+it in an environment, agents.actors.ExpQWeightedPolicy(learner) is the reference's acting policy
+(N sampled actions weighted by softmax(q / beta), one native call per step).  Same
 constructor arguments and `step()` contract as RCRRLearner: one call draws a batch of [B, T]
 sequences from the dataset iterator and runs the whole CRR step on the GPU (acme_crr_step: the
 online policy at o_tm1 and the target policy at o_t, two sets of sampled actions through the two

@@ -48,6 +48,11 @@
 // advantage-weighted behaviour-cloning loss and a target copy after the update.  Its kernels
 // are in crr_kernels.h, its step is crr_step_impl.
 //
+// The kinds with a Gaussian policy head (MPO, DMPO, CRR) also act: acme_*_act is the
+// exponentially Q-weighted policy (N sampled actions, their critic values, one drawn with
+// probability softmax(q / beta)) in one launch or, past its limits, layered over the step's
+// workspaces.  Its kernels are in expq_kernels.h, its body is ac_act.
+//
 // Small-batch regime (B = 256, widths <= 512): the step is ~1.5 GFLOP, so it is latency
 // bound.  Dense layers go through the fp32 MFMA GEMM engine with fused bias/activation
 // epilogues and masked dgrads; the row-wise work (LayerNorm+tanh, TanhToSpec head,
@@ -184,6 +189,11 @@ struct acme_actor_critic {
     float* coef_part;                           // [ceil(B / 4)] per-block coefficient sums
   } cb = {};
   int64_t crr_rows = 0;                   // R of the last step (the debug buffers' packing)
+  // The acting call (ac_act) of the kinds with a Gaussian policy head: the critic workspace its
+  // layered path runs through (MPO, DMPO: ctg; CRR: the larger of con and ctg) and its rows.
+  Acts* act_acts = nullptr;
+  int64_t act_cap = 0;
+  int act_variant = 0;  // the EXPQ_ACT tuning key, read at creation: 1 layered, 2 one launch at any rows
   // Captured step graphs, keyed by the batch / output pointers (MPO, DMPO, CRR: the noise
   // pointer too), B and the target-copy flags (CRR's copy is the graph's last node).
   struct Graph {
@@ -670,6 +680,7 @@ __global__ void __launch_bounds__(256) ddpg_head_td_kernel(const HeadTdArgs a) {
 
 #include "mpo_kernels.h"
 #include "crr_kernels.h"
+#include "expq_kernels.h"
 
 // ------------------------------------------------------------------ LayerNorm backward
 // Per row (kRows rows per block): dy = dLoss/d(LayerNorm output) (tanh' already
@@ -1768,6 +1779,17 @@ int init_learner(acme_actor_critic* l, const acme_d4pg_config* cfg, Head head,
         (rc = dev_alloc(l, &cb.logp, B)) || (rc = dev_alloc(l, &cb.coef_part, ceil_div(B, 4))))
       return rc;
   }
+  if (gauss) {
+    const bool use_con = crr && con_rows > ctg_rows;
+    l->act_acts = use_con ? &l->con : &l->ctg;
+    l->act_cap = use_con ? con_rows : ctg_rows;
+    l->act_variant = tune_variant("EXPQ_ACT");
+    // The one-launch acting kernel's dynamic LDS at its widest configuration, set once.
+    const int lds_bytes =
+        expq_lds(kExpqKernelMaxWidth, expq_stride(kExpqKernelMaxWidth)).total * (int)sizeof(float);
+    ACME_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(expq_act_fused_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+  }
   for (int i = 0; i < l->cri.nl; ++i)
     if ((rc = dev_alloc(l, &l->cdz[i], (int64_t)2 * B * l->cri.sizes[i]))) return rc;
   for (int i = 0; i < l->pol.nl; ++i)
@@ -2168,6 +2190,143 @@ int crr_step(acme_actor_critic* l, const acme_crr_batch* batch, const acme_crr_o
   return rc;
 }
 
+// ------------------------------------------------------------------ ExpQ acting
+// acme_mpo_act, acme_dmpo_act and acme_crr_act (kernels and the two paths: expq_kernels.h).
+
+// Whether a call of `rows` observations takes the one-launch path: a pure function of the
+// configuration and the row count.
+bool expq_fused(const acme_actor_critic* l, int64_t rows) {
+  const bool forced = l->act_variant == 2;
+  const int wmax = forced ? kExpqKernelMaxWidth : kExpqFusedMaxWidth;
+  if (l->act_variant == 1 || (rows > kExpqFusedMaxRows && !forced)) return false;
+  for (int i = 0; i < l->pol.nl; ++i)
+    if (l->pol.sizes[i] > wmax) return false;
+  for (int i = 0; i < l->cri.nl; ++i)
+    if (l->cri.sizes[i] > wmax) return false;
+  return true;
+}
+
+ExpqNet expq_net(const acme_actor_critic* l, const NetDesc& d, const float* prm) {
+  ExpqNet n;
+  n.w1 = P(l, prm, d.w1); n.b1 = P(l, prm, d.b1);
+  n.scale = P(l, prm, d.scale); n.offset = P(l, prm, d.offset);
+  for (int i = 0; i < ACME_D4PG_MAX_LAYERS; ++i) {
+    n.w[i] = i >= 1 && i < d.nl ? P(l, prm, d.w[i]) : nullptr;
+    n.b[i] = i >= 1 && i < d.nl ? P(l, prm, d.b[i]) : nullptr;
+    n.sizes[i] = i < d.nl ? d.sizes[i] : 0;
+  }
+  n.ow = P(l, prm, d.ow); n.ob = P(l, prm, d.ob);
+  n.nl = d.nl;
+  return n;
+}
+
+int ac_act(acme_actor_critic* l, const acme_expq_act_args* a, void* stream) {
+  ACME_CHECK_ARG(l && a, "null argument");
+  ACME_CHECK_ARG(has_gauss_head(l->head), "not a learner with a Gaussian policy head");
+  ACME_CHECK_ARG(l->params, "bind must be called before act");
+  ACME_CHECK_ARG(a->obs, "obs is null");
+  ACME_CHECK_ARG(a->action, "action is null");
+  ACME_CHECK_ARG(a->rows >= 0, "rows is negative");
+  ACME_CHECK_ARG(a->num_samples >= 1 && a->num_samples <= ACME_MPO_MAX_SAMPLES,
+                 "num_samples must be in [1, %d]", ACME_MPO_MAX_SAMPLES);
+  ACME_CHECK_ARG(a->beta > 0.f && std::isfinite(a->beta), "beta must be positive and finite");
+  const int od = l->cfg.obs_dim, A = l->cfg.act_dim, N = a->num_samples;
+  ACME_CHECK_ARG(a->rows * N * A < ((int64_t)1 << 31), "rows * num_samples * act_dim must be < 2^31");
+  if (a->rows == 0) return ACME_OK;
+  hipStream_t st = as_stream(stream);
+  const float* prm = a->use_target ? l->target : l->params;
+  const bool categorical = is_categorical(l->head);
+  const NetDesc& pd = l->pol;
+  const NetDesc& cd = l->cri;
+  const int cL = cd.nl - 1, K = cd.nout;
+  const uint32_t ubase = (uint32_t)ceil_div(a->rows * N * A, 4);
+  const ExpqOut out = {a->action, a->sampled_actions, a->q, a->probs, a->noise_out, a->index};
+  double flops = 2.0 * od * pd.sizes[0] + 2.0 * od * cd.sizes[0];
+  for (int i = 1; i < pd.nl; ++i) flops += 2.0 * pd.sizes[i - 1] * pd.sizes[i];
+  double cf = 2.0 * A * cd.sizes[0] + 2.0 * cd.sizes[cL] * K;
+  for (int i = 1; i < cd.nl; ++i) cf += 2.0 * cd.sizes[i - 1] * cd.sizes[i];
+  flops = (double)a->rows * (flops + N * cf);
+  if (expq_fused(l, a->rows)) {
+    ExpqFusedArgs f;
+    f.obs = a->obs; f.rows = (int)a->rows; f.od = od; f.A = A; f.N = N; f.K = K;
+    f.categorical = categorical ? 1 : 0;
+    f.pol = expq_net(l, pd, prm); f.cri = expq_net(l, cd, prm);
+    f.sw = P(l, prm, l->sw); f.sb = P(l, prm, l->sb);
+    f.values = l->values;
+    f.scale_mul = mpo_scale_mul(l); f.min_scale = l->mcfg.min_scale;
+    f.eps = l->cfg.layer_norm_epsilon; f.beta = a->beta;
+    f.seed = a->seed; f.step = a->step; f.noise = a->noise; f.uniform = a->uniform;
+    f.ubase = ubase;
+    int wmax = std::max(od, K), vw = od;
+    for (int i = 0; i < pd.nl; ++i) vw = std::max(vw, pd.sizes[i]);
+    for (int i = 0; i < cd.nl; ++i) wmax = std::max(wmax, cd.sizes[i]);
+    f.vw = (std::max(vw, cd.sizes[0]) + 3) & ~3;
+    f.ld = expq_stride(wmax);
+    f.out = out;
+    ACME_PROF("expq_act_fused", st, flops, 0.0);
+    expq_act_fused_kernel<<<(unsigned)a->rows, 256,
+                            (size_t)expq_lds(f.vw, f.ld).total * sizeof(float), st>>>(f);
+    ACME_LAUNCH_CHECK();
+    return ACME_OK;
+  }
+  // Layered: chunks of observations whose rows x N critic rows fit the step's workspaces.
+  const int per = (int)std::min<int64_t>(l->cfg.max_batch, l->act_cap / N);
+  ACME_CHECK_ARG(per >= 1,
+                 "num_samples %d exceeds the %lld critic rows this learner's workspaces hold", N,
+                 (long long)l->act_cap);
+  auto& mb = l->mb;
+  Acts& ca = *l->act_acts;
+  for (int64_t r0 = 0; r0 < a->rows; r0 += per) {
+    const int n = (int)std::min<int64_t>(per, a->rows - r0), M = n * N;
+    const float* o = a->obs + r0 * od;
+    int rc;
+    {
+      const NetIn in[2] = {{prm, o, nullptr, o, nullptr, n, n, &l->ptg},
+                           {l->params, o, nullptr, o, nullptr, n, 0, &l->ptg}};
+      if ((rc = lnmlp_forward_pair(l, pd, in, od, 0, "expq_policy_ln", st))) return rc;
+      GaussHeadPair g;
+      set_gauss_head(l, g, 0, prm, l->ptg.h[pd.nl - 1], n, l->ptg.out, nullptr, mb.sd_t);
+      g.a[1] = g.a[0];
+      gauss_head_kernel<<<dim3((unsigned)ceil_div(n, 4), 1), 256, 0, st>>>(g);
+      ACME_LAUNCH_CHECK();
+    }
+    {
+      ACME_PROF("expq_sample", st, 0.0, 4.0 * M * (3.0 * A + od));
+      ExpqSampleArgs s;
+      s.mean = l->ptg.out; s.sd = mb.sd_t; s.noise = a->noise; s.obs = o;
+      s.seed = a->seed; s.step = a->step;
+      s.r0 = (int)r0; s.n_obs = n; s.N = N; s.A = A; s.od = od;
+      s.act = mb.act; s.tiled = mb.tiled;
+      s.sampled = a->sampled_actions; s.noise_out = a->noise_out;
+      expq_sample_kernel<<<(unsigned)ceil_div((int64_t)M * od, 256), 256, 0, st>>>(s);
+      ACME_LAUNCH_CHECK();
+    }
+    {
+      const NetIn cin[2] = {{prm, mb.tiled, mb.act, mb.tiled, mb.act, M, M, &ca},
+                            {l->params, mb.tiled, mb.act, mb.tiled, mb.act, M, 0, &ca}};
+      // The scalar head is one dot per row, taken by the selection kernel.
+      rc = categorical ? critic_forward_pair(l, cin, st)
+                       : lnmlp_forward_pair(l, cd, cin, od, A, "expq_critic_ln", st);
+      if (rc != ACME_OK) return rc;
+    }
+    {
+      ACME_PROF("expq_select", st, 0.0, 4.0 * M * (double)(categorical ? K : cd.sizes[cL]));
+      ExpqSelectArgs s;
+      s.x = categorical ? ca.out : ca.h[cL];
+      s.ow = P(l, prm, cd.ow); s.ob = P(l, prm, cd.ob);
+      s.values = l->values; s.act = mb.act; s.uniform = a->uniform;
+      s.seed = a->seed; s.step = a->step; s.ubase = ubase;
+      s.r0 = (int)r0; s.n_obs = n; s.N = N; s.A = A; s.K = K; s.H = cd.sizes[cL];
+      s.categorical = categorical ? 1 : 0;
+      s.beta = a->beta;
+      s.out = out;
+      expq_select_kernel<<<(unsigned)ceil_div(n, 4), 256, 0, st>>>(s);
+      ACME_LAUNCH_CHECK();
+    }
+  }
+  return ACME_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2272,6 +2431,9 @@ int acme_mpo_step(acme_mpo* l, const acme_mpo_batch* batch, const acme_mpo_outpu
                   void* stream) {
   return mpo_step(l, Head::kMpo, batch, out, stream);
 }
+int acme_mpo_act(acme_mpo* l, const acme_expq_act_args* args, void* stream) {
+  return ac_act(l, args, stream);
+}
 int acme_mpo_policy(acme_mpo* l, const float* obs, int64_t rows, int32_t use_target,
                     float* mean_out, float* stddev_out, void* stream) {
   return mpo_policy(l, obs, rows, use_target, mean_out, stddev_out, stream);
@@ -2313,6 +2475,9 @@ int acme_dmpo_step(acme_dmpo* l, const acme_mpo_batch* batch, const acme_mpo_out
                    void* stream) {
   return mpo_step(l, Head::kMpoCategorical, batch, out, stream);
 }
+int acme_dmpo_act(acme_dmpo* l, const acme_expq_act_args* args, void* stream) {
+  return ac_act(l, args, stream);
+}
 int acme_dmpo_policy(acme_dmpo* l, const float* obs, int64_t rows, int32_t use_target,
                      float* mean_out, float* stddev_out, void* stream) {
   return mpo_policy(l, obs, rows, use_target, mean_out, stddev_out, stream);
@@ -2351,6 +2516,9 @@ int acme_crr_bind(acme_crr* l, float* params, float* target, float* grads, float
 int acme_crr_step(acme_crr* l, const acme_crr_batch* batch, const acme_crr_outputs* out,
                   void* stream) {
   return crr_step(l, batch, out, stream);
+}
+int acme_crr_act(acme_crr* l, const acme_expq_act_args* args, void* stream) {
+  return ac_act(l, args, stream);
 }
 int acme_crr_policy(acme_crr* l, const float* obs, int64_t rows, int32_t use_target,
                     float* mean_out, float* stddev_out, void* stream) {

@@ -71,6 +71,8 @@ constexpr uint32_t kFillTag = 0x46494C4Cu;    // "FILL"
 constexpr uint32_t kMpoNoiseTag = 0x4D504F4Eu;  // "MPON"
 // CRR's two action sets (d4pg.hip): the same counter layout under a tag of its own.
 constexpr uint32_t kCrrNoiseTag = 0x4352524Eu;  // "CRRN"
+// The ExpQ acting call's sampled actions and uniform draw (d4pg.hip): the same layout again.
+constexpr uint32_t kExpqNoiseTag = 0x45585051u;  // "EXPQ"
 
 ACME_HD double sample_uniform(uint64_t seed, uint64_t step, uint32_t j) {
   u32x4 c = {j, (uint32_t)step, (uint32_t)(step >> 32), kSampleTag};

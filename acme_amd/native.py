@@ -1129,6 +1129,59 @@ class NativeMPO(_NativeActorCritic):
         """The distribution's mean (the greedy action)."""
         return self.policy_distribution(obs, use_target, stream)[0]
 
+    _ACT_OUTPUTS = ("sampled_actions", "q", "probs", "index", "noise_out")
+
+    def act_packed(self, obs: torch.Tensor, num_samples: int = 16, beta: float = 1.0,
+                   use_target: bool = False, seed: int = 0, step: int = 0, noise=None,
+                   uniform=None, outputs: Sequence[str] = (), stream=None):
+        """The exponentially Q-weighted acting call (acme_*_act) on device observations
+        [rows, obs_dim]: N = num_samples actions from the policy, their critic values, one
+        drawn with probability softmax(q / beta).  Returns (buffer, views): one float32 device
+        buffer holding `action` [rows, act_dim] and then the `outputs` asked for (of
+        "sampled_actions" "noise_out" [rows, N, act_dim], "q" "probs" [rows, N], "index" [rows]
+        int32 bits), so that one copy brings everything to the host, and the dict of its
+        views.  `noise` [rows, N, act_dim] / `uniform` [rows]: device tensors (tests); None:
+        generated on the device from (seed, step)."""
+        rows, A, N = int(obs.shape[0]), self.act_dim, int(num_samples)
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
+                and obs.numel() == rows * self.obs_dim):
+            raise ValueError(f"observations must be contiguous float32 [rows, {self.obs_dim}] "
+                             "on the device")
+        for name, t, n in (("noise", noise, rows * N * A), ("uniform", uniform, rows)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda
+                                      and t.is_contiguous() and t.dtype == torch.float32
+                                      and t.numel() == n):
+                raise ValueError(f"{name} must be a contiguous float32 device tensor of {n} "
+                                 "elements")
+        shapes = {"action": (rows, A), "sampled_actions": (rows, N, A), "q": (rows, N),
+                  "probs": (rows, N), "index": (rows,), "noise_out": (rows, N, A)}
+        names = ["action"] + [k for k in self._ACT_OUTPUTS if k in outputs]
+        if len(names) != 1 + len(set(outputs)):
+            raise ValueError(f"outputs must be among {self._ACT_OUTPUTS}")
+        sizes = [int(np.prod(shapes[k])) for k in names]
+        buf = torch.empty(max(sum(sizes), 1), dtype=torch.float32, device=self.device)
+        a = _lib.ExpqActArgs()
+        a.obs, a.rows, a.num_samples, a.beta = ptr(obs), rows, N, float(beta)
+        a.use_target = 1 if use_target else 0
+        a.seed, a.step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        a.noise = ptr(noise) if noise is not None else None
+        a.uniform = ptr(uniform) if uniform is not None else None
+        views, off = {}, 0
+        for k, n in zip(names, sizes):
+            v = buf[off:off + n]
+            setattr(a, k, buf.data_ptr() + 4 * off if n else None)
+            views[k] = (v.view(torch.int32) if k == "index" else v).view(shapes[k])
+            off += n
+        check(self._fn("act")(self._h, ctypes.byref(a), stream_ptr(stream)), f"{self._tag} act")
+        return buf, views
+
+    def act(self, obs: torch.Tensor, num_samples: int = 16, beta: float = 1.0,
+            use_target: bool = False, seed: int = 0, step: int = 0, noise=None, uniform=None,
+            outputs: Sequence[str] = (), stream=None) -> Dict[str, torch.Tensor]:
+        """As act_packed, returning the dict of device tensors: "action" and the `outputs`."""
+        return self.act_packed(obs, num_samples, beta, use_target, seed, step, noise, uniform,
+                               outputs, stream)[1]
+
 
 class NativeDMPO(NativeMPO):
     """acme_dmpo learner: NativeMPO's policy side, duals, step and stats with D4PG's categorical
@@ -1243,6 +1296,9 @@ class NativeCRR(_NativeActorCritic):
 
     policy_distribution = NativeMPO.policy_distribution
     policy = NativeMPO.policy
+    _ACT_OUTPUTS = NativeMPO._ACT_OUTPUTS
+    act_packed = NativeMPO.act_packed
+    act = NativeMPO.act
 
 
 class NativeAZ(_NativeLearner):

@@ -1014,6 +1014,59 @@ int acme_crr_set_num_steps(acme_crr* l, int64_t n);
 int acme_crr_debug_buffer(const acme_crr* l, const char* name, const float** out,
                           int64_t* count);
 
+/* ------------------------------------------------------------ ExpQ acting -- */
+/* The exponentially Q-weighted acting policy (acme/tf/networks/stochastic.py:49-104) of the
+ * learners with a Gaussian policy head: acme_mpo_act, acme_dmpo_act, acme_crr_act.  For every
+ * observation row, in this order:
+ *   (mean, stddev) = the policy at o (acme_*_policy's);
+ *   a_n = mean + stddev eps_n, n < N, not clipped;
+ *   q_n = the critic at (o, a_n): the mean of softmax(logits) over the support for the
+ *     categorical head (DMPO, CRR), the output itself for the scalar head (MPO);
+ *   p = softmax(q / beta) over the N samples;
+ *   index = the number of entries of the running sum of p (in sample order) that are <= u, for
+ *     one uniform u in [0, 1), clamped to N - 1;
+ *   action = a_index.
+ * Noise: eps [rows, N, act_dim], element e = (row N + n) act_dim + d.  With `noise` null it is
+ * generated as MPO's (above) under the counter tag 0x45585051 with `step` the caller's counter
+ * and key = `seed`; with `uniform` null, row's u is (x >> 8) 2^-24 of one more Philox call
+ * under the same tag at counter index ceil(rows N act_dim / 4) + row.
+ *
+ * One launch (a workgroup per observation, everything in LDS, the critic's hidden layers as
+ * 16-row MFMA tiles) when every policy and critic layer size is <= ACME_EXPQ_FUSED_MAX_WIDTH and
+ * rows <= ACME_EXPQ_FUSED_MAX_ROWS; otherwise the policy forward, a sampling launch, the critic
+ * over the rows x N rows and a selection launch, in chunks of the step's workspaces (this
+ * path needs N <= the critic rows the learner was created for: max_batch num_samples for MPO and
+ * DMPO, max_batch max(N_td, 1 + N_pw) for CRR).  Both paths give the same index.  A call repeats
+ * bit for bit. */
+#define ACME_EXPQ_FUSED_MAX_WIDTH 128
+#define ACME_EXPQ_FUSED_MAX_ROWS 256
+
+typedef struct acme_expq_act_args {
+  const float* obs;        /* [rows, obs_dim] */
+  int64_t rows;
+  int32_t num_samples;     /* N in [1, ACME_MPO_MAX_SAMPLES] */
+  float beta;              /* > 0 */
+  int32_t use_target;      /* 0: the online networks (the reference's evaluator) */
+  int32_t reserved;
+  uint64_t seed, step;     /* key and counter of the generated noise and uniform */
+  const float* noise;      /* [rows, N, act_dim] or null */
+  const float* uniform;    /* [rows] in [0, 1), or null */
+  float* action;           /* [rows, act_dim] */
+  float* sampled_actions;  /* [rows, N, act_dim], optional (this and the following) */
+  float* q;                /* [rows, N] */
+  float* probs;            /* [rows, N] */
+  int32_t* index;          /* [rows] */
+  float* noise_out;        /* [rows, N, act_dim]: the eps used */
+} acme_expq_act_args;
+
+/* The three exports share their signature; a bad argument returns ACME_ERR_INVALID, names the
+ * field in acme_last_error and launches nothing. */
+#define ACME_DECLARE_EXPQ_ACT(kind) \
+  int acme_##kind##_act(acme_##kind* l, const acme_expq_act_args* args, void* stream)
+ACME_DECLARE_EXPQ_ACT(mpo);
+ACME_DECLARE_EXPQ_ACT(dmpo);
+ACME_DECLARE_EXPQ_ACT(crr);
+
 /* ---------------------------------------------------------------- IMPALA -- */
 /* Replaces IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with
  * IMPALAAtariNetwork (acme/tf/networks/atari.py:115-144): OAREmbedding(AtariTorso) ->
