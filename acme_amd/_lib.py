@@ -235,6 +235,23 @@ class IMPALAConfig(ctypes.Structure):
                 ("adam_beta2", c_f32), ("adam_epsilon", c_f32), ("semantics", c_i32)]
 
 
+IMPALA_MLP_MAX_WIDTH = 256
+IMPALA_MLP_MAX_HIDDEN = 3
+IMPALA_MLP_MAX_LSTM = 128
+IMPALA_MLP_MAX_ACTIONS = 64
+IMPALA_MLP_MAX_ROWS = 1024
+IMPALA_MLP_MAX_T = 128
+
+
+class IMPALAMLPConfig(ctypes.Structure):  # acme_impala_mlp_config
+    _fields_ = [("obs_dim", c_i32), ("num_actions", c_i32), ("max_batch", c_i32),
+                ("max_sequence_length", c_i32), ("lstm_size", c_i32), ("num_hidden", c_i32),
+                ("hidden", c_i32 * IMPALA_MLP_MAX_HIDDEN), ("discount", c_f32),
+                ("entropy_cost", c_f32), ("baseline_cost", c_f32), ("max_abs_reward", c_f32),
+                ("max_gradient_norm", c_f32), ("learning_rate", c_f32), ("adam_beta1", c_f32),
+                ("adam_beta2", c_f32), ("adam_epsilon", c_f32)]
+
+
 class R2D2Config(ctypes.Structure):
     _fields_ = [("torso", c_i32), ("obs_dim", c_i32), ("num_actions", c_i32),
                 ("max_batch", c_i32), ("max_sequence_length", c_i32), ("burn_in_length", c_i32),
@@ -401,6 +418,9 @@ _SIGS = {
     "acme_impala_policy_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),
     "acme_impala_set_policy_planes": (c_i32, [c_vp, c_i32]),
+    "acme_impala_mlp_step": (c_i32, [c_vp, ctypes.POINTER(SequenceBatch), c_vp, c_vp]),
+    "acme_impala_mlp_policy_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
     "acme_mpo_dual_offset": (c_i64, [c_vp]),
     "acme_mpo_init_duals": (c_i32, [c_vp]),
     "acme_dmpo_dual_offset": (c_i64, [c_vp]),
@@ -486,7 +506,8 @@ for _learner in (
         dict(prefix="crr", config=CRRConfig, bind=5, actor_critic=(MPOBatch, CRROutputs, 2)),
         dict(prefix="az", config=AZConfig, bind=4),  # no target
         dict(prefix="bc", config=BCConfig, bind=4),  # no target
-        dict(prefix="mlp_model", config=MLPModelConfig, bind=4)):  # no target
+        dict(prefix="mlp_model", config=MLPModelConfig, bind=4),  # no target
+        dict(prefix="impala_mlp", config=IMPALAMLPConfig, bind=4)):  # no target
     _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

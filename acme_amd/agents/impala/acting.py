@@ -29,9 +29,13 @@ class IMPALAActor(core.Actor):
         if self._state is None:
             self._state = self._initial_state(1)
         obs = observation
-        logits, _, h, c = self._policy_step(np.asarray(obs.observation)[None],
-                                            np.asarray(obs.action).reshape(1),
-                                            np.asarray(obs.reward).reshape(1),
+        if hasattr(obs, "observation"):  # an OAR
+            frame, prev_a, prev_r = obs.observation, obs.action, obs.reward
+        else:  # the raw observation: the network takes no previous action or reward
+            frame, prev_a, prev_r = obs, np.int32(0), np.float32(0)
+        logits, _, h, c = self._policy_step(np.asarray(frame)[None],
+                                            np.asarray(prev_a).reshape(1),
+                                            np.asarray(prev_r).reshape(1),
                                             self._state.hidden, self._state.cell)
         self._prev_logits = logits[0]
         self._prev_state = LSTMState(self._state.hidden[0].copy(), self._state.cell[0].copy())

@@ -12,6 +12,10 @@ A step whose f16 planes overflowed, or whose one-launch LSTM unroll timed out, a
 update (the device's step guard, as DQNLearner's): the learner sees the count lazily, logs
 `skipped_steps` and recalibrates the plane scales before its next step (or raises
 FloatingPointError with on_plane_overflow="raise").
+
+With an IMPALAMLPNetwork (examples/bsuite/run_impala.py's MLP -> LSTM -> heads on raw vector
+observations) the step is acme_impala_mlp_step: three launches, exact f32, no planes and no
+step guard; data.observation is the [B, T, ...] float observation itself.
 """
 
 from __future__ import annotations
@@ -23,7 +27,8 @@ import numpy as np
 import torch
 
 from acme_amd.agents import _learner
-from acme_amd.native import NativeIMPALA
+from acme_amd.native import NativeIMPALA, NativeIMPALAMLP
+from acme_amd.networks import IMPALAMLPNetwork
 from acme_amd.utils import counting, loggers
 
 
@@ -39,6 +44,11 @@ def _actor_networks(learner: "IMPALALearner", rows: int) -> List[NativeIMPALA]:
     (actor_policy, pipelined_policy)."""
     n = learner.native
     learner._ensure_snapshots()  # noqa: SLF001
+    if isinstance(n, NativeIMPALAMLP):
+        return [NativeIMPALAMLP(obs_dim=n.obs_dim, hidden=n.hidden, lstm_size=n.lstm_size,
+                                num_actions=n.num_actions, max_batch=rows, max_sequence_length=2,
+                                device=n.device, shared_params=buf)
+                for buf in learner._snap_buf]  # noqa: SLF001
     nets = [NativeIMPALA(num_actions=n.num_actions, max_batch=rows, max_sequence_length=2,
                          torso=n.torso, obs_dim=n.obs_dim, lstm_size=n.lstm_size,
                          head_size=learner._network.head_size,  # noqa: SLF001
@@ -70,14 +80,22 @@ class IMPALALearner(_learner.PlaneLearner):
         self._iterator = iter(dataset)
         B = batch_size or getattr(dataset, "batch_size", None) or 16
         T = sequence_length or getattr(dataset, "sequence_length", None) or 20
-        self._native = NativeIMPALA(
+        common = dict(
             num_actions=network.num_actions, max_batch=B, max_sequence_length=T,
-            torso=network.torso, obs_dim=network.obs_dim, lstm_size=network.lstm_size,
-            head_size=network.head_size, discount=discount, entropy_cost=entropy_cost,
-            baseline_cost=baseline_cost, max_abs_reward=max_abs_reward,
-            max_gradient_norm=max_gradient_norm, learning_rate=learning_rate, semantics=semantics,
+            obs_dim=network.obs_dim, lstm_size=network.lstm_size, discount=discount,
+            entropy_cost=entropy_cost, baseline_cost=baseline_cost, max_abs_reward=max_abs_reward,
+            max_gradient_norm=max_gradient_norm, learning_rate=learning_rate,
             device=device, **({} if adam is None else dict(
                 adam_beta1=adam.beta1, adam_beta2=adam.beta2, adam_epsilon=adam.epsilon)))
+        # The native learner by network type; the MLP network's has no planes and no guard.
+        self._mlp = isinstance(network, IMPALAMLPNetwork)
+        if self._mlp:
+            if semantics != "tf":
+                raise ValueError("IMPALAMLPNetwork runs the 'tf' semantics only")
+            self._native = NativeIMPALAMLP(hidden=network.hidden, **common)
+        else:
+            self._native = NativeIMPALA(torso=network.torso, head_size=network.head_size,
+                                        semantics=semantics, **common)
         self._native.set_params(network.init(seed))
         self._init_bookkeeping(counter, logger)
         m = self._native.metrics
@@ -87,6 +105,8 @@ class IMPALALearner(_learner.PlaneLearner):
         self._snap = None
 
     def step(self):
+        if self._mlp:
+            return self._step_mlp()
         skipped = self._check_guard()
         data = next(self._iterator).data
         _learner.check_oar(data.observation, "IMPALAAtariNetwork")
@@ -97,9 +117,37 @@ class IMPALALearner(_learner.PlaneLearner):
             self._publish_snapshot()
         self._finish_step(dict(self._metric_views), skipped)
 
+    def _step_mlp(self):
+        data = next(self._iterator).data
+        obs = data.observation
+        if hasattr(obs, "observation"):
+            raise ValueError("IMPALAMLPNetwork takes the raw observation, not an OAR "
+                             "(leave the environment unwrapped)")
+        B, T = int(data.action.shape[0]), int(data.action.shape[1])
+        c = lambda x, t: x.reshape(B, T).to(t).contiguous()  # noqa: E731
+        self._native.step(obs.reshape(B, T, -1).to(torch.float32).contiguous(),
+                          c(data.action, torch.int32), c(data.reward, torch.float32),
+                          c(data.discount, torch.float32),
+                          data.extras["logits"].to(torch.float32).contiguous(),
+                          *_learner.initial_core_state(data.extras))
+        if self._snap is not None:
+            self._publish_snapshot()
+        self._finish_step(dict(self._metric_views))
+
+    def _policy_args(self, convert, observation, prev_action, prev_reward, hidden, cell):
+        """The device inputs of the native policy step: the MLP network ignores the previous
+        action and reward."""
+        args = _learner.acting_inputs(convert, self._obs_dtype, observation, prev_action,
+                                      prev_reward, hidden, cell)
+        return (args[0],) + args[3:] if self._mlp else args
+
     def policy_step(self, observation, prev_action, prev_reward, hidden, cell):
         """Batched network step for actors (numpy in, numpy out)."""
         n = self._native
+        if self._mlp:
+            out = n.policy_step(*self._policy_args(_learner.to_device(n.device), observation,
+                                                   prev_action, prev_reward, hidden, cell))
+            return tuple(x.cpu().numpy() for x in out)
         out = n.policy_step(*_learner.acting_inputs(
             _learner.to_device(n.device), self._obs_dtype, observation, prev_action, prev_reward,
             hidden, cell))
@@ -151,9 +199,9 @@ class IMPALALearner(_learner.PlaneLearner):
                 j = self._snap
                 stream.wait_event(self._snap_ready[j])
             with torch.cuda.stream(stream):
-                out = nets[j].policy_step(*_learner.acting_inputs(
-                    convert, self._obs_dtype, observation, prev_action, prev_reward, hidden,
-                    cell), stream=stream)
+                out = nets[j].policy_step(*self._policy_args(
+                    convert, observation, prev_action, prev_reward, hidden, cell),
+                    stream=stream)
                 done = torch.cuda.Event()
                 done.record(stream)
                 with self._snap_lock:
@@ -170,13 +218,31 @@ class IMPALALearner(_learner.PlaneLearner):
         (ProcessActorPool): issue(obs, prev_a, prev_r, h, c) stages the numpy inputs in pinned
         memory and issues the copies, the network step and the copies back on this policy's
         own stream without waiting; result() waits for them and returns (logits, v, h, c)."""
+        if self._mlp:
+            raise ValueError("pipelined_policy packs OAR inputs: use actor_policy with an "
+                             "IMPALAMLPNetwork")
         return _PipelinedPolicy(self, int(max_rows))
 
     def get_variables(self, names: List[str]) -> List[Dict[str, np.ndarray]]:
         return [self._native.get_params("params")]
 
+    def save(self) -> Dict:
+        if not self._mlp:
+            return super().save()
+        n = self._native
+        return {"network": n.get_params("params"),
+                "optimizer": {"m": n.get_params("m"), "v": n.get_params("v"),
+                              "step": n.num_steps},
+                "num_steps": n.num_steps}
+
     def restore(self, state: Dict):
-        super().restore(state)
+        if self._mlp:
+            n = self._native
+            n.set_params(state["network"])
+            self._restore_moments(state["optimizer"])
+            n.num_steps = int(state["num_steps"])
+        else:
+            super().restore(state)
         if self._snap is not None:  # actors act with the restored weights from now on
             self._publish_snapshot()
 

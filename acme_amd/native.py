@@ -1664,6 +1664,72 @@ class NativeIMPALA(_PlaneOverflow, _PlaneState, _NativeLearner):
         return tuple(out)
 
 
+class NativeIMPALAMLP(_NativeLearner):
+    """acme_impala_mlp learner (networks.IMPALAMLPNetwork: MLP -> LSTM -> two heads on raw float
+    observations) + its flat buffers: the whole step in three launches, the policy step in
+    one.  Exact f32: no planes, no step guard."""
+
+    _prefix, _tag, _has_target = "acme_impala_mlp", "impala_mlp", False
+    torso = "mlp"
+
+    def __init__(self, *, obs_dim: int, hidden: Sequence[int], lstm_size: int, num_actions: int,
+                 max_batch: int, max_sequence_length: int, discount: float = 0.99,
+                 entropy_cost: float = 0.0, baseline_cost: float = 1.0,
+                 max_abs_reward: Optional[float] = None,
+                 max_gradient_norm: Optional[float] = None, learning_rate: float = 1e-3,
+                 adam_beta1: float = 0.9, adam_beta2: float = 0.999, adam_epsilon: float = 1e-8,
+                 device=None, shared_params: Optional[torch.Tensor] = None):
+        _lib.require_gpu()
+        if len(hidden) > _lib.IMPALA_MLP_MAX_HIDDEN:
+            raise ValueError(f"hidden takes at most {_lib.IMPALA_MLP_MAX_HIDDEN} layer sizes")
+        cfg = _lib.IMPALAMLPConfig()
+        cfg.obs_dim, cfg.num_actions = int(obs_dim), int(num_actions)
+        cfg.max_batch, cfg.max_sequence_length = int(max_batch), int(max_sequence_length)
+        cfg.lstm_size, cfg.num_hidden = int(lstm_size), len(hidden)
+        for i, s in enumerate(hidden):
+            cfg.hidden[i] = int(s)
+        cfg.discount, cfg.entropy_cost, cfg.baseline_cost = discount, entropy_cost, baseline_cost
+        # learning.py:67-71: None -> no reward clipping, gradient norm 1e10.
+        cfg.max_abs_reward = float("inf") if max_abs_reward is None else max_abs_reward
+        cfg.max_gradient_norm = 1e10 if max_gradient_norm is None else max_gradient_norm
+        cfg.learning_rate = learning_rate
+        cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
+        self.obs_dim, self.hidden = int(obs_dim), tuple(int(h) for h in hidden)
+        self.num_actions, self.lstm_size = int(num_actions), int(lstm_size)
+        self.max_batch, self.max_sequence_length = int(max_batch), int(max_sequence_length)
+        self._create(cfg, device, shared_params)
+        self.metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def step(self, observation, action, reward, discount, behaviour_logits, h0, c0, stream=None):
+        """Batch-major device tensors: observation float32 [B, T, obs_dim], the rest [B, T]
+        (behaviour_logits [B, T, A]); h0 / c0 are [B, H] views with unit inner stride."""
+        # The network has no previous action or reward: the checked [B, T] stand-ins are the
+        # action and reward themselves, and the struct's two pointers are cleared below.
+        b = self._sequence_batch(observation, action, reward, action, reward, discount, h0, c0,
+                                 behaviour_logits=behaviour_logits)
+        if observation.numel() != b.batch * b.sequence_length * self.obs_dim:
+            raise ValueError(f"observation has shape {tuple(observation.shape)}, expected "
+                             f"[{b.batch}, {b.sequence_length}, {self.obs_dim}]")
+        b.prev_action = b.prev_reward = None  # not inputs of this network
+        check(lib().acme_impala_mlp_step(self._h, ctypes.byref(b), ptr(self.metrics),
+                                         stream_ptr(stream)), "impala_mlp step")
+
+    def policy_step(self, obs, h, c, stream=None, out=None):
+        """One network step for `rows` actors: obs [rows, obs_dim], h / c [rows, H] float32
+        device tensors; returns (logits, values, h, c) (into `out` when given)."""
+        rows = int(h.shape[0])
+        for name, t, n in (("obs", obs, rows * self.obs_dim), ("h", h, rows * self.lstm_size),
+                           ("c", c, rows * self.lstm_size)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == n):
+                raise ValueError(f"{name} must be a float32 device tensor of {n} elements")
+        if out is None:
+            out = self._acting_outputs(rows, torch.float32)
+        check(lib().acme_impala_mlp_policy_step(
+            self._h, ptr(obs.contiguous()), ptr(h.contiguous()), ptr(c.contiguous()), rows,
+            *[ptr(o) for o in out], stream_ptr(stream)), "impala_mlp policy_step")
+        return tuple(out)
+
+
 class NativeR2D2(_PlaneState, _NativeLearner):
     """acme_r2d2 learner + its flat buffers (params, target, grads, Adam m / v):
     R2D2Learner._step (acme/agents/tf/r2d2/learning.py:112-200) on R2D2AtariNetwork."""

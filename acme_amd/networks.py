@@ -558,6 +558,57 @@ class IMPALAAtariNetwork:
         return LSTMState(z, z.copy())
 
 
+# ------------------------------------------------------------------ IMPALA (vector observations)
+
+
+@dataclasses.dataclass(frozen=True)
+class IMPALAMLPNetwork:
+    """snt.DeepRNN([snt.Flatten(), snt.nets.MLP(hidden), snt.LSTM(lstm_size),
+    PolicyValueHead(num_actions)]) (examples/bsuite/run_impala.py:46-52) on raw float
+    observations: ReLU between the MLP's layers and none after the last, the LSTM on the MLP's
+    output, two linear heads on h (logits [A] and a value).  No OAR embedding: the previous
+    action and reward are not inputs."""
+
+    obs_dim: int
+    hidden: Tuple[int, ...]
+    lstm_size: int
+    num_actions: int
+    obs_dtype: str = dataclasses.field(default="float32", init=False)
+    torso: str = dataclasses.field(default="mlp", init=False)
+
+    def __init__(self, obs_dim: int, hidden: Sequence[int] = (50, 50), lstm_size: int = 20,
+                 num_actions: int = 0):
+        object.__setattr__(self, "obs_dim", int(obs_dim))
+        object.__setattr__(self, "hidden", tuple(int(h) for h in hidden))
+        object.__setattr__(self, "lstm_size", int(lstm_size))
+        object.__setattr__(self, "num_actions", int(num_actions))
+        object.__setattr__(self, "obs_dtype", "float32")
+        object.__setattr__(self, "torso", "mlp")
+        if not self.hidden:
+            raise ValueError("IMPALAMLPNetwork needs at least one MLP layer")
+        if self.num_actions < 1:
+            raise ValueError("IMPALAMLPNetwork needs num_actions >= 1")
+
+    def tensor_shapes(self):
+        out, d, H = [], self.obs_dim, self.lstm_size
+        for i, h in enumerate(self.hidden):
+            out += [(f"mlp/linear_{i}/w", (d, h)), (f"mlp/linear_{i}/b", (h,))]
+            d = h
+        out += [("lstm/w_i", (d, 4 * H)), ("lstm/w_h", (H, 4 * H)), ("lstm/b", (4 * H,)),
+                ("policy_value_network/linear/w", (H, self.num_actions)),
+                ("policy_value_network/linear/b", (self.num_actions,)),
+                ("policy_value_network/linear_1/w", (H, 1)),
+                ("policy_value_network/linear_1/b", (1,))]
+        return out
+
+    @property
+    def obs_shape(self) -> Tuple[int, ...]:
+        return (self.obs_dim,)
+
+    init = IMPALAAtariNetwork.init
+    initial_state = IMPALAAtariNetwork.initial_state
+
+
 # ------------------------------------------------------------------ R2D2 (Atari)
 
 

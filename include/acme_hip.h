@@ -1165,6 +1165,81 @@ int acme_impala_set_num_steps(acme_impala* l, int64_t n);
 int acme_impala_debug_buffer(const acme_impala* l, const char* name, const float** out,
                              int64_t* count);
 
+/* ---------------------------------------------------- IMPALA / MLP + LSTM -- */
+/* IMPALALearner._step (acme/agents/tf/impala/learning.py:97-169) with the network of
+ * examples/bsuite/run_impala.py: snt.DeepRNN([snt.Flatten(), snt.nets.MLP(hidden),
+ * snt.LSTM(lstm_size), PolicyValueHead(num_actions)]) on raw float observations (no OAR
+ * embedding, no layer between the LSTM and the heads).  Flat buffer: mlp/linear_i/{w,b},
+ * lstm/{w_i,w_h,b} (gates i, f, g, o; the forget bias folded into b, as acme_impala's),
+ * policy_value_network/linear/{w,b} (logits) and policy_value_network/linear_1/{w,b} (value).
+ * Everything is f32: no planes, no step guard.
+ *
+ * Limits (acme_impala_mlp_create refuses anything else, naming the field; they keep a tile of
+ * 16 sequences in LDS, so one fused path serves every accepted shape):
+ *   obs_dim and every hidden[i] in [1, ACME_IMPALA_MLP_MAX_WIDTH] (any value);
+ *   num_hidden in [1, ACME_IMPALA_MLP_MAX_HIDDEN];
+ *   lstm_size in [1, ACME_IMPALA_MLP_MAX_LSTM] (any value);
+ *   num_actions in [1, ACME_IMPALA_MLP_MAX_ACTIONS];
+ *   max_batch in [1, ACME_IMPALA_MLP_MAX_ROWS];
+ *   max_sequence_length in [2, ACME_IMPALA_MLP_MAX_T]. */
+#define ACME_IMPALA_MLP_MAX_WIDTH 256
+#define ACME_IMPALA_MLP_MAX_HIDDEN 3
+#define ACME_IMPALA_MLP_MAX_LSTM 128
+#define ACME_IMPALA_MLP_MAX_ACTIONS 64
+#define ACME_IMPALA_MLP_MAX_ROWS 1024
+#define ACME_IMPALA_MLP_MAX_T 128
+
+typedef struct acme_impala_mlp acme_impala_mlp;
+
+typedef struct acme_impala_mlp_config {
+  int32_t obs_dim;
+  int32_t num_actions;
+  int32_t max_batch;            /* sequences per step (B), and rows of a policy step */
+  int32_t max_sequence_length;  /* T */
+  int32_t lstm_size;
+  int32_t num_hidden;
+  int32_t hidden[ACME_IMPALA_MLP_MAX_HIDDEN];
+  float discount, entropy_cost, baseline_cost;
+  float max_abs_reward;         /* INFINITY = no reward clipping */
+  float max_gradient_norm;      /* 1e10 = effectively none */
+  float learning_rate, adam_beta1, adam_beta2, adam_epsilon;
+} acme_impala_mlp_config;
+
+int acme_impala_mlp_create(const acme_impala_mlp_config* cfg, acme_impala_mlp** out);
+int acme_impala_mlp_destroy(acme_impala_mlp* l);
+int64_t acme_impala_mlp_flat_size(const acme_impala_mlp* l);
+int32_t acme_impala_mlp_num_tensors(const acme_impala_mlp* l);
+int acme_impala_mlp_tensor_info(const acme_impala_mlp* l, int32_t i, int64_t* offset,
+                                int64_t* numel, int32_t* ndim, int64_t* shape4,
+                                const char** name);
+/* Flat device buffers of acme_impala_mlp_flat_size floats each (gradients and moments zeroed). */
+int acme_impala_mlp_bind(acme_impala_mlp* l, float* params, float* grads, float* adam_m,
+                         float* adam_v);
+/* One SGD step in three launches on `stream`, whatever T and the depth, no host
+ * synchronisation.  batch->observation is f32 [B, T, obs_dim]; prev_action and prev_reward are
+ * not read (may be NULL).  Launch 1: one workgroup per 16 sequences unrolls the network over T,
+ * computes V-trace (both clip thresholds 1), the losses' gradients with the divisor (T - 1) B
+ * and the backward through time.  Launch 2: every weight and bias gradient over the B T rows
+ * in a fixed order.  Launch 3: clip_by_global_norm(max_gradient_norm), snt.Adam at
+ * t = num_steps + 1 and metrics (device, optional) = [loss, critic_loss, entropy_loss,
+ * policy_gradient_loss].  No float atomics: the same step from the same state gives the same
+ * bits. */
+int acme_impala_mlp_step(acme_impala_mlp* l, const acme_sequence_batch* batch, float* metrics,
+                         void* stream);
+/* One network step for `rows` independent actors in one launch: obs [rows, obs_dim], state
+ * h / c [rows, lstm_size]; outputs (each optional) logits [rows, A], values [rows], next
+ * state h_out / c_out.  1 <= rows <= max_batch.  Changes no learner state. */
+int acme_impala_mlp_policy_step(acme_impala_mlp* l, const float* obs, const float* h,
+                                const float* c, int64_t rows, float* logits, float* values,
+                                float* h_out, float* c_out, void* stream);
+int64_t acme_impala_mlp_num_steps(const acme_impala_mlp* l);
+int acme_impala_mlp_set_num_steps(acme_impala_mlp* l, int64_t n);
+/* Internal device workspaces (tests) of the last step over B sequences of T: "pv" and "dpv"
+ * [B*T, A + 1] batch-major rows (logits, then the value), "vs" and "pg_adv" [(T-1)*B]
+ * time-major, "h" [B*T, H], "grad_norm" [1]. */
+int acme_impala_mlp_debug_buffer(const acme_impala_mlp* l, const char* name, const float** out,
+                                 int64_t* count);
+
 /* ------------------------------------------------------------------ R2D2 -- */
 /* Replaces R2D2Learner._step (acme/agents/tf/r2d2/learning.py:112-200) with
  * R2D2AtariNetwork (acme/tf/networks/atari.py:72-112): OAREmbedding(AtariTorso, or the
