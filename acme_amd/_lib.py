@@ -264,6 +264,26 @@ class R2D2Config(ctypes.Structure):
                 ("adam_epsilon", c_f32)]
 
 
+R2D2_MLP_MAX_WIDTH = 256
+R2D2_MLP_MAX_HIDDEN = 3
+R2D2_MLP_MAX_LSTM = 128
+R2D2_MLP_MAX_ACTIONS = 64
+R2D2_MLP_MAX_ROWS = 1024
+R2D2_MLP_MAX_T = 128
+
+
+class R2D2MLPConfig(ctypes.Structure):  # acme_r2d2_mlp_config
+    _fields_ = [("obs_dim", c_i32), ("num_actions", c_i32), ("max_batch", c_i32),
+                ("max_sequence_length", c_i32), ("burn_in_length", c_i32), ("lstm_size", c_i32),
+                ("num_hidden", c_i32), ("hidden", c_i32 * R2D2_MLP_MAX_HIDDEN),
+                ("n_step", c_i32), ("store_lstm_state", c_i32), ("target_update_period", c_i32),
+                ("reserved", c_i32), ("max_replay_size", c_i64),
+                ("max_priority_weight", ctypes.c_double),
+                ("importance_sampling_exponent", ctypes.c_double), ("discount", c_f32),
+                ("learning_rate", c_f32), ("adam_beta1", c_f32), ("adam_beta2", c_f32),
+                ("adam_epsilon", c_f32)]
+
+
 class R2D2Outputs(ctypes.Structure):
     _fields_ = [("loss", c_vp), ("errors", c_vp), ("priorities", c_vp)]
 
@@ -421,6 +441,10 @@ _SIGS = {
     "acme_impala_mlp_step": (c_i32, [c_vp, ctypes.POINTER(SequenceBatch), c_vp, c_vp]),
     "acme_impala_mlp_policy_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                             c_vp]),
+    "acme_r2d2_mlp_step": (c_i32, [c_vp, ctypes.POINTER(SequenceBatch), c_vp,
+                                   ctypes.POINTER(R2D2Outputs), c_vp]),
+    "acme_r2d2_mlp_q_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f64, c_u64,
+                                     c_u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "acme_mpo_dual_offset": (c_i64, [c_vp]),
     "acme_mpo_init_duals": (c_i32, [c_vp]),
     "acme_dmpo_dual_offset": (c_i64, [c_vp]),
@@ -507,7 +531,8 @@ for _learner in (
         dict(prefix="az", config=AZConfig, bind=4),  # no target
         dict(prefix="bc", config=BCConfig, bind=4),  # no target
         dict(prefix="mlp_model", config=MLPModelConfig, bind=4),  # no target
-        dict(prefix="impala_mlp", config=IMPALAMLPConfig, bind=4)):  # no target
+        dict(prefix="impala_mlp", config=IMPALAMLPConfig, bind=4),  # no target
+        dict(prefix="r2d2_mlp", config=R2D2MLPConfig, bind=5)):
     _SIGS.update(_learner_sigs(**_learner))
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -14,19 +14,30 @@ replay (learning.py:192-199).  Nothing synchronises the host with the device.
 
 `network` / `target_network` are acme_amd.networks.R2D2AtariNetwork descriptors (the
 reference takes Sonnet RNN cores); the target starts from its own initialisation.
+
+With an R2D2MLPNetwork (the reference's own R2D2 test network: LSTM -> MLP on raw vector
+observations) the step is acme_r2d2_mlp_step: three launches, exact f32, no planes, no step
+guard and no skip word; data.observation is the [B, T, ...] float observation itself.
 """
 
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from acme_amd.adders import reverb as adders
 from acme_amd.agents import _learner
-from acme_amd.native import NativeR2D2
+from acme_amd.native import NativeR2D2, NativeR2D2MLP
+from acme_amd.networks import R2D2MLPNetwork
 from acme_amd.utils import counting, loggers
+
+
+def _check_raw(observation) -> None:
+    if hasattr(observation, "observation"):
+        raise ValueError("R2D2MLPNetwork takes the raw observation, not an OAR "
+                         "(leave the environment unwrapped)")
 
 
 class R2D2Policy:
@@ -50,17 +61,21 @@ class R2D2Policy:
         self._c = torch.zeros(1, H, dtype=torch.float32, device=dev)
         self._action = torch.zeros(1, dtype=torch.int32, device=dev)
         self._out = [None, self._action, self._h, self._c]
+        self._mlp = isinstance(network, R2D2MLPNetwork)
 
     def initial_state(self, batch_size: int = 1):
         return self._network.initial_state(batch_size)
 
     def __call__(self, observation, state=None, store_state: bool = True):
-        """observation: the unbatched OAR.  state: an LSTMState [1, H] to start from (an
-        episode's first call), or None to continue from the state on the device.  Returns
-        (action, the LSTMState [1, H] that went into the step, or None without
-        store_state)."""
+        """observation: the unbatched OAR (the raw observation with an R2D2MLPNetwork).
+        state: an LSTMState [1, H] to start from (an episode's first call), or None to
+        continue from the state on the device.  Returns (action, the LSTMState [1, H] that
+        went into the step, or None without store_state)."""
         from acme_amd.networks import LSTMState
-        _learner.check_oar(observation, "R2D2AtariNetwork")
+        if self._mlp:
+            _check_raw(observation)
+        else:
+            _learner.check_oar(observation, "R2D2AtariNetwork")
         n, t = self._native, self._convert
         prev = None
         if state is not None:
@@ -72,10 +87,14 @@ class R2D2Policy:
                                  np.array(cell, np.float32).reshape(1, -1))
         elif store_state:
             prev = LSTMState(self._h.cpu().numpy(), self._c.cpu().numpy())
-        n.q_step(t(observation.observation, self._dt).reshape(1, -1),
-                 t(observation.action, torch.int32).reshape(1),
-                 t(observation.reward, torch.float32).reshape(1), self._h, self._c,
-                 epsilon=self.epsilon, seed=self.seed, step=self.calls, out=self._out)
+        if self._mlp:
+            n.q_step(t(observation, self._dt).reshape(1, -1), self._h, self._c,
+                     epsilon=self.epsilon, seed=self.seed, step=self.calls, out=self._out)
+        else:
+            n.q_step(t(observation.observation, self._dt).reshape(1, -1),
+                     t(observation.action, torch.int32).reshape(1),
+                     t(observation.reward, torch.float32).reshape(1), self._h, self._c,
+                     epsilon=self.epsilon, seed=self.seed, step=self.calls, out=self._out)
         self.calls += 1
         return np.int32(self._action.item()), prev
 
@@ -110,20 +129,28 @@ class R2D2Learner(_learner.PlaneLearner):
         self._burn_in = int(burn_in_length)
         self._T = int(sequence_length)
         B = batch_size or getattr(dataset, "batch_size", None) or 32
-        self._native = NativeR2D2(
+        common = dict(
             num_actions=network.num_actions, max_batch=B, max_sequence_length=self._T,
-            burn_in_length=self._burn_in, torso=network.torso, obs_dim=network.obs_dim,
-            lstm_size=network.lstm_size, head_size=network.head_size, n_step=n_step,
-            discount=discount, importance_sampling_exponent=importance_sampling_exponent,
+            burn_in_length=self._burn_in, obs_dim=network.obs_dim, lstm_size=network.lstm_size,
+            n_step=n_step, discount=discount,
+            importance_sampling_exponent=importance_sampling_exponent,
             max_replay_size=max_replay_size, max_priority_weight=max_priority_weight,
             target_update_period=target_update_period, learning_rate=learning_rate,
             store_lstm_state=store_lstm_state, device=device)
+        # The native learner by network type; the MLP network's has no planes and no guard.
+        self._mlp = isinstance(network, R2D2MLPNetwork)
+        if self._mlp:
+            self._native = NativeR2D2MLP(hidden=network.hidden, **common)
+        else:
+            self._native = NativeR2D2(torso=network.torso, head_size=network.head_size, **common)
         self._native.set_params(network.init(seed),
                                 target_network.init(seed + 1 if target_seed is None
                                                     else target_seed))
         self._init_bookkeeping(counter, logger)
 
     def step(self):
+        if self._mlp:
+            return self._step_mlp()
         skipped = self._check_guard()
         sample = next(self._iterator)
         data = sample.data
@@ -144,15 +171,40 @@ class R2D2Learner(_learner.PlaneLearner):
                                            priorities=n.priorities[:B], **kw)
         self._finish_step({"loss": n.loss[0]}, skipped)
 
+    def _step_mlp(self):
+        sample = next(self._iterator)
+        data = sample.data
+        _check_raw(data.observation)
+        n = self._native
+        B, T = int(data.action.shape[0]), int(data.action.shape[1])
+        h0 = c0 = None
+        if n.store_lstm_state:
+            h0, c0 = _learner.initial_core_state(data.extras)
+        keys, probs = sample.info.key, sample.info.probability
+        if probs.dim() == 2:  # per-step info of a sequence item: the item's own
+            keys, probs = keys[:, 0], probs[:, 0]
+        c = lambda x, t: x.reshape(B, T).to(t).contiguous()  # noqa: E731
+        n.step(data.observation.reshape(B, T, -1).to(torch.float32).contiguous(),
+               c(data.action, torch.int32), c(data.reward, torch.float32),
+               c(data.discount, torch.float32), probs.to(torch.float64).contiguous(), h0, c0)
+        if self._client is not None:  # learning.py:195-198; every step applies its update
+            self._client.update_priorities(table=adders.DEFAULT_PRIORITY_TABLE, keys=keys,
+                                           priorities=n.priorities[:B])
+        self._finish_step({"loss": n.loss[0]})
+
     # ------------------------------------------------------------------ acting
     def q_step(self, observation, prev_action, prev_reward, hidden, cell, *,
                epsilon: float = 0.0, seed: int = 0, step: int = 0, use_target: bool = False):
         """Batched network step for actors (numpy in, numpy out): (q [rows, A], actions
-        [rows], hidden, cell), the actions epsilon-greedy draws from (seed, step, row)."""
+        [rows], hidden, cell), the actions epsilon-greedy draws from (seed, step, row).  An
+        R2D2MLPNetwork ignores the previous action and reward."""
         n = self._native
-        out = n.q_step(*_learner.acting_inputs(
+        args = _learner.acting_inputs(
             _learner.to_device(n.device), self._obs_dtype, observation, prev_action, prev_reward,
-            hidden, cell), epsilon=epsilon, seed=seed, step=step, use_target=use_target)
+            hidden, cell)
+        if self._mlp:
+            args = (args[0],) + args[3:]
+        out = n.q_step(*args, epsilon=epsilon, seed=seed, step=step, use_target=use_target)
         return tuple(x.cpu().numpy() for x in out)
 
     def make_policy(self, epsilon: float, seed: int = 0) -> "R2D2Policy":
@@ -165,3 +217,20 @@ class R2D2Learner(_learner.PlaneLearner):
         # As the TF learner (learning.py:216-217): one collection, names ignored.
         p = self._native.get_params("params")
         return [[p[k] for k in sorted(p)]]
+
+    def save(self) -> Dict:
+        if not self._mlp:
+            return super().save()
+        n = self._native
+        return {"network": n.get_params("params"), "target_network": n.get_params("target"),
+                "optimizer": {"m": n.get_params("m"), "v": n.get_params("v"),
+                              "step": n.num_steps},
+                "num_steps": n.num_steps}
+
+    def restore(self, state: Dict):
+        if not self._mlp:
+            return super().restore(state)
+        n = self._native
+        n.set_params(state["network"], state["target_network"])
+        self._restore_moments(state["optimizer"])
+        n.num_steps = int(state["num_steps"])

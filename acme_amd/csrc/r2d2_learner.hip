@@ -43,6 +43,7 @@
 #include "launch.h"
 #include "learner_common.h"
 #include "profiler.h"
+#include "r2d2_transforms.h"
 #include "torso.h"
 #include "lstm.h"
 #include "recurrent_common.h"
@@ -188,31 +189,6 @@ struct R2Loss {
   double* prio;    // [B]
   double* loss_part;  // [B]: w_b * 0.5 sum_t errors^2
 };
-
-__device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : x); }
-
-// IEEE (correctly rounded) f32 square root and quotient: evaluated in f64 and rounded once
-// to f32, which is exact for both (53 >= 2 x 24 + 2 bits: the double rounding is innocuous).
-// (__fsqrt_rn without OCML_BASIC_ROUNDED_OPERATIONS is the native approximation.)
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)__builtin_sqrt((double)x); }
-__device__ __forceinline__ float div_rn(float x, float y) { return (float)((double)x / (double)y); }
-
-// _signed_hyperbolic_tx (losses/r2d2.py:172-174): sign(x) (sqrt(|x| + 1) - 1) + eps x, in
-// TF's f32 operation order, no contraction.
-__device__ __forceinline__ float hyperbolic(float x) {
-#pragma clang fp contract(off)
-  const float s = sqrt_rn(fabsf(x) + 1.f) - 1.f;
-  return sgnf(x) * s + 1e-3f * x;
-}
-
-// _signed_parabolic_tx (:177-180): z = sqrt(1 + 4 eps (eps + 1 + |x|)) / 2 / eps - 1 / 2 / eps
-// (Python folds eps + 1 and 4 eps and 1 / 2 / eps into f32 constants); sign(x) (z^2 - 1).
-__device__ __forceinline__ float parabolic(float x) {
-#pragma clang fp contract(off)
-  const float t = 0.004f * (1.001f + fabsf(x));
-  const float z = div_rn(sqrt_rn(1.f + t) * 0.5f, 1e-3f) - 500.f;  // x / 2 exact as x * 0.5
-  return sgnf(x) * (z * z - 1.f);
-}
 
 // tf.argmax (first maximal index) of online q row (t, b).
 __device__ __forceinline__ int greedy(const R2Loss& a, int t, int b) {

@@ -1839,6 +1839,115 @@ class NativeR2D2(_PlaneState, _NativeLearner):
         return tuple(out)
 
 
+class NativeR2D2MLP(_NativeLearner):
+    """acme_r2d2_mlp learner (networks.R2D2MLPNetwork: LSTM -> MLP on raw float observations) +
+    its flat buffers (params, target, grads, Adam m / v): the whole R2D2 step in three
+    launches, the acting step in one.  Exact f32: no planes, no step guard, no skip word."""
+
+    _prefix, _tag = "acme_r2d2_mlp", "r2d2_mlp"
+    torso = "lstm_mlp"
+
+    def __init__(self, *, obs_dim: int, lstm_size: int, hidden: Sequence[int], num_actions: int,
+                 max_batch: int, max_sequence_length: int, burn_in_length: int, n_step: int = 5,
+                 discount: float = 0.99, importance_sampling_exponent: float = 0.2,
+                 max_replay_size: int = 1_000_000, max_priority_weight: float = 0.9,
+                 target_update_period: int = 100, learning_rate: float = 1e-3,
+                 adam_beta1: float = 0.9, adam_beta2: float = 0.999, adam_epsilon: float = 1e-3,
+                 store_lstm_state: bool = True, device=None):
+        """Defaults are R2D2Learner's (learning.py:47-66; snt.Adam epsilon 1e-3, :78)."""
+        _lib.require_gpu()
+        if len(hidden) > _lib.R2D2_MLP_MAX_HIDDEN:
+            raise ValueError(f"hidden takes at most {_lib.R2D2_MLP_MAX_HIDDEN} layer sizes")
+        cfg = _lib.R2D2MLPConfig()
+        cfg.obs_dim, cfg.num_actions = int(obs_dim), int(num_actions)
+        cfg.max_batch, cfg.max_sequence_length = int(max_batch), int(max_sequence_length)
+        cfg.burn_in_length, cfg.lstm_size = int(burn_in_length), int(lstm_size)
+        cfg.num_hidden = len(hidden)
+        for i, s in enumerate(hidden):
+            cfg.hidden[i] = int(s)
+        cfg.n_step = int(n_step)
+        cfg.store_lstm_state = 1 if store_lstm_state else 0
+        cfg.target_update_period = int(target_update_period)
+        cfg.max_replay_size = int(max_replay_size)
+        cfg.max_priority_weight = max_priority_weight
+        cfg.importance_sampling_exponent = importance_sampling_exponent
+        cfg.discount, cfg.learning_rate = discount, learning_rate
+        cfg.adam_beta1, cfg.adam_beta2, cfg.adam_epsilon = adam_beta1, adam_beta2, adam_epsilon
+        self.obs_dim, self.hidden = int(obs_dim), tuple(int(h) for h in hidden)
+        self.num_actions, self.lstm_size = int(num_actions), int(lstm_size)
+        self.max_batch, self.max_sequence_length = int(max_batch), int(max_sequence_length)
+        self.burn_in_length = int(burn_in_length)
+        self.store_lstm_state = bool(store_lstm_state)
+        self._create(cfg, device)
+        T, B = self.max_sequence_length, self.max_batch
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._errors = torch.zeros(max(T - self.burn_in_length - 1, 1) * B, dtype=torch.float32,
+                                   device=self.device)
+        self._last = (1, B)
+        self.priorities = torch.zeros(B, dtype=torch.float64, device=self.device)
+
+    errors = NativeR2D2.errors
+
+    def set_params(self, params: Dict[str, np.ndarray], target: Dict[str, np.ndarray]) -> None:
+        super().set_params(params, target)
+
+    def step(self, observation, action, reward, discount, probabilities, h0=None, c0=None,
+             stream=None):
+        """Batch-major device tensors: observation float32 [B, T, obs_dim], action int32 and
+        reward / discount float32 [B, T], the sample's probabilities [B] (f64) and the core
+        state at t = 0 (h0 / c0 [B, H] views with unit inner stride; ignored with
+        store_lstm_state=False).  Loss, errors [T - burn_in - 1, B] and priorities [B] land in
+        .loss / .errors / .priorities."""
+        # The network has no previous action or reward: the checked [B, T] stand-ins are the
+        # action and reward themselves, and the struct's two pointers are cleared below.
+        b = self._sequence_batch(observation, action, reward, action, reward, discount, h0, c0,
+                                 core_state=self.store_lstm_state)
+        B, T = int(b.batch), int(b.sequence_length)
+        if observation.numel() != B * T * self.obs_dim:
+            raise ValueError(f"observation has shape {tuple(observation.shape)}, expected "
+                             f"[{B}, {T}, {self.obs_dim}]")
+        if not (probabilities.is_cuda and probabilities.dtype == torch.float64
+                and probabilities.is_contiguous() and probabilities.numel() == B):
+            raise ValueError(f"probabilities must be a contiguous float64 [{B}] device tensor")
+        b.prev_action = b.prev_reward = None  # not inputs of this network
+        o = _lib.R2D2Outputs()
+        o.loss, o.errors, o.priorities = ptr(self.loss), ptr(self._errors), ptr(self.priorities)
+        self._last = (T - self.burn_in_length - 1, B)
+        check(lib().acme_r2d2_mlp_step(self._h, ctypes.byref(b), ptr(probabilities),
+                                       ctypes.byref(o), stream_ptr(stream)), "r2d2_mlp step")
+
+    def q_step(self, obs, h, c, *, epsilon: float, seed: int, step: int,
+               use_target: bool = False, stream=None, out=None):
+        """One network step for `rows` actors (acme_r2d2_mlp_q_step): device tensors obs
+        [rows, obs_dim], core state h / c [rows, H] float32 views with unit inner stride and one
+        row stride.  Returns (q [rows, A], actions int32 [rows], h, c), the epsilon-greedy
+        actions drawn from (seed, step, row).  out: four device tensors (or None to skip an
+        output) to write into; the state outputs may be contiguous h and c themselves."""
+        rows, H = int(h.shape[0]), self.lstm_size
+        for name, t in (("h", h), ("c", c)):
+            if (t.dtype != torch.float32 or tuple(t.shape) != (rows, H) or t.stride(1) != 1
+                    or not t.is_cuda):
+                raise ValueError(f"{name} must be a float32 [{rows}, {H}] device tensor with "
+                                 "unit inner stride")
+        if h.stride(0) != c.stride(0):
+            raise ValueError("h and c must share a row stride")
+        if not (obs.is_cuda and obs.dtype == torch.float32
+                and obs.numel() == rows * self.obs_dim):
+            raise ValueError(f"obs must be a float32 device tensor of {rows * self.obs_dim} "
+                             "elements")
+        if out is None:
+            out = self._acting_outputs(rows, torch.int32)
+        for o in out[2:]:
+            if o is not None and not o.is_contiguous():
+                raise ValueError("the state outputs must be contiguous [rows, H] tensors")
+        check(lib().acme_r2d2_mlp_q_step(
+            self._h, ptr(obs.contiguous()), ptr(h), ptr(c), int(h.stride(0)), rows,
+            1 if use_target else 0, float(epsilon), int(seed) & (2 ** 64 - 1),
+            int(step) & (2 ** 64 - 1), *[ptr(o) for o in out], stream_ptr(stream)),
+            "r2d2_mlp q_step")
+        return tuple(out)
+
+
 def epsilon_greedy(q: torch.Tensor, epsilon: float, seed: int, step: int,
                    stream=None) -> torch.Tensor:
     """Epsilon-greedy actions (int32 [rows]) of a contiguous float32 [rows, A] device tensor:

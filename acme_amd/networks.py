@@ -656,3 +656,50 @@ class R2D2AtariNetwork:
 
     init = IMPALAAtariNetwork.init
     initial_state = IMPALAAtariNetwork.initial_state
+
+
+# ------------------------------------------------------------------ R2D2 (vector observations)
+
+
+@dataclasses.dataclass(frozen=True)
+class R2D2MLPNetwork:
+    """snt.DeepRNN([snt.Flatten(), snt.LSTM(lstm_size), snt.nets.MLP(hidden + (num_actions,))])
+    (acme/agents/tf/r2d2/agent_test.py:28-45) on raw float observations: the LSTM on the
+    flattened observation, ReLU between the MLP's layers and none after the last, whose output
+    is q.  No OAR embedding and no duelling head: the previous action and reward are not
+    inputs."""
+
+    obs_dim: int
+    lstm_size: int
+    hidden: Tuple[int, ...]
+    num_actions: int
+    obs_dtype: str = dataclasses.field(default="float32", init=False)
+    torso: str = dataclasses.field(default="lstm_mlp", init=False)
+
+    def __init__(self, obs_dim: int, lstm_size: int = 20, hidden: Sequence[int] = (50, 50),
+                 num_actions: int = 0):
+        object.__setattr__(self, "obs_dim", int(obs_dim))
+        object.__setattr__(self, "lstm_size", int(lstm_size))
+        object.__setattr__(self, "hidden", tuple(int(h) for h in hidden))
+        object.__setattr__(self, "num_actions", int(num_actions))
+        object.__setattr__(self, "obs_dtype", "float32")
+        object.__setattr__(self, "torso", "lstm_mlp")
+        if not self.hidden:
+            raise ValueError("R2D2MLPNetwork needs at least one hidden MLP layer")
+        if self.num_actions < 1:
+            raise ValueError("R2D2MLPNetwork needs num_actions >= 1")
+
+    def tensor_shapes(self):
+        H, d = self.lstm_size, self.lstm_size
+        out = [("lstm/w_i", (self.obs_dim, 4 * H)), ("lstm/w_h", (H, 4 * H)), ("lstm/b", (4 * H,))]
+        for i, h in enumerate(self.hidden + (self.num_actions,)):
+            out += [(f"mlp/linear_{i}/w", (d, h)), (f"mlp/linear_{i}/b", (h,))]
+            d = h
+        return out
+
+    @property
+    def obs_shape(self) -> Tuple[int, ...]:
+        return (self.obs_dim,)
+
+    init = IMPALAAtariNetwork.init
+    initial_state = IMPALAAtariNetwork.initial_state

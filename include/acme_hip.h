@@ -1345,6 +1345,96 @@ int acme_r2d2_q_step(acme_r2d2* l, const void* obs, const int32_t* prev_action,
 int acme_r2d2_debug_buffer(const acme_r2d2* l, const char* name, const float** out,
                            int64_t* count);
 
+/* ------------------------------------------------------ R2D2 / LSTM + MLP -- */
+/* R2D2Learner._step (acme/agents/tf/r2d2/learning.py:112-200) with the network of the
+ * reference's own R2D2 test (acme/agents/tf/r2d2/agent_test.py:28-45):
+ * snt.DeepRNN([snt.Flatten(), snt.LSTM(lstm_size), snt.nets.MLP(hidden + [num_actions])]) on
+ * raw float observations: no OAR embedding, no duelling head; the MLP's output is q (ReLU
+ * between its layers, none after the last).  Flat buffer: lstm/{w_i,w_h,b} (gates i, f, g, o;
+ * the forget bias folded into b), then mlp/linear_i/{w,b}.  The loss, the importance weights,
+ * the priorities, snt.Adam and the target copy are acme_r2d2's.  Everything is f32: no planes,
+ * no step guard, no float atomics.
+ *
+ * Limits (acme_r2d2_mlp_create refuses anything else, naming the field; they keep a tile of
+ * 16 sequences of both networks in LDS, so one fused path serves every accepted shape):
+ *   obs_dim and every hidden[i] in [1, ACME_R2D2_MLP_MAX_WIDTH] (any value);
+ *   num_hidden in [1, ACME_R2D2_MLP_MAX_HIDDEN];
+ *   lstm_size in [1, ACME_R2D2_MLP_MAX_LSTM] (any value);
+ *   num_actions in [1, ACME_R2D2_MLP_MAX_ACTIONS];
+ *   max_batch in [1, ACME_R2D2_MLP_MAX_ROWS];
+ *   max_sequence_length in [2, ACME_R2D2_MLP_MAX_T];
+ *   burn_in_length in [0, max_sequence_length - 2]; n_step >= 1. */
+#define ACME_R2D2_MLP_MAX_WIDTH 256
+#define ACME_R2D2_MLP_MAX_HIDDEN 3
+#define ACME_R2D2_MLP_MAX_LSTM 128
+#define ACME_R2D2_MLP_MAX_ACTIONS 64
+#define ACME_R2D2_MLP_MAX_ROWS 1024
+#define ACME_R2D2_MLP_MAX_T 128
+
+typedef struct acme_r2d2_mlp acme_r2d2_mlp;
+
+typedef struct acme_r2d2_mlp_config {
+  int32_t obs_dim;
+  int32_t num_actions;
+  int32_t max_batch;            /* sequences per step (B), and rows of a q step */
+  int32_t max_sequence_length;  /* T = burn_in + trace + 1 */
+  int32_t burn_in_length;
+  int32_t lstm_size;
+  int32_t num_hidden;
+  int32_t hidden[ACME_R2D2_MLP_MAX_HIDDEN];
+  int32_t n_step;               /* bootstrap_n (learning.py:65: 5) */
+  int32_t store_lstm_state;     /* 1: core state from extras (h0 / c0), 0: zeros */
+  int32_t target_update_period;
+  int32_t reserved;
+  int64_t max_replay_size;      /* N of the importance weights */
+  double max_priority_weight;   /* eta; eta and 1 - eta are rounded to f32 from double */
+  double importance_sampling_exponent;  /* beta: the f64 weights' exponent */
+  float discount;
+  float learning_rate, adam_beta1, adam_beta2, adam_epsilon;
+} acme_r2d2_mlp_config;
+
+int acme_r2d2_mlp_create(const acme_r2d2_mlp_config* cfg, acme_r2d2_mlp** out);
+int acme_r2d2_mlp_destroy(acme_r2d2_mlp* l);
+int64_t acme_r2d2_mlp_flat_size(const acme_r2d2_mlp* l);
+int32_t acme_r2d2_mlp_num_tensors(const acme_r2d2_mlp* l);
+int acme_r2d2_mlp_tensor_info(const acme_r2d2_mlp* l, int32_t i, int64_t* offset, int64_t* numel,
+                              int32_t* ndim, int64_t* shape4, const char** name);
+/* Flat device buffers of acme_r2d2_mlp_flat_size floats each (gradients and moments zeroed). */
+int acme_r2d2_mlp_bind(acme_r2d2_mlp* l, float* params, float* target, float* grads,
+                       float* adam_m, float* adam_v);
+/* One learner step in three launches on `stream`, whatever T and the depth, no host
+ * synchronisation.  batch->observation is f32 [B, T, obs_dim]; prev_action, prev_reward and
+ * behaviour_logits are not read (may be NULL); h0 / c0 are read with store_lstm_state only.
+ * burn_in_length + 2 <= T <= max_sequence_length.  Launch 1: one workgroup per 16 sequences
+ * unrolls the online and the target network over T from the core state, reduces the suffix's
+ * q rows to the loss's scalars, computes the transformed n-step double-Q loss of its sequences
+ * (acme_r2d2_step's f32 operation order), the priorities and the backward through time down
+ * to the end of the burn-in.  Launch 2: every weight and bias gradient over the
+ * (T - burn_in) B suffix rows in a fixed order.  Launch 3: the loss, snt.Adam at
+ * t = num_steps + 1, then target <- online when num_steps % target_update_period == 0.
+ * Outputs as acme_r2d2_step's.  The same step from the same state gives the same bits. */
+int acme_r2d2_mlp_step(acme_r2d2_mlp* l, const acme_sequence_batch* batch,
+                       const double* probabilities, const acme_r2d2_outputs* out, void* stream);
+/* One network step for `rows` independent actors in one launch (1 <= rows <= max_batch) on
+ * the online parameters, or the target's with use_target != 0: obs [rows, obs_dim], core state
+ * rows h / c at h + i * state_stride (state_stride >= lstm_size).  Outputs, each optional:
+ * q [rows, A], actions [rows] (acme_epsilon_greedy's selection on each row of q from (seed,
+ * step_counter, row)), the next state h_out / c_out [rows, lstm_size]; h_out may be h and
+ * c_out may be c when state_stride == lstm_size (a workgroup reads its rows' state before it
+ * writes it).  Changes no learner state. */
+int acme_r2d2_mlp_q_step(acme_r2d2_mlp* l, const float* obs, const float* h, const float* c,
+                         int64_t state_stride, int64_t rows, int32_t use_target, double epsilon,
+                         uint64_t seed, uint64_t step_counter, float* q, int32_t* actions,
+                         float* h_out, float* c_out, void* stream);
+int64_t acme_r2d2_mlp_num_steps(const acme_r2d2_mlp* l);
+int acme_r2d2_mlp_set_num_steps(acme_r2d2_mlp* l, int64_t n);
+/* Internal device workspaces (tests) of the last step over B sequences of T, L = T - burn_in:
+ * "q" and "target_q" [B * T, A] batch-major rows (the L suffix steps of a sequence are
+ * written), "g" [L, B] time-major d loss / d q[a], "h" [B * T, H] batch-major (steps from
+ * burn_in - 1 on). */
+int acme_r2d2_mlp_debug_buffer(const acme_r2d2_mlp* l, const char* name, const float** out,
+                               int64_t* count);
+
 /* ----------------------------------------------------------- elementwise ops -- */
 
 /* Epsilon-greedy actions of q [rows, num_actions] (device, f32; num_actions in [1, 1024],
